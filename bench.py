@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - throughput of the ssr_eval DSP / metric hot path on MI355X.
 
-    python bench.py [--config cfg2|cfg3|cfg4|cfg5] [--gpus N --steps K --warmup W]
+    python bench.py [--config cfg2|cfg3|cfg4|cfg5] [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no torchrun environment spawns the N ranks itself (one process per GPU, RCCL) and fails if
@@ -208,6 +208,10 @@ class Cfg2:
         torch.sum(out[:, 0::3], dim=0, out=self.agg[:2])
         return self.agg
 
+    def outputs(self):
+        """What the last step computed, as its caller receives it: the per-pair LSD and SSIM (the mask leaves the SISpec columns NaN)."""
+        return {"lsd": self.batch.out[:, 0], "ssim": self.batch.out[:, 3]}
+
     def config(self, world):
         a = self.a
         return {"workload": "%s: %d synthetic 48 kHz 4 s float32 (est, target) pairs per GPU resident in HBM, STFT n_fft=%d "
@@ -326,6 +330,12 @@ class Cfg3:
         acc = self.batch.run(self.B.M_ALL).sum((0, 1))
         torch.cat([acc, self.cnt], out=self.agg)
         return self.agg
+
+    def outputs(self):
+        """The four metrics [target, cutoff] of the last step and the low-passed estimates it scored ([cutoff x target, samples], key-major)."""
+        out = self.batch.out
+        return {"lsd": out[..., 0], "log_sispec": out[..., 1], "sispec": out[..., 2], "ssim": out[..., 3],
+                "lowpassed": self.est.view(-1, N_SAMPLES)}
 
     def config(self, world):
         a = self.a
@@ -508,6 +518,10 @@ class Cfg5:
         torch.cat([out[:, 0].sum(0, keepdim=True), self.cnt], out=self.agg)
         return self.agg
 
+    def outputs(self):
+        """The 48 kHz signals the last step's resampling chain produced and their LSD against the targets."""
+        return {"resampled": self.chain.out.view(-1, N_SAMPLES), "lsd": self.batch.out[:, 0]}
+
     def config(self, world):
         a = self.a
         return {"workload": "cfg-5: %d synthetic utterances of 64,000 float32 samples @ 16 kHz per GPU resident in HBM: polyphase "
@@ -679,6 +693,12 @@ class Cfg4:
             torch.sum(self.gathered[:, self.cap:], dim=0, out=self.buf)           # ranks added in rank order, on every rank alike
         return self.buf
 
+    def outputs(self):
+        """This rank's per-utterance metrics of the last step (in the order of `mine`) and their global utterance indices."""
+        out = self.fake_out if self.fake else self.batch.out
+        return {"utterance_index": self.pack[:len(self.mine), 0], "lsd": out[:, 0], "log_sispec": out[:, 1], "sispec": out[:, 2],
+                "ssim": out[:, 3]}
+
     def job_means(self, agg):
         """mean over speakers of the per-speaker means (ssr_eval/eval.py:200-216), from the all-reduced buffer."""
         a = np.asarray(agg).reshape(self.n_spk, 5)
@@ -760,6 +780,9 @@ class Skeleton:
     def step(self):
         self.agg[0], self.agg[1] = float(self.rank + 1), 1.0
         return self.agg
+
+    def outputs(self):
+        return {}
 
     def config(self, world):
         return {"workload": "skeleton", "parallelism": "x%d" % world}
@@ -869,6 +892,36 @@ def cpu_baseline(wl, budget_s=24.0):
     if err:
         out["pool_error"] = err
     return out, vals
+
+
+# ----------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, so that two builds can be compared output for output
+DUMP_CAP_BYTES = 64 << 20
+DUMP_SEED = 20220328
+
+
+def dump_outputs(arrays, out_dir):
+    """arrays: name -> tensor.  Writes <out_dir>/<name>.npy (float32 stays float32, everything else becomes float64), at most
+    DUMP_CAP_BYTES in all: a 2-D array too large for its share is cut to a fixed, seeded sample of its rows (sorted; the same rows
+    for the same shape on every run).  Returns what was written, for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    nbytes = {k: t.numel() * (4 if t.dtype == torch.float32 else 8) for k, t in arrays.items()}
+    small = [k for k in arrays if nbytes[k] <= DUMP_CAP_BYTES // len(arrays)]
+    share = (DUMP_CAP_BYTES - sum(nbytes[k] for k in small)) // max(1, len(arrays) - len(small))
+    info = {}
+    for name, t in arrays.items():
+        shape, rows = list(t.shape), None
+        if name not in small and nbytes[name] > share:
+            if t.dim() != 2:
+                raise ValueError("dump_outputs: %s %s exceeds its %d-byte share and is not a 2-D array of rows" % (name, shape, share))
+            keep = share // (nbytes[name] // t.shape[0])
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        x = t.detach().cpu().numpy()
+        x = np.ascontiguousarray(x if x.dtype in (np.float32, np.float64) else x.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        info[name] = {"shape": shape, "dtype": str(x.dtype), "rows_sampled": None if rows is None else int(len(rows))}
+    return info
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -1024,7 +1077,11 @@ def run(a):
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE is %d (launch with --nproc-per-node == --gpus)" % (a.gpus, world))
     if a.cpu_skeleton:
         dev, sync, backend = torch.device("cpu"), (lambda: None), "gloo"
+        # torch's barrier() looks up the host's accelerator first, which initialises HIP: on a GPU host every rank of this CPU
+        # self-test would hold the device open.  A one-element all-reduce waits for every rank just the same.
+        barrier = lambda: dist.all_reduce(torch.zeros(1))
     else:
+        barrier = dist.barrier
         assert torch.cuda.is_available(), "bench.py needs an MI355X"
         if torch.cuda.device_count() <= local_rank and not a.share_gpu:
             raise SystemExit("bench.py: rank %d has no device (%d visible)" % (local_rank, torch.cuda.device_count()))
@@ -1072,14 +1129,14 @@ def run(a):
         drain()
         sync()
         if world > 1:
-            dist.barrier()
+            barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
             agg = step()
         drain()
         sync()
         if world > 1:
-            dist.barrier()
+            barrier()
         dt = time.perf_counter() - t0
         if world > 1:
             tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -1093,6 +1150,10 @@ def run(a):
     per_rank = []
     elapsed, agg = timed(wl, a.steps, a.warmup)
     per_rank_ms = [round(t / a.steps * 1e3, 4) for t in per_rank]
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # before anything else runs the workload's batches: their output buffers still hold the last timed step
+        dumped = dump_outputs(dict(wl.outputs(), step_sums=torch.from_numpy(agg)), a.dump_outputs)
     # weak scaling: every rank owns units_per_step units; strong scaling: units_per_step is the whole job's
     value = wl.units_per_step * (1 if strong else joined) * a.steps / elapsed
     means = wl.job_means(agg) if hasattr(wl, "job_means") else (agg[:-1] / agg[-1]).tolist()
@@ -1115,12 +1176,14 @@ def run(a):
         if getattr(wl_cls, "own_collectives", False) and world > 1:
             wl.report(a)                                                # its report times the collectives: every rank takes part
         if world > 1:
-            dist.barrier()
+            barrier()
             dist.destroy_process_group()
         return
 
     roofline, extra = wl.report(a)
     extra["job_means"] = means
+    if dumped is not None:
+        extra["dumped_outputs"] = dumped
     extra["allreduce_payload_bytes_per_step"] = payload if world > 1 else 0
     if world > 1:
         # what a reader of the scaling curve needs to trust it: the ranks that joined, each rank's own clock, the library underneath
@@ -1149,13 +1212,13 @@ def run(a):
         extra.update(side_figures(a, dev))
 
     line = {"metric": wl_cls.metric, "value": round(value, 2), "unit": wl_cls.unit, "n_gpus": joined,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 4), "higher_is_better": True,
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": float("%.6g" % (elapsed / a.steps * 1e3)), "higher_is_better": True,
             "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": a.precision, "data": "synthetic",
             "config": _config_of(wl_cls, a, joined),
             "roofline": roofline, "cpu_baseline": cpu, "extra": extra}
     print(json.dumps(line), flush=True)
     if world > 1:
-        dist.barrier()
+        barrier()
         dist.destroy_process_group()
 
 
@@ -1194,9 +1257,14 @@ def parse(argv=None):
                          "all-reduce (the collective BASELINE cfg-4 names)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-side", action="store_true", help="skip the cfg3 / cfg5 / API-true / end-to-end side figures")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (rank 0's arrays, 64 MB at most)")
     ap.add_argument("--_cpu-skeleton", dest="cpu_skeleton", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--_share-gpu", dest="share_gpu", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def main():

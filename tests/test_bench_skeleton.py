@@ -111,3 +111,32 @@ def test_true_world_size_8_launcher_and_accounting_gloo():
             assert d["extra"]["allgather_rows_received"] == 2937
         means[coll] = np.array(d["extra"]["job_means"])
     np.testing.assert_allclose(means["allreduce"], means["allgather"], rtol=1e-12, atol=1e-12)
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """--dump-outputs DIR: after the timed steps, what the last step computed as DIR/<name>.npy (float32 / float64, 64 MB at most),
+    the same bits from run to run; --steps is the number of timed steps and must be at least 1.  cfg-4 on CPU (gloo, one rank):
+    the step's "metrics" are functions of the global utterance index, so every dumped row can be checked."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = _bench("--config", "cfg4", "--gpus", "1", "--steps", "3", "--warmup", "1", "--_cpu-skeleton", "--dump-outputs", str(out))
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        names = sorted(p.name for p in out.iterdir())
+        assert names == sorted(n + ".npy" for n in d["extra"]["dumped_outputs"])
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+        runs.append({n[:-4]: np.load(out / n) for n in names})
+    a = runs[0]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    gi = a["utterance_index"]
+    assert sorted(gi.tolist()) == list(range(2937))
+    np.testing.assert_array_equal(a["lsd"], gi)
+    np.testing.assert_array_equal(a["log_sispec"], 0.5 * gi)
+    np.testing.assert_allclose(a["ssim"], np.cos(gi), rtol=0, atol=1e-15)       # (torch and NumPy cosines: last bits)
+    assert a["step_sums"].shape == (8, 5) and a["step_sums"][:, 4].sum() == 2937
+    assert all(np.array_equal(a[n], runs[1][n]) for n in a)
+    r = _bench("--steps", "0", "--_cpu-skeleton")
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -202,7 +202,7 @@ def _worker_decode_tree(rank, world, port, root, out_dir):
 
 def test_world_size_8_file_tree_reader_threads_within_the_affinity(tmp_path):
     """EIGHT gloo ranks decode their round-robin shards of one wav tree (the host stage of evaluate(): the kernels need a GPU,
-    tests/test_gpu_configs.py runs the whole evaluate() under eight processes) - every rank's pool is its share of the cores, the
+    tests/test_gpu_configs.py runs the whole evaluate() under five processes that share one device) - every rank's pool is its share of the cores, the
     job as a whole starts no more reader threads than max(ranks, usable cores), and the gathered table is the one-process one."""
     sys.path.insert(0, ROOT)
     from ssr_eval_amd.io import write_wav, read_audio, usable_cores

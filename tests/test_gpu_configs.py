@@ -633,10 +633,15 @@ def test_evaluate_sharded_two_processes_equals_single_process(tmp_path):
     assert list(a) == list(c) and max(abs(a[k] - c[k]) / max(abs(a[k]), 1e-300) for k in a) <= 1e-12
 
 
-def test_evaluate_sharded_eight_processes_share_the_host_cores(tmp_path):
-    """the driver's 8-rank launch in small - EIGHT processes (gloo, sharing cuda:0) run the real evaluate() on one
-    wav tree: every rank returns the single-process result (1e-12), and the job as a whole starts no more reader threads than
-    max(ranks, the cores its affinity mask / cgroup grant) - each rank's pool is its share (ssr_eval_amd.io.decode_threads)."""
+RANKS_SHARING_THE_GPU = 5     # + this test's own process: at most six processes may hold the device of a shared GPU host at once
+
+
+def test_evaluate_sharded_five_processes_share_the_host_cores(tmp_path):
+    """the driver's multi-rank launch in small - FIVE processes (gloo, sharing cuda:0) run the real evaluate() on
+    one wav tree: every rank returns the single-process result (1e-12), and the job as a whole starts no more reader threads than
+    max(ranks, the cores its affinity mask / cgroup grant) - each rank's pool is its share (ssr_eval_amd.io.decode_threads).
+    Five ranks, not the driver's eight: with the test's own process that is the most processes a shared device may have open at
+    once; eight ranks' share of the cores is covered on CPU (test_dist_gloo.py::test_world_size_8_file_tree_reader_threads_within_the_affinity)."""
     from ssr_eval_amd.io import write_wav
     rng = np.random.default_rng(13)
     root = tmp_path / "vctk"
@@ -659,7 +664,8 @@ def test_evaluate_sharded_eight_processes_share_the_host_cores(tmp_path):
         return json.loads([l for l in out.splitlines() if l.startswith("RESULT")][-1][6:])
     single = result(launch(0, 1, 0))
     port = 36500 + os.getpid() % 1000
-    ranks = [result(p) for p in [launch(r, 8, port) for r in range(8)]]
+    world = RANKS_SHARING_THE_GPU
+    ranks = [result(p) for p in [launch(r, world, port) for r in range(world)]]
     assert all(r["res"] == ranks[0]["res"] for r in ranks)
 
     def flat(d, pre=""):
@@ -671,18 +677,19 @@ def test_evaluate_sharded_eight_processes_share_the_host_cores(tmp_path):
     a, b = dict(flat(single["res"])), dict(flat(ranks[0]["res"]))
     assert list(a) == list(b) and max(abs(a[k] - b[k]) / max(abs(a[k]), 1e-300) for k in a) <= 1e-12
     assert all(1 <= r["readers"] <= r["limit"] for r in ranks)
-    assert sum(r["readers"] for r in ranks) <= max(8, ranks[0]["cores"])
+    assert sum(r["readers"] for r in ranks) <= max(world, ranks[0]["cores"])
     assert single["limit"] == min(16, single["cores"])
 
 
 def test_cabi_allreduce_sums_two_rank_communicator():
-    """ssr_allreduce_sums over a TWO-rank RCCL communicator (one process per device) where the box has two devices."""
-    if torch.cuda.device_count() < 2:
-        pytest.skip("one HIP device on this box: the two-rank RCCL communicator needs two (covered by the gloo tests on CPU)")
+    """The C ABI's communicator (ssr_comm_unique_id -> ssr_comm_init_rank -> ssr_allreduce_sums -> ssr_comm_destroy), one process per
+    device: TWO ranks where the box has two devices, the one-rank communicator on a one-device box (RCCL refuses two ranks on one
+    device: "Duplicate GPU detected") - the all-reduce kernel runs on the device either way."""
+    world = min(2, torch.cuda.device_count())
     code = r"""
 import os, sys, ctypes as C
 sys.path.insert(0, %r)
-rank = int(sys.argv[1]); path = sys.argv[2]
+rank = int(sys.argv[1]); path = sys.argv[2]; world = int(sys.argv[3])
 import torch
 torch.cuda.set_device(rank)
 from ssr_eval_amd import _lib
@@ -690,40 +697,61 @@ lib = _lib.load()
 uid = C.create_string_buffer(128)
 if rank == 0:
     _lib.check(lib.ssr_comm_unique_id(uid)); open(path + ".tmp", "wb").write(uid.raw); os.rename(path + ".tmp", path)
+    bad = C.c_void_p(1)
+    assert lib.ssr_comm_init_rank(uid, world, world, C.byref(bad)) != 0 and not bad.value     # rank outside [0, n_ranks)
 else:
     import time
     while not os.path.exists(path): time.sleep(0.05)
     uid = C.create_string_buffer(open(path, "rb").read(), 128)
 comm = C.c_void_p()
-_lib.check(lib.ssr_comm_init_rank(uid, 2, rank, C.byref(comm)))
-t = torch.arange(10, dtype=torch.float64, device="cuda") * (rank + 1)
+_lib.check(lib.ssr_comm_init_rank(uid, world, rank, C.byref(comm)))
+t = torch.arange(10, dtype=torch.float64, device="cuda") * (rank + 1) + 0.25
 _lib.check(lib.ssr_allreduce_sums(C.c_void_p(t.data_ptr()), 10, comm, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
 torch.cuda.synchronize()
-assert t.cpu().tolist() == [3.0 * i for i in range(10)], t
+assert t.cpu().tolist() == [world * (world + 1) / 2 * i + 0.25 * world for i in range(10)], t
 _lib.check(lib.ssr_comm_destroy(comm))
 print("OK")
 """ % ROOT
     import tempfile
     path = os.path.join(tempfile.mkdtemp(), "uid")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, "-c", code, str(r), path], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
-             for r in range(2)]
+    procs = [subprocess.Popen([sys.executable, "-c", code, str(r), path, str(world)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                              env=env) for r in range(world)]
     for p in procs:
         out, err = p.communicate(timeout=600)
         assert p.returncode == 0 and "OK" in out, err[-3000:]
 
 
-def test_bench_cli_configs_smoke():
-    """bench.py --config cfg3 / cfg5 at a small batch: one JSON line with the contract's fields."""
+def test_bench_cli_configs_smoke(tmp_path):
+    """bench.py --config cfg3 / cfg5 at a small batch: one JSON line with the contract's fields; --dump-outputs writes the last
+    step's arrays (float32 / float64, 64 MB at most), whose sums are the step's sums."""
     for cfg, extra in (("cfg3", ["--pairs", "32"]), ("cfg5", ["--utterances", "64"]), ("cfg4", [])):
+        out = tmp_path / cfg
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "2", "--warmup", "1",
-                            "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=900)
+                            "--no-cpu-baseline", "--dump-outputs", str(out)] + extra, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1
         d = json.loads(lines[0])
         assert d["n_gpus"] == 1 and d["value"] > 0 and d["roofline"]["frac"] > 0 and d["config"]["workload"].startswith(cfg[:3] + "-" + cfg[3])
         assert d["scaling"] == ("strong" if cfg == "cfg4" else "weak")
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+        got = {p.name[:-4]: np.load(p) for p in out.iterdir()}
+        assert sorted(got) == sorted(d["extra"]["dumped_outputs"]) and all(v.dtype in (np.float32, np.float64) for v in got.values())
+        sums = got["step_sums"]
+        if cfg == "cfg3":
+            lp = d["extra"]["dumped_outputs"]["lowpassed"]            # 172 MB in all: a seeded sample of its rows
+            assert lp["shape"] == [32 * len(CUTOFFS), 192000] and got["lowpassed"].shape == (lp["rows_sampled"], 192000) and lp["rows_sampled"] > 0
+            assert got["lsd"].shape == (32, len(CUTOFFS)) and np.isfinite(got["lowpassed"]).all()
+            for i, k in enumerate(KEYS):
+                assert abs(got[k].sum() - sums[i]) <= 1e-9 * np.abs(got[k]).sum(), (cfg, k)
+        elif cfg == "cfg5":
+            assert got["lsd"].shape == (64,) and got["resampled"].shape == (64, 192000) and np.isfinite(got["resampled"]).all()
+            assert abs(got["lsd"].sum() - sums[0]) <= 1e-9 * got["lsd"].sum()
+        else:
+            assert got["lsd"].shape == (2937,) and sorted(got["utterance_index"].tolist()) == list(range(2937))
+            for i, k in enumerate(KEYS):
+                assert abs(got[k].sum() - sums[:, i].sum()) <= 1e-9 * np.abs(got[k]).sum(), (cfg, k)
 
 
 def test_bench_under_two_ranks_as_the_driver_launches_it():

@@ -171,7 +171,13 @@ def test_lowpass_matches_reference_vectors(golden):
     np.testing.assert_array_equal(olp.align_length(np.arange(7.0), np.arange(4.0)), golden["al_pad"])
     np.testing.assert_array_equal(olp.align_length(np.arange(4.0), np.arange(7.0)), golden["al_cut"])
     mag, cos, sin = olp.spectrogram_phase(golden["fd_x"][None])
-    np.testing.assert_allclose(mag[0, 0], golden["fd_mag"], rtol=2e-7, atol=2e-7 * golden["fd_mag"].max())
+    # the reference's float32 dense-DFT convolution sits within its round-off floor of the float64 transform (host-independent);
+    # torch's conv1d sums in an order that depends on the CPU it dispatches for (the same box: 1e-8 of the peak; another vendor's
+    # CPU: 1.1e-6), so the oracle's member may stand up to three times that floor away from the reference's
+    ideal = olp.spectrogram_phase(golden["fd_x"][None], arithmetic="ideal")[0][0, 0]
+    floor = np.abs(golden["fd_mag"] - ideal).max()
+    assert floor <= 5e-7 * golden["fd_mag"].max()
+    np.testing.assert_allclose(mag[0, 0], golden["fd_mag"], rtol=2e-7, atol=2e-7 * golden["fd_mag"].max() + 3 * floor)
     big = golden["fd_mag"] > 1e-2 * golden["fd_mag"].max()          # (cos of a bin at the float32 noise floor is that noise's phase)
     np.testing.assert_allclose(cos[0, 0][big], golden["fd_cos"][big], atol=1e-4)
 
@@ -281,9 +287,12 @@ def test_round5_reference_vectors_and_torchs_square_root():
     v = (rng.random(200000).astype(np.float32) * 12)
     exact = np.sqrt(v.astype(np.float64)).astype(np.float32)
     np.testing.assert_array_equal(np.sqrt(v), exact)
-    off = (torch.from_numpy(v) ** 0.5).numpy() != exact
+    got = (torch.from_numpy(v) ** 0.5).numpy()
+    off = got != exact
+    # never more than one ulp away; how many are off depends on the code path MKL picks for the CPU (0.7 % on one, 17 % on another)
+    assert np.abs(got.view(np.int32).astype(np.int64) - exact.view(np.int32)).max() <= 1
     if torch.__config__.show().find("BLAS_INFO=mkl") >= 0:
-        assert 0.001 < off.mean() < 0.02
+        assert off.mean() > 0.001
     for name, seed, n, cuts in json.loads(str(g["lp5_cases"])):
         if name != "noise":
             continue
