@@ -224,6 +224,40 @@ int ssr_spectrogram_metrics(const float* est_sp, const float* tgt_sp, const int6
                             int n_items, int max_rows, int n_bins, unsigned metric_mask, double* out, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* Band-split LSD: AudioMetrics.lsd (ssr_eval/metrics.py:109-112) applied to the columns [a, b) of each band - e.g. LSD-LF / LSD-HF
+ * on either side of a degradation's cutoff bin,
+ *   lsd_band(E, T, a, b) = mean_t sqrt( mean_{a <= k < b} log10( T^2 / (E + 1e-12)^2 + 1e-12 )^2 ).
+ * The per-bin term is the float32 sequence of the fused LSD epilogue; per-band row sums and frame totals are float64.
+ * edges: HOST int32 [n_images][n_bands + 1] (the one other exception to the device-pointer convention, like ssr_tl_weights):
+ * strictly ascending, 0 <= edges[0], edges[n_bands] <= n_bins; band j of image v is [edges[v][j], edges[v][j + 1]).  They are
+ * validated before anything is enqueued and copied into the workspace on `stream` - from page-locked memory that copy is
+ * asynchronous, and the caller keeps the values unchanged until the stream has reached it.  1 <= n_bands <= SSR_MAX_BANDS. */
+#define SSR_MAX_BANDS 8
+/* Image level, backs AudioMetrics.lsd_bands on [B, C, T, F] tensors: image v is the est rows [est_frame_off[v], + n_rows[v]) of
+ * est_sp and the target rows [tgt_frame_off[v], + n_rows[v]) of tgt_sp, both [*, n_bins] float32 matrices (several images may
+ * share one target).  max_rows >= every n_rows[v].  out: double [n_images][n_bands].
+ * workspace: ssr_spectrogram_lsd_bands_workspace_bytes(n_images, max_rows, n_bands). */
+size_t ssr_spectrogram_lsd_bands_workspace_bytes(int n_images, int max_rows, int n_bands);
+int ssr_spectrogram_lsd_bands(const float* est_sp, const int64_t* est_frame_off, const float* tgt_sp, const int64_t* tgt_frame_off,
+                              const int32_t* n_rows, int n_images, int max_rows, int n_bins, const int32_t* edges, int n_bands,
+                              double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* Waveform level: K float32 estimates per float32 target with the key-major [n_keys][n_items] estimate offsets and the length /
+ * frame descriptors of ssr_pair_metrics_multi; edges [n_keys][n_items][n_bands + 1] (image v = k * n_items + i).  The target is
+ * transformed once per item (with estimate 0, as ssr_pair_metrics does) into a magnitude image; the other estimates go into
+ * magnitude images two per complex transform where the plan's pair transform is a wave kernel (else one per transform with the
+ * target, whose image is not rewritten) - the magnitudes of ssr_pair_metrics_multi - and the band reduction runs on the images.
+ * Bands [0, n_bins) give ssr_pair_metrics' LSD to <= 1e-6 relative.  out: double [n_items][n_keys][n_bands].
+ * The workspace holds K + 1 magnitude images of the batch (8 (K + 1) * total_rows * n_bins bytes, rows padded to 16 bytes): callers
+ * with many keys run them in chunks.  ssr_pair_lsd_bands_workspace_bytes serves both entry points. */
+size_t ssr_pair_lsd_bands_workspace_bytes(const ssr_plan* plan, int n_items, int n_keys, int max_len, int64_t total_rows, int n_bands);
+int ssr_pair_lsd_bands(const ssr_plan* plan, const float* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
+                       const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
+                       const int32_t* edges, int n_bands, double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for FLOAT64 estimates (IIR keys, as ssr_pair_metrics_multi_est64): transformed at float64, |.| rounded once to float32. */
+int ssr_pair_lsd_bands_est64(const ssr_plan* plan, const double* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
+                             const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
+                             const int32_t* edges, int n_bands, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* A6.  The tensor helpers of ssr_eval/utils.py as stand-alone calls (inside ssr_pair_metrics /
  * ssr_spectrogram_metrics they are fused; these back `from ssr_eval.utils import to_log, pow_p_norm, ...`).
  *   ssr_to_log      out = log10(x + 1e-12)                       utils.py:43-44

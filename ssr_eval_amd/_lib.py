@@ -16,6 +16,7 @@ STFT_MAG, STFT_COMPLEX = 1, 2
 LOWPASS_SEGMENTS, LOWPASS_FUSED, LOWPASS_CONV = 0, 1, 2
 PAD_REFLECT, PAD_CONSTANT = 0, 1
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE = -1, -2, -3, -4      # include/ssr_hip.h
+MAX_BANDS = 8                                                                   # SSR_MAX_BANDS
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -46,6 +47,11 @@ SIGNATURES = {
     "ssr_pair_metrics_stages": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _u, _vp, _vp, _sz, _vp, _i]),
     "ssr_spectrogram_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "ssr_spectrogram_metrics": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _u, _vp, _vp, _sz, _vp]),
+    "ssr_spectrogram_lsd_bands_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ssr_spectrogram_lsd_bands": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "ssr_pair_lsd_bands_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i64, _i]),
+    "ssr_pair_lsd_bands": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
+    "ssr_pair_lsd_bands_est64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
     "ssr_to_log": (_i, [_vp, _i64, _vp, _vp]),
     "ssr_from_log": (_i, [_vp, _i64, _vp, _vp]),
     "ssr_energy_sums": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),

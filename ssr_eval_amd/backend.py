@@ -232,7 +232,9 @@ class _DescRing:
                 r = cls._by_dev[idx] = cls()
             return r
 
-    def put(self, a, dev):
+    def stage(self, a, dev):
+        """A page-locked copy of `a` that stays untouched until the current stream has passed what is queued next (a library
+        call that reads host memory asynchronously: ssr_*_lsd_bands' edges)."""
         nbytes = a.nbytes
         room = (nbytes + 63) & ~63
         with self.lock:
@@ -253,10 +255,13 @@ class _DescRing:
             st = torch.cuda.current_stream(dev)
             self.streams[st.cuda_stream] = st
             self.host[pos:pos + nbytes] = a.reshape(-1).view(np.uint8)
-            src = self.buf[pos:pos + nbytes].view(_TORCH_OF[a.dtype.type]).view(a.shape)
-            out = torch.empty(a.shape, dtype=src.dtype, device=dev)
-            out.copy_(src, non_blocking=True)
-            return out
+            return self.buf[pos:pos + nbytes].view(_TORCH_OF[a.dtype.type]).view(a.shape)
+
+    def put(self, a, dev):
+        src = self.stage(a, dev)
+        out = torch.empty(a.shape, dtype=src.dtype, device=dev)
+        out.copy_(src, non_blocking=True)
+        return out
 
 
 _TORCH_OF = {np.int32: torch.int32, np.int64: torch.int64, np.float32: torch.float32, np.float64: torch.float64,
@@ -558,6 +563,95 @@ def pair_metrics(plan, est_list, tgt_list, mask=M_ALL, deferred=False):
         b = PairBatch(plan, Ragged.from_list_keep64(est_list, plan.device, allow_gaps=True),
                       Ragged.from_list_keep64(tgt_list, plan.device, allow_gaps=True))
         return Pending(b.run(mask)) if deferred else b.run(mask).cpu().numpy()
+
+
+# ---- band-split LSD ---------------------------------------------------------------------------------------------------------
+# Bytes of magnitude images one ssr_pair_lsd_bands call may hold: K + 1 images per item (8 bytes per bin of the batch per key) are
+# more than HBM holds for 36 keys of a large batch, so the keys run in chunks whose images fit in this.
+LSD_BANDS_WS_BYTES = 1 << 30
+
+
+def _edges_host(edges, n_images, n_bands, dev):
+    """int32 [n_images][n_bands + 1] as the library reads it (host memory, page-locked when it fits the ring: asynchronous copy)."""
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.int32).reshape(n_images, n_bands + 1))
+    if dev.type == "cuda" and e.nbytes <= _DescRing.SIZE // 8:
+        with torch.cuda.device(dev):
+            st = _DescRing.get(torch.cuda.current_device()).stage(e, dev)
+        return st, C.c_void_p(st.data_ptr())
+    return e, e.ctypes.data_as(C.c_void_p)
+
+
+def spectrogram_lsd_bands(est, target, edges):
+    """est / target: [N, T, F] magnitude images (float32, on one device), edges: int [N][n_bands + 1] -> [N, n_bands] float64 device
+    tensor (ssr_spectrogram_lsd_bands)."""
+    require_gpu()
+    lib = _lib.load()
+    dev = est.device if isinstance(est, torch.Tensor) and est.is_cuda else default_device()
+    with torch.cuda.device(dev):
+        x = _dev_f32(est, dev).contiguous()
+        y = _dev_f32(target, dev).contiguous()
+        if x.dim() != 3 or x.shape != y.shape:
+            raise ValueError("spectrogram shape mismatch: %s vs %s" % (tuple(x.shape), tuple(y.shape)))
+        N, T, F = (int(v) for v in x.shape)
+        e = np.asarray(edges, dtype=np.int32)
+        if e.ndim != 2 or e.shape[0] != N:
+            raise ValueError("edges must be [n_images][n_bands + 1]")
+        nb = e.shape[1] - 1
+        if nb < 1:
+            raise ValueError("at least one band (two edges) per image")
+        off = torch.arange(N, device=dev, dtype=torch.int64) * T
+        rows = torch.full((N,), T, device=dev, dtype=torch.int32)
+        out = torch.empty((N, nb), dtype=torch.float64, device=dev)
+        ws_bytes = int(lib.ssr_spectrogram_lsd_bands_workspace_bytes(N, T, nb))
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        keep, ep = _edges_host(e, N, nb, dev)
+        _lib.check(lib.ssr_spectrogram_lsd_bands(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, ep, nb, _vp(out), _vp(ws),
+                                                 ws_bytes, _stream()))
+        return out
+
+
+def pair_lsd_bands(plan, est_lists, tgt_list, edges, deferred=False, keys_per_chunk=None):
+    """Band LSDs of K estimates per target: est_lists = K lists of n waveforms (all float32 or all float64, each as long as its
+    target), tgt_list = n float32 targets, edges: int [K][n][n_bands + 1] -> [n, K, n_bands] float64 (deferred: a Pending).
+    The keys run in chunks (ssr_pair_lsd_bands holds K + 1 magnitude images per item): keys_per_chunk, or as many as fit in
+    LSD_BANDS_WS_BYTES (a multiple of six where more than six fit: whole groups of the reduction's three keys per wave)."""
+    K, n = len(est_lists), len(tgt_list)
+    e = np.asarray(edges, dtype=np.int32)
+    if e.ndim != 3 or e.shape[:2] != (K, n):
+        raise ValueError("edges must be [n_keys][n_items][n_bands + 1]")
+    nb = e.shape[2] - 1
+    if nb < 1:
+        raise ValueError("at least one band (two edges) per image")
+    with torch.cuda.device(plan.device):
+        tgt = Ragged.from_list(tgt_list, plan.device, allow_gaps=True)
+        if any(_is_f64(t) for t in tgt_list):
+            raise ValueError("band LSD takes float32 targets (float64 estimates are kept float64)")
+        _check_nonempty(tgt.lens_host)
+        rows = _Rows(plan, tgt.lens_host, tgt.device)
+        out = torch.empty((n, K, nb), dtype=torch.float64, device=tgt.device)
+        if n and K:
+            if keys_per_chunk is None:
+                plane = rows.total * ((plan.n_bins + 3) & ~3) * 4
+                keys_per_chunk = max(1, LSD_BANDS_WS_BYTES // max(plane, 1) - 1)
+                if keys_per_chunk > 6:
+                    keys_per_chunk -= keys_per_chunk % 6
+            kc = max(1, min(int(keys_per_chunk), K))
+            lib = plan.lib
+            ws_bytes = int(lib.ssr_pair_lsd_bands_workspace_bytes(plan.handle, n, kc, tgt.max_len, rows.total, nb))
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=tgt.device)
+            for k0 in range(0, K, kc):
+                k1 = min(K, k0 + kc)
+                est = Ragged.from_list_keep64([w for key in est_lists[k0:k1] for w in key], plan.device, allow_gaps=True)
+                if not np.array_equal(est.lens_host, np.tile(tgt.lens_host, k1 - k0)):
+                    raise ValueError("every estimate must be as long as its target (truncate to min_len first)")
+                o = out if k1 - k0 == K else torch.empty((n, k1 - k0, nb), dtype=torch.float64, device=tgt.device)
+                keep, ep = _edges_host(e[k0:k1], (k1 - k0) * n, nb, tgt.device)
+                fn = lib.ssr_pair_lsd_bands_est64 if est.data.dtype == torch.float64 else lib.ssr_pair_lsd_bands
+                _lib.check(fn(plan.handle, _vp(est.data), _vp(est.off), _vp(tgt.data), _vp(tgt.off), _vp(tgt.len), _vp(rows.off), n,
+                              k1 - k0, tgt.max_len, rows.total, ep, nb, _vp(o), _vp(ws), ws_bytes, _stream()))
+                if o is not out:
+                    out[:, k0:k1] = o
+        return Pending(out) if deferred else out.cpu().numpy()
 
 
 def stft(plan, wavs, kind="mag", torch_style_pad=False):

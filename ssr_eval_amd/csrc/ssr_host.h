@@ -90,6 +90,16 @@ int ssr_pair_units_per_chunk(const ssr_plan* pl, int max_units, int n_items, boo
 // the frames whose samples overlap are transformed at the same time on one XCD (ssr_stft_wave.h); n_chunks is a multiple of it.
 int ssr_pair_interleave(const ssr_plan* pl, bool in64);
 
+// row pitch of the pair pipeline's magnitude images: rows padded to 16 bytes (k_ssim's aligned loads, ssr_metrics.h CONTIG)
+inline int ssr_mag_pitch(int n_bins) { return (n_bins + 3) & ~3; }
+// Estimates of a multi-key call go two per complex transform (images only) where the plan has a wave kernel for that
+// (ssr_pair_metrics_multi, ssr_pair_lsd_bands).  est64: float64 estimates - n_fft = 3 q on the rotating four-wave engine
+// (AudioMetrics(48000), ssr_stft_r3_rot.h SSR_IN_EST64X2).
+inline bool ssr_multi_fast_path(const ssr_plan* pl, bool est64) {
+  if (est64) return pl->precision == SSR_F64 && ssr_stft_rn_wave_radix(pl) == 3 && pl->weng.m == 1536;
+  return ssr_stft_uses_wave_engine(pl, false) || ssr_stft_rn_wave_radix(pl) != 0;
+}
+
 // ---- launchers defined by the kernel translation units --------------------------------------------------------
 template <typename T> struct SsrStftParams;
 template <typename T> struct SsrLowpassParams;

@@ -1,0 +1,218 @@
+// libssrhip.so translation unit: band-split LSD (ssr_lsd_bands.h) and its entry points (ssr_spectrogram_lsd_bands,
+// ssr_pair_lsd_bands, ssr_pair_lsd_bands_est64).
+#include "ssr_host.h"
+#include "ssr_lsd_bands.h"
+
+template <int KG, int NB, bool VEC> __global__ __launch_bounds__(64) void k_lsd_bands(SsrLsdBandsParams p) {
+  ssr_lsd_bands_body<KG, NB, VEC>(p, blockIdx.x % p.n_chunks, blockIdx.x / p.n_chunks);
+}
+
+__global__ __launch_bounds__(256) void k_lsd_bands_finalize(SsrLsdBandsFinalizeParams p, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) ssr_lsd_bands_finalize(p, i);
+}
+
+__global__ void k_lsd_rows_from_len(const int32_t* len, int n_items, int n_fft, int hop, int32_t* rows) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_items) rows[i] = ssr_num_frames_dev(len[i], n_fft, hop);
+}
+
+// host-side validation of the caller's edges: nothing reaches the device unless every band lies inside [0, n_bins)
+static int check_edges(const int32_t* edges, int64_t n_images, int n_bands, int n_bins) {
+  if (n_bands < 1 || n_bands > SSR_MAX_BANDS) return ssr_fail(SSR_ERR_INVALID_ARG, "n_bands must be in 1..SSR_MAX_BANDS");
+  if (!edges) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  for (int64_t v = 0; v < n_images; ++v) {
+    const int32_t* e = edges + v * (n_bands + 1);
+    if (e[0] < 0) return ssr_fail(SSR_ERR_INVALID_ARG, "band edges must be >= 0");
+    for (int j = 0; j < n_bands; ++j)
+      if (e[j + 1] <= e[j]) return ssr_fail(SSR_ERR_INVALID_ARG, "band edges must be strictly ascending");
+    if (e[n_bands] > n_bins) return ssr_fail(SSR_ERR_INVALID_ARG, "last band edge exceeds n_bins");
+  }
+  return SSR_OK;
+}
+
+// rows per one-wave workgroup: ~16 k workgroups per launch, at least 8 rows each (the k_specred_wave rule)
+static void band_chunks(int max_rows, int64_t groups, int* rows_per_chunk, int* n_chunks) {
+  int64_t spc = ((int64_t)16384 + groups - 1) / groups;
+  if (spc > max_rows / 8) spc = max_rows / 8;
+  if (spc < 1) spc = 1;
+  *rows_per_chunk = ssr_ceil_div(max_rows, spc);
+  *n_chunks = ssr_ceil_div(max_rows, *rows_per_chunk);
+}
+
+// estimate keys per wave sharing the target's rows: three where they divide by three, else two, else one (k_specred_wave measured 3
+// and 2 best on the four-metric reduction)
+static int band_kg(int n_keys) { return n_keys % 3 == 0 ? 3 : (n_keys % 2 == 0 ? 2 : 1); }
+
+template <int KG, int NB>
+static void launch_bands_kg(const SsrLsdBandsParams& p, bool vec, dim3 grid, hipStream_t s) {
+  if (vec) hipLaunchKernelGGL((k_lsd_bands<KG, NB, true>), grid, dim3(64), 0, s, p);
+  else hipLaunchKernelGGL((k_lsd_bands<KG, NB, false>), grid, dim3(64), 0, s, p);
+}
+
+// the reduction + the finalisation; `edges_dev` already on the device, n_keys * n_items images
+static int launch_bands(SsrLsdBandsParams p, int n_keys, int kg, int max_rows, const int32_t* n_rows, double* out, hipStream_t s) {
+  band_chunks(max_rows, (int64_t)p.n_items * (n_keys / kg), &p.rows_per_chunk, &p.n_chunks);
+  const bool vec = p.pitch % 4 == 0 && (((uintptr_t)p.x | (uintptr_t)p.y) & 15) == 0 && (p.x_plane % 4) == 0;
+  const dim3 grid((unsigned)((int64_t)(n_keys / kg) * p.n_items * p.n_chunks));
+  const bool two = p.n_bands <= 2;        // the LF / HF split: 2 accumulators per key instead of SSR_MAX_BANDS
+  switch (kg * 2 + (two ? 1 : 0)) {
+    case 7: launch_bands_kg<3, 2>(p, vec, grid, s); break;
+    case 6: launch_bands_kg<3, SSR_MAX_BANDS>(p, vec, grid, s); break;
+    case 5: launch_bands_kg<2, 2>(p, vec, grid, s); break;
+    case 4: launch_bands_kg<2, SSR_MAX_BANDS>(p, vec, grid, s); break;
+    case 3: launch_bands_kg<1, 2>(p, vec, grid, s); break;
+    default: launch_bands_kg<1, SSR_MAX_BANDS>(p, vec, grid, s); break;
+  }
+  HIP_TRY(hipGetLastError());
+  SsrLsdBandsFinalizeParams f{p.part, n_rows, p.n_chunks, p.n_bands, p.n_items, n_keys, out};
+  const int64_t n = (int64_t)n_keys * p.n_items * p.n_bands;
+  hipLaunchKernelGGL(k_lsd_bands_finalize, dim3((unsigned)ssr_ceil_div(n, 256)), dim3(256), 0, s, f, n);
+  HIP_TRY(hipGetLastError());
+  return SSR_OK;
+}
+
+static size_t part_bytes(int64_t n_images, int max_rows, int n_bands, int64_t groups) {
+  int rpc, nc;
+  band_chunks(max_rows, groups, &rpc, &nc);
+  return ssr_align256((size_t)n_images * nc * n_bands * sizeof(double));
+}
+static size_t edges_bytes(int64_t n_images, int n_bands) { return ssr_align256((size_t)n_images * (n_bands + 1) * sizeof(int32_t)); }
+
+// ----------------------------------------------------------------------------------------------------
+// image level: one image per (est, target) view, one key (KG = 1), the caller's [*, n_bins] pitch
+extern "C" size_t ssr_spectrogram_lsd_bands_workspace_bytes(int n_images, int max_rows, int n_bands) {
+  if (n_images <= 0 || max_rows < 1 || n_bands < 1 || n_bands > SSR_MAX_BANDS) return 0;
+  return part_bytes(n_images, max_rows, n_bands, n_images) + edges_bytes(n_images, n_bands);
+}
+
+extern "C" int ssr_spectrogram_lsd_bands(const float* est_sp, const int64_t* est_frame_off, const float* tgt_sp, const int64_t* tgt_frame_off,
+                                         const int32_t* n_rows, int n_images, int max_rows, int n_bins, const int32_t* edges, int n_bands,
+                                         double* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!est_sp || !est_frame_off || !tgt_sp || !tgt_frame_off || !n_rows || !edges || !out) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  if (n_images <= 0) return SSR_OK;
+  if (max_rows < 1 || n_bins < 1) return ssr_fail(SSR_ERR_INVALID_ARG, "empty spectrogram");
+  if ((int64_t)max_rows * n_bins >= ((int64_t)1 << 30))
+    return ssr_fail(SSR_ERR_UNSUPPORTED, "spectrogram of 2^30 elements or more (4 GiB buffer views)");
+  if (int rc = check_edges(edges, n_images, n_bands, n_bins)) return rc;
+  const size_t pb = part_bytes(n_images, max_rows, n_bands, n_images);
+  if (!workspace || workspace_bytes < pb + edges_bytes(n_images, n_bands)) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* e_dev = (int32_t*)(ws + pb);
+  HIP_TRY(hipMemcpyAsync(e_dev, edges, (size_t)n_images * (n_bands + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  SsrLsdBandsParams p{est_sp, tgt_sp, est_frame_off, tgt_frame_off, n_rows, e_dev, 0, n_bins, n_bins, n_bands, n_images, 0, 0,
+                      (double*)ws};
+  return launch_bands(p, 1, 1, max_rows, n_rows, out, s);
+}
+
+// ----------------------------------------------------------------------------------------------------
+// waveform level: K + 1 magnitude images per item (the pair transform of ssr_pair_metrics_multi), then the reduction
+struct BandWs { size_t plane, off_est, off_tgt, off_scratch, off_part, off_edges, off_rows, total; int units_per_chunk, n_chunks, kg; };
+static BandWs band_ws(const ssr_plan* pl, int n_items, int n_keys, int max_len, int64_t total_rows, int n_bands, bool in64) {
+  BandWs w;
+  const int max_T = (int)ssr_num_frames(pl, max_len);
+  w.units_per_chunk = ssr_pair_units_per_chunk(pl, max_T, n_items, in64);
+  w.n_chunks = ssr_ceil_div(max_T, w.units_per_chunk);
+  const int S = ssr_pair_interleave(pl, in64);
+  w.n_chunks = ssr_ceil_div(w.n_chunks, S) * S;
+  w.kg = band_kg(n_keys);
+  w.plane = ssr_align256((size_t)total_rows * ssr_mag_pitch(pl->n_bins) * sizeof(float));
+  size_t o = 0;
+  w.off_est = o; o += (size_t)n_keys * w.plane;
+  w.off_tgt = o; o += w.plane;
+  // the block engines store both images of a pair (they take no null out_b): keys 1 .. K-1 paired with the target put the target's
+  // rows here, so that the image key 0 wrote stays the one every key is reduced against
+  w.off_scratch = o; o += (n_keys > 1 && !ssr_multi_fast_path(pl, in64)) ? w.plane : 0;
+  w.off_part = o; o += part_bytes((int64_t)n_keys * n_items, max_T, n_bands, (int64_t)n_items * (n_keys / w.kg));
+  w.off_edges = o; o += edges_bytes((int64_t)n_keys * n_items, n_bands);
+  w.off_rows = o; o += ssr_align256((size_t)n_items * sizeof(int32_t));
+  w.total = o;
+  return w;
+}
+
+extern "C" size_t ssr_pair_lsd_bands_workspace_bytes(const ssr_plan* pl, int n_items, int n_keys, int max_len, int64_t total_rows, int n_bands) {
+  if (!pl || n_items <= 0 || n_keys <= 0 || max_len < 1 || n_bands < 1 || n_bands > SSR_MAX_BANDS) return 0;
+  const size_t a = band_ws(pl, n_items, n_keys, max_len, total_rows, n_bands, false).total;
+  const size_t b = band_ws(pl, n_items, n_keys, max_len, total_rows, n_bands, true).total;
+  return a > b ? a : b;
+}
+
+template <typename T>
+static int band_stft(const ssr_plan* pl, const float* a, const double* a64, const int64_t* a_off, const float* b, const double* b64,
+                     const int64_t* b_off, const int32_t* len, const int64_t* frame_off, int n_items, float* out_a, float* out_b,
+                     const BandWs& w, hipStream_t s) {
+  SsrStftParams<T> p{};
+  p.a = a; p.a64 = a64; p.b = b; p.b64 = b64; p.a_off = a_off; p.b_off = b_off; p.len = len; p.frame_off = frame_off;
+  p.mode = SSR_MODE_PAIR; p.out_kind = SSR_OUT_MAG; p.metric_mask = 0;     // images only, no metric epilogue
+  p.n_fft = pl->n_fft; p.hop = pl->hop; p.n_bins = pl->n_bins;
+  p.units_per_chunk = w.units_per_chunk; p.n_chunks = w.n_chunks; p.interleave = ssr_pair_interleave(pl, a64 != nullptr);
+  p.out_a = out_a; p.out_b = out_b; p.out_pitch = ssr_mag_pitch(pl->n_bins); p.part = nullptr;
+  return ssr_launch_stft<T>(pl, p, n_items * w.n_chunks, s);
+}
+
+static int pair_lsd_bands_impl(const ssr_plan* pl, const float* est, const double* est64, const int64_t* est_off, const float* tgt,
+                               const int64_t* tgt_off, const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len,
+                               int64_t total_rows, const int32_t* edges, int n_bands, double* out, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  if (!pl || (!est && !est64) || !est_off || !tgt || !tgt_off || !len || !frame_off || !edges || !out)
+    return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  if (n_bands < 1 || n_bands > SSR_MAX_BANDS) return ssr_fail(SSR_ERR_INVALID_ARG, "n_bands must be in 1..SSR_MAX_BANDS");
+  if (n_items <= 0 || n_keys <= 0) return SSR_OK;
+  if (max_len < 1) return ssr_fail(SSR_ERR_INVALID_ARG, "empty signals");
+  if (max_len >= (1 << 29)) return ssr_fail(SSR_ERR_UNSUPPORTED, "signals of 2^29 samples or more (4 GiB buffer views)");
+  if ((int64_t)n_items * n_keys > 0x3fffffff) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
+  if (int rc = check_edges(edges, (int64_t)n_items * n_keys, n_bands, pl->n_bins)) return rc;
+  const int max_T = (int)ssr_num_frames(pl, max_len);
+  if ((int64_t)max_T * pl->n_bins >= ((int64_t)1 << 30)) return ssr_fail(SSR_ERR_UNSUPPORTED, "spectrogram of 2^30 elements or more (4 GiB buffer views)");
+  const bool e64 = est64 != nullptr;
+  const BandWs w = band_ws(pl, n_items, n_keys, max_len, total_rows, n_bands, e64);
+  if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
+  if (int rc_dev = ssr_check_plan_device(pl)) return rc_dev;
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* rows = (int32_t*)(ws + w.off_rows);
+  int32_t* e_dev = (int32_t*)(ws + w.off_edges);
+  HIP_TRY(hipMemcpyAsync(e_dev, edges, (size_t)n_items * n_keys * (n_bands + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_lsd_rows_from_len, dim3(ssr_ceil_div(n_items, 256)), dim3(256), 0, s, len, n_items, pl->n_fft, pl->hop, rows);
+  HIP_TRY(hipGetLastError());
+  auto plane_of = [&](int k) { return (float*)(ws + w.off_est + (size_t)k * w.plane); };
+  float* tgt_plane = (float*)(ws + w.off_tgt);
+  auto stft = [&](const float* a, const double* a64, const int64_t* a_off, const float* b, const double* b64, const int64_t* b_off,
+                  float* oa, float* ob) {
+    return pl->precision == SSR_F64 ? band_stft<double>(pl, a, a64, a_off, b, b64, b_off, len, frame_off, n_items, oa, ob, w, s)
+                                    : band_stft<float>(pl, a, a64, a_off, b, b64, b_off, len, frame_off, n_items, oa, ob, w, s);
+  };
+  // key 0 with the target: both images (the target's written once, here)
+  int rc = stft(est, est64, est_off, tgt, nullptr, tgt_off, plane_of(0), tgt_plane);
+  if (rc) return rc;
+  int k = 1;
+  const bool fast = ssr_multi_fast_path(pl, e64);
+  if (fast)                                  // two estimates per complex transform (wave engines)
+    for (; k + 1 < n_keys; k += 2)
+      if ((rc = stft(est, est64, est_off + (size_t)k * n_items, est, est64, est_off + (size_t)(k + 1) * n_items, plane_of(k), plane_of(k + 1))))
+        return rc;
+  // the rest with the target, whose image is not rewritten: the wave engines skip a null out_b, the block engines get the scratch plane
+  float* tgt_sink = fast ? nullptr : (float*)(ws + w.off_scratch);
+  for (; k < n_keys; ++k)
+    if ((rc = stft(est, est64, est_off + (size_t)k * n_items, tgt, nullptr, tgt_off, plane_of(k), tgt_sink))) return rc;
+  SsrLsdBandsParams p{plane_of(0), tgt_plane, frame_off, frame_off, rows, e_dev, (int64_t)(w.plane / sizeof(float)), pl->n_bins,
+                      ssr_mag_pitch(pl->n_bins), n_bands, n_items, 0, 0, (double*)(ws + w.off_part)};
+  return launch_bands(p, n_keys, w.kg, max_T, rows, out, s);
+}
+
+extern "C" int ssr_pair_lsd_bands(const ssr_plan* pl, const float* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
+                                  const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
+                                  const int32_t* edges, int n_bands, double* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!est) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  return pair_lsd_bands_impl(pl, est, nullptr, est_off, tgt, tgt_off, len, frame_off, n_items, n_keys, max_len, total_rows, edges, n_bands,
+                             out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ssr_pair_lsd_bands_est64(const ssr_plan* pl, const double* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
+                                        const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
+                                        const int32_t* edges, int n_bands, double* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!est) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  return pair_lsd_bands_impl(pl, nullptr, est, est_off, tgt, tgt_off, len, frame_off, n_items, n_keys, max_len, total_rows, edges, n_bands,
+                             out, workspace, workspace_bytes, stream);
+}

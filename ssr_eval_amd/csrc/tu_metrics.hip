@@ -17,8 +17,6 @@ __global__ __launch_bounds__(SSR_SSIM_NT, CPT == 8 ? SSR_SSIM8_WPE : SSR_SSIM_WA
   ssr_ssim_body<CPT, CONTIG>(p, blk, blockIdx.x % tiles, blockIdx.x / tiles, smem);
 }
 
-// row pitch of the pair pipeline's magnitude images: rows padded to 16 bytes (k_ssim's aligned loads, ssr_metrics.h CONTIG)
-static int mag_pitch(int n_bins) { return (n_bins + 3) & ~3; }
 
 __global__ __launch_bounds__(256) void k_specred(SsrSpecRedParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -79,8 +77,8 @@ static PairWs pair_ws(const ssr_plan* pl, int n_items, int max_len, int64_t tota
   w.n_chunks = ssr_ceil_div(w.n_chunks, S) * S;
   w.sg = ssim_geom(max_T, pl->n_bins, n_items, true);
   size_t o = 0;
-  w.off_est = o; o += want_mag ? ssr_align256((size_t)total_rows * mag_pitch(pl->n_bins) * sizeof(float)) : 0;
-  w.off_tgt = o; o += want_mag ? ssr_align256((size_t)total_rows * mag_pitch(pl->n_bins) * sizeof(float)) : 0;
+  w.off_est = o; o += want_mag ? ssr_align256((size_t)total_rows * ssr_mag_pitch(pl->n_bins) * sizeof(float)) : 0;
+  w.off_tgt = o; o += want_mag ? ssr_align256((size_t)total_rows * ssr_mag_pitch(pl->n_bins) * sizeof(float)) : 0;
   w.off_part = o; o += ssr_align256((size_t)n_items * w.n_chunks * SSR_NPART * sizeof(double));
   w.off_ssim = o; o += ssr_align256((size_t)n_items * w.sg.n_row_tiles * w.sg.n_strips * sizeof(double));
   w.total = o;
@@ -168,7 +166,7 @@ static int pair_stage_stft(const ssr_plan* pl, const float* est, const double* e
   p.mode = SSR_MODE_PAIR; p.out_kind = need_mag ? SSR_OUT_MAG : SSR_OUT_NONE; p.metric_mask = (int)mask;
   p.n_fft = pl->n_fft; p.hop = pl->hop; p.n_bins = pl->n_bins;
   p.units_per_chunk = w.units_per_chunk; p.n_chunks = w.n_chunks; p.interleave = ssr_pair_interleave(pl, est64 != nullptr);
-  p.out_a = (float*)(ws + w.off_est); p.out_b = (float*)(ws + w.off_tgt); p.out_pitch = mag_pitch(pl->n_bins);
+  p.out_a = (float*)(ws + w.off_est); p.out_b = (float*)(ws + w.off_tgt); p.out_pitch = ssr_mag_pitch(pl->n_bins);
   p.part = (double*)(ws + w.off_part);
   return ssr_launch_stft<T>(pl, p, n_items * w.n_chunks, s);
 }
@@ -208,7 +206,7 @@ static int pair_metrics_impl(const ssr_plan* pl, const float* est, const double*
   }
   if ((stages & 2) && want_ssim) {
     rc = launch_ssim((const float*)(ws + w.off_est), (const float*)(ws + w.off_tgt), frame_off, rows, n_items,
-                     pl->n_bins, mag_pitch(pl->n_bins), w.sg, (double*)(ws + w.off_ssim), s);
+                     pl->n_bins, ssr_mag_pitch(pl->n_bins), w.sg, (double*)(ws + w.off_ssim), s);
     if (rc) return rc;
   }
   if (stages & 4) {
@@ -268,22 +266,16 @@ struct MultiWs {
   int spec_rows_per_chunk, spec_chunks, spec_kg, n_tiles;
   bool fast;
 };
-// est64 (ssr_pair_metrics_multi_est64): the estimates are float64 signals - two per complex transform where the plan has a wave kernel for
-// that (n_fft = 3 q on the rotating four-wave engine: AudioMetrics(48000), ssr_stft_r3_rot.h SSR_IN_EST64X2)
-static bool multi_fast_path(const ssr_plan* pl, bool est64) {
-  if (est64) return pl->precision == SSR_F64 && ssr_stft_rn_wave_radix(pl) == 3 && pl->weng.m == 1536;
-  return ssr_stft_uses_wave_engine(pl, false) || ssr_stft_rn_wave_radix(pl) != 0;
-}
 static MultiWs multi_ws(const ssr_plan* pl, int n_items, int n_keys, int max_len, int64_t total_rows, unsigned mask, bool est64 = false) {
   MultiWs m;
   const bool want_ssim = mask & SSR_METRIC_SSIM;
-  m.fast = multi_fast_path(pl, est64) && n_keys > 1;
+  m.fast = ssr_multi_fast_path(pl, est64) && n_keys > 1;
   const bool mag = want_ssim || m.fast;
   m.w = pair_ws(pl, n_items, max_len, total_rows, est64, mag);
   const int max_T = (int)ssr_num_frames(pl, max_len);
   m.w.sg = ssim_geom(max_T, pl->n_bins, m.fast ? n_items * n_keys : n_items, true);    // (the plain passes keep ssr_pair_metrics' tiles)
   m.n_tiles = m.w.sg.n_row_tiles * m.w.sg.n_strips;
-  m.plane = mag ? ssr_align256((size_t)total_rows * mag_pitch(pl->n_bins) * sizeof(float)) : 0;
+  m.plane = mag ? ssr_align256((size_t)total_rows * ssr_mag_pitch(pl->n_bins) * sizeof(float)) : 0;
   const int n_spec = ((n_keys - 1) / 2) * 2;                                  // keys whose reductions come from the images (in pairs)
   // keys of an item per wave (they share the target's rows).  Measured on cfg-3 (6 such keys, 1024 items): 1 key per wave 4.37 ms
   // (20 GB of images at 4.6 TB/s: HBM-bound), 2 per wave 3.2-3.4 ms (90 VGPRs, five waves per SIMD), 3 per wave the same,
@@ -329,7 +321,7 @@ static int multi_stage_stft(const ssr_plan* pl, const float* a, const double* a6
   p.mode = SSR_MODE_PAIR; p.out_kind = mag ? SSR_OUT_MAG : SSR_OUT_NONE; p.metric_mask = (int)mask;
   p.n_fft = pl->n_fft; p.hop = pl->hop; p.n_bins = pl->n_bins;
   p.units_per_chunk = w.units_per_chunk; p.n_chunks = w.n_chunks; p.interleave = ssr_pair_interleave(pl, a64 != nullptr);
-  p.out_a = out_a; p.out_b = out_b; p.out_pitch = mag_pitch(pl->n_bins); p.part = part;
+  p.out_a = out_a; p.out_b = out_b; p.out_pitch = ssr_mag_pitch(pl->n_bins); p.part = part;
   return ssr_launch_stft<T>(pl, p, n_items * w.n_chunks, s);
 }
 
@@ -358,7 +350,7 @@ static int pair_metrics_multi_impl(const ssr_plan* pl, const float* est, const d
   HIP_TRY(hipGetLastError());
   const bool mag = m.plane != 0;
   const size_t part_a_bytes = ssr_align256((size_t)n_items * m.w.n_chunks * SSR_NPART * sizeof(double));
-  const int pitch = mag_pitch(pl->n_bins);
+  const int pitch = ssr_mag_pitch(pl->n_bins);
   const unsigned red_mask = mask & (SSR_METRIC_LSD | SSR_METRIC_LOG_SISPEC | SSR_METRIC_SISPEC);
   auto plane_of = [&](int k) { return mag ? (float*)(ws + m.off_est + (size_t)k * m.plane) : nullptr; };
   float* tgt_plane = mag ? (float*)(ws + m.off_tgt) : nullptr;

@@ -12,6 +12,7 @@ File decoding / sox resampling are host I/O (ssr_eval_amd.io).  
 memory use ``evaluate_arrays``.
 """
 import collections
+import numbers
 import os
 
 import numpy as np
@@ -23,7 +24,17 @@ from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpas
 from .metrics import AudioMetrics
 from .utils import dict_mean, write_json
 
-_METRIC_KEYS = ("lsd", "log_sispec", "sispec", "ssim")
+# the reference's four, then the band-split LSD of SSR_Eval_Helper(lsd_split=...) (only present in runs that ask for it)
+_METRIC_KEYS = ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf")
+
+
+def key_cutoff_hz(key):
+    """Cutoff in Hz of a degradation key: the integer after the tag, floor-divided by 2 - what preprocess passed to lowpass()
+    (proc_bw_8000_4_44100 -> 4000, proc_fft_44099_44100 -> 22049: the sr - 1 quirk).  proc_mp3_* carries none: None."""
+    parts = key.split("_")
+    if len(parts) < 4 or parts[0] != "proc" or parts[1] == "mp3":
+        return None
+    return int(parts[2]) // 2
 
 
 def pipeline_batches(paths, step):
@@ -91,7 +102,12 @@ class SSR_Eval_Helper:
     def __init__(self, testee, input_sr, output_sr, evaluation_sr=44100, test_name="test",
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
-                 precision="f64", device=None, download=False):
+                 precision="f64", device=None, download=False, lsd_split=None):
+        """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
+        cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included."""
+        if lsd_split is not None and not (lsd_split is True or (isinstance(lsd_split, numbers.Real) and not isinstance(lsd_split, bool))):
+            raise ValueError("lsd_split must be None, True or a split frequency in Hz")
+        self.lsd_split = lsd_split
         self.testee = testee
         self.test_name = test_name
         self.test_data_root = test_data_root
@@ -341,6 +357,10 @@ class SSR_Eval_Helper:
             extras.append(add)
         return keys, outs, extras
 
+    def split_cutoff_hz(self, key):
+        """The split frequency of `key` under lsd_split (None: no cutoff - NaN values)."""
+        return key_cutoff_hz(key) if self.lsd_split is True else float(self.lsd_split)
+
     def evaluate_arrays(self, items, files=None, resident_inputs=None, device_mode=False, deferred=False):
         """items: list of (target waveform @ evaluation_sr, input waveform @ input_sr).
         -> list of {key: {metric: float}} (one dict per item), everything batched on the GPU.
@@ -390,6 +410,15 @@ class SSR_Eval_Helper:
                 values = self.audio_metrics.evaluation_multi(by_key, [all_tgt[i * K] for i in range(len(items))], resident=True, deferred=True)
             else:
                 values = self.audio_metrics.evaluation_batch(all_proc, all_tgt, resident=True, deferred=True)
+        if all_proc and self.lsd_split is not None:
+            # the band-split LSD, queued behind the four metrics in the same deferred batch
+            cuts = [self.split_cutoff_hz(k) for k in all_keys]
+            if multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items))):
+                splits = self.audio_metrics.lsd_split_multi(by_key, [all_tgt[i * K] for i in range(len(items))], cuts[:K],
+                                                            resident=True, deferred=True)
+                flat_splits = lambda: [r for row in splits() for r in row]     # noqa: E731
+            else:
+                flat_splits = self.audio_metrics.lsd_split_batch(all_proc, all_tgt, cuts, resident=True, deferred=True)
         self._last_processed = None
         keep = list(zip(owner, all_keys, all_proc)) if self.save_processed_result else None
 
@@ -398,8 +427,11 @@ class SSR_Eval_Helper:
             if values is not None:
                 rows = values()
                 vals = [rows[i][k] for i in range(len(items)) for k in range(K)] if multi else rows
+                if self.lsd_split is not None:
+                    for v, sp in zip(vals, flat_splits()):
+                        v.update(sp)
                 for i, k, v, e in zip(owner, all_keys, vals, all_extra):
-                    v.update(e)
+                    v.update(e)                                 # the testee's extra metrics last, as the reference's update
                     results[i][k] = v
             if keep is not None:
                 self._last_processed = {(i, k): (y.cpu().numpy() if isinstance(y, torch.Tensor) else y) for i, k, y in keep}

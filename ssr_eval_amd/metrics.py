@@ -146,6 +146,106 @@ class AudioMetrics:
             return out
         return finish if deferred else finish()
 
+    # ---- band-split LSD (not in the reference): lsd() over the bins on either side of a degradation's cutoff
+    def split_bin(self, cutoff_hz):
+        """c = int(F * (cutoff_hz / (rate / 2))), F = n_fft // 2 + 1: lowpass.cut_bin's expression at this rate's STFT size."""
+        return int((self.n_fft // 2 + 1) * (cutoff_hz / (self.rate / 2)))
+
+    def _split_edges(self, cutoff_hz):
+        """-> (edges, (lf band index or None, hf band index or None)); None for no cutoff: both NaN.  A side that comes out empty
+        (c <= 0 or c >= F) is NaN and the other side is the whole band."""
+        F = self.n_fft // 2 + 1
+        if cutoff_hz is None:
+            return None, (None, None)
+        c = self.split_bin(cutoff_hz)
+        if c <= 0:
+            return (0, F), (None, 0)
+        if c >= F:
+            return (0, F), (0, None)
+        return (0, c, F), (0, 1)
+
+    @staticmethod
+    def _split_dict(vals, which):
+        return {name: (float(vals[j]) if j is not None else float("nan")) for name, j in zip(("lsd_lf", "lsd_hf"), which)}
+
+    def lsd_bands(self, est, target, edges):
+        """[B, C, T, F] magnitude tensors x2 -> [B, C, n_bands] float64: lsd() over the bins [edges[j], edges[j + 1]) of each band.
+        edges: n_bands + 1 strictly ascending bins in [0, F] for every image, or [B, C, n_bands + 1] per image."""
+        if est.shape != target.shape or est.dim() != 4:
+            raise ValueError("expected two [B, C, T, F] tensors of one shape, got %s and %s" % (tuple(est.shape), tuple(target.shape)))
+        Bn, Cn, T, F = (int(v) for v in est.shape)
+        e = np.asarray(edges, dtype=np.int64)
+        e = np.broadcast_to(e, (Bn, Cn, e.shape[-1])) if e.ndim == 1 else e
+        if e.shape[:2] != (Bn, Cn):
+            raise ValueError("edges must be [n_bands + 1] or [B, C, n_bands + 1]")
+        v = B.spectrogram_lsd_bands(est.reshape(Bn * Cn, T, F), target.reshape(Bn * Cn, T, F), e.reshape(Bn * Cn, -1))
+        return v.to(est.device).reshape(Bn, Cn, -1)
+
+    def lsd_split(self, est, target, cutoff_hz):
+        """{'lsd_lf', 'lsd_hf'} of one (estimate, target) pair split at cutoff_hz."""
+        return self.lsd_split_batch([est], [target], [cutoff_hz])[0]
+
+    def lsd_split_batch(self, ests, targets, cutoffs_hz, resident=False, deferred=False):
+        """lsd_split for lists of pairs (the input rules of evaluation_batch: metrics.py:89-90 truncation, float64 estimates kept
+        float64; float32 targets).  cutoffs_hz: one value for every pair, or one per pair (None: both values NaN)."""
+        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
+        cuts = list(cutoffs_hz) if isinstance(cutoffs_hz, (list, tuple)) else [cutoffs_hz] * len(pairs)
+        if len(cuts) != len(pairs):
+            raise ValueError("one cutoff per pair")
+        split = [self._split_edges(c) for c in cuts]
+        groups = {}                      # (float64 estimate, number of bands) -> pair indices: one ssr_pair_lsd_bands call each
+        for i, (edges, _) in enumerate(split):
+            if edges is not None:
+                groups.setdefault((bool(B._is_f64(pairs[i][0])), len(edges) - 1), []).append(i)
+        pending = [(idx, B.pair_lsd_bands(self._plan(), [[pairs[i][0] for i in idx]], [pairs[i][1] for i in idx],
+                                          [[split[i][0] for i in idx]], deferred=True)) for idx in groups.values()]
+
+        def finish():
+            out = [self._split_dict((), (None, None)) for _ in pairs]
+            for idx, p in pending:
+                vals = p()
+                for r, i in enumerate(idx):
+                    out[i] = self._split_dict(vals[r, 0], split[i][1])
+            return out
+        return finish if deferred else finish()
+
+    def lsd_split_multi(self, ests_by_key, targets, cutoffs_hz, resident=False, deferred=False, keys_per_chunk=None):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms, cutoffs_hz = one
+        split frequency per key (None: NaN) -> n lists of K {'lsd_lf', 'lsd_hf'}.  Keys with the same estimate dtype and band count
+        share one multi-key launch sequence (the target transformed once per chunk of keys); otherwise - lengths that differ between
+        keys, a key with both dtypes - the pairs go through lsd_split_batch."""
+        K, n = len(ests_by_key), len(targets)
+        if len(cutoffs_hz) != K:
+            raise ValueError("one cutoff per key")
+        pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for i in range(n)] for k in range(K)]
+        same_len = all(len({pairs[k][i][0].shape[0] for k in range(K)}) == 1 for i in range(n))
+        kinds = [{bool(B._is_f64(pairs[k][i][0])) for i in range(n)} for k in range(K)]
+        if n == 0 or not same_len or any(len(kd) != 1 for kd in kinds):
+            flat = self.lsd_split_batch([pairs[k][i][0] for i in range(n) for k in range(K)],
+                                        [pairs[k][i][1] for i in range(n) for k in range(K)],
+                                        [cutoffs_hz[k] for _ in range(n) for k in range(K)], True, deferred=True)
+            finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
+            return finish if deferred else finish()
+        tgts = [pairs[0][i][1] for i in range(n)]
+        split = [self._split_edges(c) for c in cutoffs_hz]
+        groups = {}
+        for k, (edges, _) in enumerate(split):
+            if edges is not None:
+                groups.setdefault((next(iter(kinds[k])), len(edges) - 1), []).append(k)
+        pending = [(keys, B.pair_lsd_bands(self._plan(), [[pairs[k][i][0] for i in range(n)] for k in keys], tgts,
+                                           [[split[k][0]] * n for k in keys], deferred=True, keys_per_chunk=keys_per_chunk))
+                   for keys in groups.values()]
+
+        def finish():
+            out = [[self._split_dict((), (None, None)) for _ in range(K)] for _ in range(n)]
+            for keys, p in pending:
+                vals = p()
+                for i in range(n):
+                    for j, k in enumerate(keys):
+                        out[i][k] = self._split_dict(vals[i, j], split[k][1])
+            return out
+        return finish if deferred else finish()
+
     # ---- reductions on [B, C, T, F] tensors (est first)
     @staticmethod
     def _images(x):
