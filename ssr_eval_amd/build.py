@@ -39,38 +39,31 @@ def _obj_of(src):
     return os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
 
 
-def _stale(src, hdr_mtime, extra):
+def _stale(src, hdr_mtime):
     o = _obj_of(src)
-    stamp = o + ".flags"
-    if not os.path.exists(o) or not os.path.exists(stamp) or open(stamp).read() != " ".join(extra):
-        return True
-    return max(os.path.getmtime(src), hdr_mtime) > os.path.getmtime(o)
+    return not os.path.exists(o) or max(os.path.getmtime(src), hdr_mtime) > os.path.getmtime(o)
 
 
-def needs_build(extra=()):
+def needs_build():
     if not os.path.exists(OUT):
         return True
     h = _headers_mtime()
-    return any(_stale(u, h, list(extra)) for u in units()) or any(
-        os.path.getmtime(_obj_of(u)) > os.path.getmtime(OUT) for u in units())
+    return any(_stale(u, h) for u in units()) or any(os.path.getmtime(_obj_of(u)) > os.path.getmtime(OUT) for u in units())
 
 
-def build(force=False, verbose=False, extra=(), jobs=None, out=None):
-    """extra: additional compiler flags (e.g. -DSSR_DEV_KNOBS for the profiling tools)."""
-    extra = list(extra)
+def build(force=False, verbose=False, jobs=None, out=None):
     out = out or OUT
-    if not force and out == OUT and not needs_build(extra):
+    if not force and out == OUT and not needs_build():
         return out
     os.makedirs(OBJ, exist_ok=True)
     cc, h = hipcc(), _headers_mtime()
-    todo = [u for u in units() if force or _stale(u, h, extra)]
+    todo = [u for u in units() if force or _stale(u, h)]
 
     def one(src):
-        cmd = [cc] + FLAGS + extra + ["-c", src, "-o", _obj_of(src)]
+        cmd = [cc] + FLAGS + ["-c", src, "-o", _obj_of(src)]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-        open(_obj_of(src) + ".flags", "w").write(" ".join(extra))
 
     with ThreadPoolExecutor(max_workers=jobs or max(1, (os.cpu_count() or 2))) as ex:
         list(ex.map(one, todo))
@@ -82,4 +75,4 @@ def build(force=False, verbose=False, extra=(), jobs=None, out=None):
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True, extra=[a for a in sys.argv[1:] if a.startswith("-D")]))
+    print(build(force="--force" in sys.argv, verbose=True))

@@ -69,9 +69,6 @@ static inline double ssr_fmul_rn(double a, double b) { volatile double r = a * b
 static inline double ssr_fadd_rn(double a, double b) { volatile double r = a + b; return r; }
 #else
 #include <hip/hip_runtime.h>
-#if defined(SSR_FULL_BARRIER)
-#define SSR_BARRIER() __syncthreads()
-#else
 // Workgroup barrier that orders LDS traffic only.  All cross-thread hand-offs inside a kernel body go
 // through LDS; __syncthreads() would additionally drain every outstanding GLOBAL access (s_waitcnt
 // vmcnt(0)), i.e. expose the full HBM store/load latency at every phase boundary.
@@ -81,7 +78,6 @@ static inline double ssr_fadd_rn(double a, double b) { volatile double r = a + b
     __builtin_amdgcn_s_barrier();                                       \
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");     \
   } while (0)
-#endif
 #define SSR_DEV __device__ __forceinline__
 #define SSR_BODY __device__ __forceinline__
 #define SSR_MEMBER __device__ __forceinline__
@@ -264,9 +260,6 @@ template <typename E> struct SsrRwView {
   // the same by BYTE offset; any negative offset is out of range (callers OR an all-ones mask into it to switch a lane off)
   SSR_MEMBER E ld_raw(int off) const { return ld((unsigned)off / (unsigned)sizeof(E), off >= 0); }
   SSR_MEMBER void st_raw(int off, E v) const { st((unsigned)off / (unsigned)sizeof(E), v, off >= 0); }
-  SSR_MEMBER void st_raw_nt(int off, E v) const { st_raw(off, v); }
-  SSR_MEMBER void st_raw2(int off, E a, E b) const { st_raw(off, a); st_raw(off + (int)sizeof(E), b); }
-  SSR_MEMBER void st_raw4(int off, E a, E b, E c, E d) const { st_raw2(off, a, b); st_raw2(off + 2 * (int)sizeof(E), c, d); }
 #else
   __amdgpu_buffer_rsrc_t rsrc;
   SSR_MEMBER SsrRwView(E* p, int64_t n_elems)
@@ -289,24 +282,6 @@ template <typename E> struct SsrRwView {
     if constexpr (sizeof(E) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, off, 0, 0);
     else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, v), rsrc, off, 0, 0);
   }
-  // two / four consecutive 4-byte elements with one buffer_store_dwordx2 / x4 (off: 8- / 16-byte aligned)
-  SSR_MEMBER void st_raw2(int off, E a, E b) const {
-    static_assert(sizeof(E) == 4, "dword elements");
-    typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    u2 v; v.x = __builtin_bit_cast(unsigned, a); v.y = __builtin_bit_cast(unsigned, b);
-    __builtin_amdgcn_raw_buffer_store_b64(v, rsrc, off, 0, 0);
-  }
-  SSR_MEMBER void st_raw4(int off, E a, E b, E c, E d) const {
-    static_assert(sizeof(E) == 4, "dword elements");
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    u4 v; v.x = __builtin_bit_cast(unsigned, a); v.y = __builtin_bit_cast(unsigned, b); v.z = __builtin_bit_cast(unsigned, c); v.w = __builtin_bit_cast(unsigned, d);
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 0);
-  }
-  // streaming store (nt): written once, not read again by this kernel - do not displace what the caches are kept for
-  SSR_MEMBER void st_raw_nt(int off, E v) const {
-    if constexpr (sizeof(E) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, off, 0, 2);
-    else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, v), rsrc, off, 0, 2);
-  }
 #endif
 };
 
@@ -318,16 +293,13 @@ template <typename T> SSR_DEV cx<T> csub(cx<T> a, cx<T> b) { return {a.x - b.x, 
 template <typename T> SSR_DEV cx<T> cmul(cx<T> a, cx<T> b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 template <typename T> SSR_DEV cx<T> cmul_negi(cx<T> a) { return {a.y, -a.x}; }   // a * (-i)
 
-// LDS index padding for the FFT arrays: one spare element per 2^SSR_PAD_SHIFT.  An ADDITIVE pad keeps
+// LDS index padding for the FFT arrays: one spare element per 16.  An ADDITIVE pad keeps
 // pad(j + q*stride) = pad(j) + q*stride' for the power-of-two strides of the passes, so the compiler folds
 // the eight per-register offsets into the ds_read/ds_write immediate field (one address VALU op per
 // pass).  An XOR swizzle with fewer modelled bank conflicts was measured 28 % SLOWER on MI355X because it
 // needs per-access address arithmetic on a VALU-bound kernel (profiles/r01_notes.md).
-#ifndef SSR_PAD_SHIFT
-#define SSR_PAD_SHIFT 4
-#endif
-SSR_DEV int ssr_pad(int i) { return i + (i >> SSR_PAD_SHIFT); }
-SSR_HD constexpr int ssr_padded_len(int n) { return n + (n >> SSR_PAD_SHIFT) + 1; }
+SSR_DEV int ssr_pad(int i) { return i + (i >> 4); }
+SSR_HD constexpr int ssr_padded_len(int n) { return n + (n >> 4) + 1; }
 
 // centred-STFT reflect padding of sample index s into [0, n): numpy.pad(mode="reflect"), i.e. reflection about both
 // ends repeated with period 2 (n - 1) when the pad is longer than the signal (n = 1: constant).  The modulo is only

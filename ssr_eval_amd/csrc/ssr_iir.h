@@ -89,7 +89,7 @@ template <typename X> static inline void ssr_iir_item_host(const SsrIirParamsT<X
 //   * G lanes per utterance = the smallest power of two >= n_sections (1, 2, 4, 8, 16): every lane of a group owns a section, a wave
 //     carries 64 / G utterances (an order-2 design: 64) - the same recurrences on a sixth of the waves;
 //   * a chunk is SSR_IIR_CK = 16 steps: lane 0's sixteen input samples sit in registers, loaded TWO chunks ahead with 16-byte
-//     vector loads (SSR_IIR_NB = 3 rotating buffers), the last section's sixteen outputs leave with 16-byte vector stores - a step is the nine
+//     vector loads (NB = 3 rotating buffers), the last section's sixteen outputs leave with 16-byte vector stores - a step is the nine
 //     float64 operations of SciPy's statement sequence plus (G > 1) the DPP hand-off from the lane below: no LDS, no exec masking;
 //   * a chunk in which some lane starts or ends its signal, or that touches the odd extension, takes the general per-step path
 //     (a few chunks per utterance).  Lanes whose utterance has ended (or that have none) run on: nothing they compute is stored;
@@ -102,9 +102,6 @@ template <typename X> static inline void ssr_iir_item_host(const SsrIirParamsT<X
 #include <type_traits>
 
 constexpr int SSR_IIR_CK = 16;   // steps per chunk
-#ifndef SSR_IIR_NB
-#define SSR_IIR_NB 3             // rotating input buffers: requests run NB - 1 chunks ahead (5: 242 VGPRs, the same time - measured)
-#endif
 
 typedef double ssr_d2u __attribute__((ext_vector_type(2), aligned(8)));    // 16-byte accesses at the signals' own alignment
 typedef float ssr_f4u __attribute__((ext_vector_type(4), aligned(4)));
@@ -171,10 +168,6 @@ SSR_DEV void ssr_iir_pass(const SsrIirLane<X>& q, int s, int S, int edge, double
   // the sixteen inputs of chunk c (consumed by lane 0 of the group; every lane of the group requests them), 16-byte loads.
   // A lane whose chunk is not interior reads the scratch block: values nobody uses (the chunk is then not run as a regular one).
   auto load_regular = [&](int c, XT (&b)[CK]) __attribute__((always_inline)) {
-#ifdef SSR_IIR_DEV_NO_LOAD             /* developer experiment (wrong results): what the sixteen-sample loads cost */
-    SSR_UNROLL for (int k = 0; k < CK; ++k) b[k] = (XT)(0.001 * (c + k));
-    return;
-#endif
     const int t0 = c * CK;
     const bool inner = BACKWARD ? (t0 + CK <= q.ne) : (t0 >= edge && t0 + CK <= edge + q.len);
     if constexpr (BACKWARD) {
@@ -220,10 +213,6 @@ SSR_DEV void ssr_iir_pass(const SsrIirLane<X>& q, int s, int S, int edge, double
     yout = yv[CK - 1];
     const bool full = n0 >= 0 && n0 + CK <= q.ne;
     const bool keep = last && full && (BACKWARD ? (n0 >= edge && n0 + CK <= q.ne - edge) : true);
-#ifdef SSR_IIR_DEV_NO_STORE            /* developer experiment (wrong results): what the sixteen-sample stores cost */
-    if (yv[0] == 1.2345e300) q.trash[0] = yv[CK - 1];
-    return;
-#endif
     if constexpr (BACKWARD) {
       ssr_d2u* dst = reinterpret_cast<ssr_d2u*>(keep ? q.y + ((q.ne - 1 - edge - n0) - (CK - 1)) : q.trash);
       SSR_UNROLL for (int j = 0; j < CK / 2; ++j) { ssr_d2u v; v.x = yv[CK - 1 - 2 * j]; v.y = yv[CK - 2 - 2 * j]; dst[j] = v; }
@@ -236,7 +225,7 @@ SSR_DEV void ssr_iir_pass(const SsrIirLane<X>& q, int s, int S, int edge, double
   // loads, sixteen steps, eight stores, NB times - the compiler's memory-counter waits are then exact (vmcnt = the requests issued
   // since), and a wait for inputs requested NB - 1 chunks ago never waits for a store or a younger load.  (NB = 5 - 64 steps between
   // a request and its use - runs at the same 34-39 ns per step as NB = 3: the loop is not waiting for its inputs any more.)
-  constexpr int NB = SSR_IIR_NB;
+  constexpr int NB = 3;            // rotating input buffers: requests run NB - 1 chunks ahead (5: 242 VGPRs, the same time - measured)
   XT buf[NB][CK];
   auto nb_regular = [&](int c) __attribute__((always_inline)) {
     SSR_UNROLL for (int j = 0; j < NB; ++j) {

@@ -316,17 +316,12 @@ SSR_BODY void ssr_ssim_body(const SsrSsimParams& p, BLK& blk, int tile, int item
   // step s has consumed its own (two steps in flight: one was not enough to cover the load latency - each wave sat idle
   // ~80 % of its life, and neither fewer LDS bytes nor fewer instructions moved the kernel).
   const int n_steps = (W - 1) + (r1 - r0);
-#if defined(SSR_DEV_KNOBS) && defined(SSR_ABL_SSIM)   // timing-only ablations (wrong results): 1 no ssim_value, 2 no LDS, 4 no row loads
-#define SSR_SABL(bit) ((SSR_ABL_SSIM) & (bit))
-#else
-#define SSR_SABL(bit) 0
-#endif
 #define SSR_SSIM_STEP(s_, SET, SLOT)                                                                                         \
   SSR_PHASE(blk, regs, {                                                                                                    \
     ssr_ssim_row_apply<CPT, false, SET, SLOT>(R, tid, (s_) >= W, ncol_in);                                                   \
-    if ((s_) + 2 < n_steps && !SSR_SABL(4))                                                                                 \
+    if ((s_) + 2 < n_steps)                                                                                                 \
       ssr_ssim_row_load<CPT, false, SET>(p, R, tid, x, y, r0 + (s_) + 2, ((s_) + 2 >= W) ? r0 + (s_) + 2 - W : -1, c_in0, ncol_in); \
-    if ((s_) >= W - 1 && !SSR_SABL(2)) {                                                                                    \
+    if ((s_) >= W - 1) {                                                                                                    \
       for (int i = 0; i < VC; ++i) {                                                                                        \
         const int c = ssr_ssim_col<CPT, false>(tid, i);                                                                     \
         if (c < ncol_in)                                                                                                    \
@@ -344,8 +339,7 @@ SSR_BODY void ssr_ssim_body(const SsrSsimParams& p, BLK& blk, int tile, int item
           for (int d = 0; d < CPT + W - 1; ++d) {                                                                           \
             int c = j0 + d;                                                                                                 \
             if (c >= ncol_in) c = ncol_in - 1;      /* only feeds outputs that are masked below */                          \
-            if (SSR_SABL(2)) v[d] = R.cs[d % VC][q];                                                                        \
-            else v[d] = L.col[q * PW + ssr_ssim_slot<CPT>(c)];                                                              \
+            v[d] = L.col[q * PW + ssr_ssim_slot<CPT>(c)];                                                                   \
           }                                                                                                                 \
           double sw = v[0];                                                                                                 \
           for (int d = 1; d < W; ++d) sw += v[d];                                                                           \
@@ -356,7 +350,7 @@ SSR_BODY void ssr_ssim_body(const SsrSsimParams& p, BLK& blk, int tile, int item
           }                                                                                                                 \
         }                                                                                                                   \
         for (int i = 0; i < CPT; ++i)                                                                                       \
-          if (j0 + i < ncol_out) R.s += SSR_SABL(1) ? w[0][i] + w[1][i] + w[2][i] + w[3][i] : ssr_ssim_value(w[0][i], w[1][i], w[2][i], w[3][i]); \
+          if (j0 + i < ncol_out) R.s += ssr_ssim_value(w[0][i], w[1][i], w[2][i], w[3][i]);                                  \
       }                                                                                                                     \
     });                                                                                                                     \
   }
@@ -381,7 +375,7 @@ SSR_BODY void ssr_ssim_body(const SsrSsimParams& p, BLK& blk, int tile, int item
 #define SSR_SSIM_STEP_C(s_, SET, SLOT)                                                                                       \
     SSR_WPHASE(blk, regs, {                                                                                                  \
       ssr_ssim_row_apply_contig<CPT, SET, SLOT>(R, L.yring + (SLOT) * Lds::RW, tid);                                              \
-      if ((s_) + 2 < n_steps && !SSR_SABL(4))                                                                                \
+      if ((s_) + 2 < n_steps)                                                                                                \
         ssr_ssim_row_load<CPT, true, SET>(p, R, tid, x, y, r0 + (s_) + 2, -1, c_in0, ncol_in);                               \
     });                                                                                                                      \
     if ((s_) >= W - 1) {                                                                                                     \

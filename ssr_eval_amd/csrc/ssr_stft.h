@@ -26,12 +26,7 @@ enum { SSR_MODE_PAIR = 0, SSR_MODE_SINGLE = 1 };
 
 // points per thread of the FFT engine for a given transform length: 16 for the 8192-point Bluestein
 // transforms (512 threads x up to 256 VGPRs instead of 1024 threads x 128 VGPRs with spills), else 8.
-#ifndef SSR_PPT_2048
-#define SSR_PPT_2048 8   /* developer A/B knob for the direct 2048-point engine */
-#endif
-SSR_HD constexpr int ssr_stft_ppt(int logn, bool bluestein) {
-  return logn >= 13 ? 16 : ((logn == 11 && !bluestein) ? SSR_PPT_2048 : 8);
-}
+SSR_HD constexpr int ssr_stft_ppt(int logn, bool bluestein) { return logn >= 13 ? 16 : 8; }
 enum { SSR_OUT_NONE = 0, SSR_OUT_MAG = 1, SSR_OUT_COMPLEX = 2 };
 enum { SSR_M_LSD = 1, SSR_M_LOG_SISPEC = 2, SSR_M_SISPEC = 4, SSR_M_SSIM = 8 };
 
@@ -120,13 +115,7 @@ template <typename T> SSR_DEV SsrBinOut<T> ssr_separate(cx<T> zk, cx<T> zn) {
 
 // |re + i im| for float32 parts: numpy.abs(complex64) is hypotf (a plain sqrtf(re^2 + im^2) measured slower
 // in this kernel, profiles/r01_notes.md).
-SSR_DEV float ssr_cabsf(float re, float im) {
-#ifdef SSR_FASTABS_ALL   /* developer A/B: the fast magnitude in every engine */
-  return sqrtf(fmaf(re, re, im * im));
-#else
-  return hypotf(re, im);
-#endif
-}
+SSR_DEV float ssr_cabsf(float re, float im) { return hypotf(re, im); }
 
 // The same magnitude without ocml's hypotf (~25 instructions of scaling logic: 1/5 of the wave engine's epilogue): one
 // float32 multiply, one fused multiply-add and the 1-ulp hardware square root - within 1.5 ulp of the correctly rounded
@@ -587,11 +576,7 @@ SSR_BODY void ssr_stft_body(const SsrStftParams<T>& p, BLK& blk, int chunk, int 
 
   BLK blk0 = blk;
   for (int u = u0; u < u1; ++u) {
-#if defined(SSR_LAUNDER_ALL)
-    blk = blk0; ssr_launder(blk);
-#else
     if constexpr (PPT > 8) { blk = blk0; ssr_launder(blk); }   // see ssr_launder: keeps addresses out of scratch
-#endif
     const int ta = (MODE == SSR_MODE_PAIR) ? u : 2 * u;
     const int tb = (MODE == SSR_MODE_PAIR) ? u : 2 * u + 1;
     const bool a_ok = ta < n_frames, b_ok = tb < n_frames;       // a missing frame re-reads the last one, scaled by 0

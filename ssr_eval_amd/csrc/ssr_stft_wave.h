@@ -23,45 +23,10 @@
 
 // (SSR_WPHASE / SSR_WAVE_SYNC: ssr_block.h)
 
-// Developer build (-DSSR_PHASE_CLOCKS): shader-clock stamps at the phase boundaries of k_stft_wave's frame loop, summed per
-// launch (tu_stft.inc prints them).  SSR_CLK(i) is empty everywhere else.
-#define SSR_CLK(i)
-#if defined(SSR_PHASE_CLOCKS) && !defined(SSR_HOST_EMU)
-static __device__ unsigned long long ssr_dbg_clk[8];
-#define SSR_CLK_NOW(i) do { SSR_SCHED_BARRIER(); clk_[i] = __builtin_readcyclecounter(); SSR_SCHED_BARRIER(); } while (0)
-#endif
-
-// k_stft_wave's third pass in PAIRED butterfly order (below): 1 = the product, 0 = the ascending order + half exchange of
-// rounds 2-5 (A/B builds)
-#ifndef SSR_WAVE_PAIRED
-#define SSR_WAVE_PAIRED 1
-#endif
-// (developer builds: -DSSR_WAVE_EPI_SB_OFF lets the compiler place the epilogue's sample / window requests freely)
-#ifdef SSR_WAVE_EPI_SB_OFF
-#define SSR_WAVE_EPI_SB() do {} while (0)
-#else
-#define SSR_WAVE_EPI_SB() SSR_SCHED_BARRIER()
-#endif
-#ifdef SSR_WAVE_NOPF
-#define SSR_WAVE_PF(...) do {} while (0)
-#else
-#define SSR_WAVE_PF(...) do { __VA_ARGS__; } while (0)
-#endif
-#ifndef SSR_WAVE_PF1_SUMS
-#define SSR_WAVE_PF1_SUMS 1
-#endif
-#ifndef SSR_WAVE_PF1
-#define SSR_WAVE_PF1 0
-#endif
 constexpr int SSR_W_N = 2048, SSR_W_L = 64, SSR_W_P = 32;     // points, lanes, points per lane
 constexpr int SSR_W_TWP = 7 * 32 + 12 * 64;                   // lane-ordered twiddle copies behind the table (= SSR_WAVE_TWP)
 SSR_DEV int ssr_wpad(int i) { return i + (i >> 5); }            // lane stride 32 -> 33 doubles: conflict-free ds_*_b64
 constexpr int SSR_W_PN = SSR_W_N + (SSR_W_N >> 5) + 1;
-constexpr int SSR_W_IMOFF = 1024 + 32;    // SPLIT: the upper-half imaginary parts of the final exchange sit behind the real parts
-constexpr int SSR_W_ROWB = 4 * 1028;      // ROWS_VIA_LDS: bytes between the two staged magnitude rows (1025 bins, 16-byte aligned)
-#ifndef SSR_WAVE_ROWS_VIA_LDS
-#define SSR_WAVE_ROWS_VIA_LDS 0           // developer build: 1 (measured: a null - see ROWS_VIA_LDS below)
-#endif
 
 // exp(-2 pi i m / 32), m = 0..21 (the exponents n2 * k1 of the in-lane 4 x 8 decomposition)
 template <typename T> SSR_DEV cx<T> ssr_w32(int m) {
@@ -173,11 +138,9 @@ template <typename T, bool SPLIT, bool SUMS> constexpr size_t ssr_stft_wave_lds_
 //  radix-8 load : register 8 b + q = input q of butterfly j = tid + 64 b -> slot j + 256 q, padded tid + tid/32 + 66 b + 264 q
 //  after pass 1 : output q of butterfly j -> slot (j - k) 8 + k + 32 q, k = j mod 32,
 //                 padded 264 (tid/32) + tid mod 32 + 528 b + 33 q
-//  partner read : Z[2048 - k], k = tid + 64 b + 256 q, sits at upper-half slot 1024 - k,
-//                 padded 1056 - tid - ceil(tid/32) - 66 b - 264 q   (lane 0, b = q = 0 reads a slot it does not use)
-struct SsrWaveBase { int st0, ld8, st1, pr; };
+struct SsrWaveBase { int st0, ld8, st1; };
 SSR_DEV SsrWaveBase ssr_wave_bases(int tid) {
-  return {33 * tid, tid + (tid >> 5), 264 * (tid >> 5) + (tid & 31), 1056 - tid - ((tid + 31) >> 5)};
+  return {33 * tid, tid + (tid >> 5), 264 * (tid >> 5) + (tid & 31)};
 }
 SSR_DEV constexpr int ssr_w_off_st0(int i) { return ssr_dft32_freq(i); }
 SSR_DEV constexpr int ssr_w_off_ld8(int i) { return 66 * (i >> 3) + 264 * (i & 7); }
@@ -260,7 +223,6 @@ SSR_DEV int ssr_w_rd_paired(const SsrWavePBase& B, int i) {
       SSR_UNROLL for (int q = 1; q < 8; ++q) R.v[8 * b + q] = cmul(R.v[8 * b + q], R.tw1[q - 1]);                   \
       ssr_bfly8(R.v + 8 * b);                                                                                       \
     }                                                                                                               \
-    SSR_CLK(2);                                                                                                     \
   });                                                                                                               \
   blk = BLK0; ssr_launder(blk);                                                                                     \
   EXCH2;                                                                                                            \
@@ -279,7 +241,6 @@ SSR_DEV int ssr_w_rd_paired(const SsrWavePBase& B, int i) {
       x[7] = cmul(x[7], cmul(w3, w4));                                                                              \
       ssr_bfly8(x);                                                                                                 \
     }                                                                                                               \
-    SSR_CLK(3);                                                                                                     \
   });
 
 // Request unit u's samples into the prefetch registers (branch-free, always valid addresses, reflection only at the ends).
@@ -321,14 +282,8 @@ template <typename REGS> SSR_DEV void ssr_wave_flags(REGS& R, int tid, int* nz, 
 template <typename T, bool SUMS, bool SPLIT, int MAG = -1, typename BLK>
 SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk, int item, char* lds_base) {
   constexpr int N = SSR_W_N, F = N / 2 + 1;
-  constexpr bool PAIRED = SSR_WAVE_PAIRED != 0;
-  // Developer variant (round 6, -DSSR_WAVE_ROWS_VIA_LDS=1; NOT the product): the two magnitude rows of a frame leave as 2 x 4 aligned
-  // 16-byte stores per lane instead of 2 x 16 dword stores - laid out in bin order in the wave's exchange array (free between the last
-  // pass and the next frame's first exchange; the DS operations of a wave execute in order) and read back four consecutive bins per
-  // lane.  The premise: the address unit is busy 60-67 % of this kernel and its address FIFO fills 16x as often as in the variant that
-  // stores no rows (profiles/r06_stft_wave_vmem_path.txt).  Measured: 136 -> 112 vector-memory instructions per frame pair, the same
-  // time (2.34 ms alternating on one box, three rounds; same magnitudes, 84 tests) - the 0.5 ms the rows cost is not instruction count.
-  constexpr bool ROWS_VIA_LDS = PAIRED && SSR_WAVE_ROWS_VIA_LDS != 0;
+  // (the magnitude rows staged through LDS and stored as 16-byte writes instead - 136 -> 112 vector-memory instructions per frame
+  // pair - measured the same time, 2.34 ms: the 0.5 ms the rows cost is not instruction count; profiles/r06_stft_wave_vmem_path.txt)
   using Regs = SsrWaveRegs<T, SUMS>;
   SsrWaveLds<T, SPLIT> L(lds_base);
   const int n = p.len[item], hop = p.hop;
@@ -366,11 +321,6 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
   });
 
   BLK blk0 = blk;
-#ifdef SSR_CLK_NOW
-#undef SSR_CLK
-#define SSR_CLK(i) SSR_CLK_NOW(i)
-  unsigned long long clk_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, clk_sum[5] = {0, 0, 0, 0, 0}, clk_top[2] = {0, 0}, clk_frames = 0;
-#endif
   for (int u = u0, it = 0; u < u1; u += S, ++it) {
     // The lane's table values (window, twiddles) and addresses are loop-invariant, and 128 + 64 registers of data and
     // prefetched samples leave no room to keep them: with the lane index opaque the optimiser cannot hoist them out of the
@@ -380,40 +330,19 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
     // ---- pass 0: window, radix-32 DFT in registers (Stockham pass with stride 1: no twiddle).  Lane 0 also closes the
     // previous frame's LSD.
     SSR_WPHASE(blk, regs, {
-      SSR_CLK(0);
-#ifdef SSR_WAVE_NOPF   /* developer experiment: no frame-ahead requests - the unit's samples and window are loaded here (occupancy study) */
-      ssr_wave_prefetch<T>(p, R, tid, va, vb, u, n, n_frames);
-      SSR_UNROLL for (int r = 0; r < SSR_W_P / 2; ++r) R.wl[r] = vw.at(SSR_UIDX(tid + 64 * r));
-#endif
       ssr_wave_flags(R, tid, L.nz, it & 1);            // silent-frame votes of this unit, read by its epilogue
-      SSR_CLK(6);
       SSR_UNROLL for (int r = 0; r < SSR_W_P; ++r) {
         const T w = (r < SSR_W_P / 2) ? R.wl[r] : (T)0.5 - R.wl[r - SSR_W_P / 2];       // w[m + N/2] = 1/2 - w[m]
         R.v[r] = {(T)R.pa[r] * w, (T)R.pb[r] * w};
       }
-      SSR_CLK(7);
       ssr_dft32(R.v);
       if (want_lsd && it > 0 && tid == 0) R.lsd_total += sqrt(L.sc1[0] / (double)F);
-      SSR_CLK(1);
     });
 #define VT vt
-    if constexpr (PAIRED) { SSR_W_FFT_TAIL_PAIRED(blk, blk0, regs, L); } else { SSR_W_FFT_TAIL(blk, blk0, regs, L, ); }
+    SSR_W_FFT_TAIL_PAIRED(blk, blk0, regs, L);
 #undef VT
-    // PAIRED: register 8 b + q holds Z[j_b + 256 q], j = tid, 64 + tid, 192 - tid, 256 - tid (lane 0: 0, 64, 192, 128) - every
+    // register 8 b + q holds Z[j_b + 256 q], j = tid, 64 + tid, 192 - tid, 256 - tid (lane 0: 0, 64, 192, 128) - every
     // partner Z[2048 - k] of the lane's bins is in the lane's own registers (see SSR_W_FFT_TAIL_PAIRED).
-    // Ascending order: register 8 b + q holds Z[k], k = tid + 64 b + 256 q.  The bins k <= 1024 are this lane's to emit; each
-    // needs Z[2048 - k], which lives in the upper half (q >= 4) of lane 64 - tid: the upper halves go through LDS once.
-    if constexpr (PAIRED) {
-    } else if constexpr (!SPLIT) {
-      SSR_WPHASE(blk, regs, { const int w_ = ssr_wave_bases(tid).ld8;
-        SSR_UNROLL for (int b = 0; b < 4; ++b) SSR_UNROLL for (int q = 4; q < 8; ++q) {
-          L.re[w_ + 66 * b + 264 * (q - 4)] = R.v[8 * b + q].x; L.im[w_ + 66 * b + 264 * (q - 4)] = R.v[8 * b + q].y; } });
-    } else {
-      SSR_WPHASE(blk, regs, { const int w_ = ssr_wave_bases(tid).ld8;
-        SSR_UNROLL for (int b = 0; b < 4; ++b) SSR_UNROLL for (int q = 4; q < 8; ++q) {
-          L.re[w_ + 66 * b + 264 * (q - 4)] = R.v[8 * b + q].x;
-          L.re[SSR_W_IMOFF + w_ + 66 * b + 264 * (q - 4)] = R.v[8 * b + q].y; } });
-    }
 
     // ---- epilogue: four groups of four bins (partner values in, magnitudes out per group: few registers live at once)
     blk = blk0; ssr_launder(blk);
@@ -422,73 +351,49 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
     float* rb0 = p.out_b ? p.out_b + (row0 + u) * OP : nullptr;
     SSR_WPHASE(blk, regs, {
       // UNCONDITIONAL (the last frame of a chunk re-requests a clamped, valid frame that nobody consumes): under a condition
-      // the previous contents of the 64 + 32 registers would stay live through all three passes for the path not taken
-      // The first signal and the window now (32 + 16 requests), the second signal half-way through the bins: 64 + 16 at once
-      // stopped the wave at the 64th request until the oldest ones had returned, i.e. exposed the latency it is here to hide.
-      // PAIRED: all 128 data registers are live here, and a quarter of them is released per butterfly group - the first
+      // the previous contents of the 64 + 32 registers would stay live through all three passes for the path not taken.
+      // The two signals are requested at different times: 64 + 16 requests at once stop the wave at the 64th until the oldest
+      // ones have returned, i.e. expose the latency they are here to hide.
+      // All 128 data registers are live here, and a quarter of them is released per butterfly group - the first
       // signal is requested after group 0, the second after group 1, the window (the shortest way: L1 / L2) after group 2
-      if constexpr (!PAIRED) {
-        ssr_wave_prefetch<T, 1>(p, R, tid, va, vb, u + S, n, n_frames);
-        SSR_UNROLL for (int r = 0; r < SSR_W_P / 2; ++r) R.wl[r] = vw.at(SSR_UIDX(tid + 64 * r));
-      }
       SSR_SCHED_BARRIER();
-      SSR_CLK(4);
       double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       const int par = it & 1;
       const bool a_nz = L.nonzero(0, par), b_nz = L.nonzero(1, par);
       const bool both = a_nz && b_nz;                             // wave-uniform: the common case carries no selects
-      const int im_off = SPLIT ? SSR_W_IMOFF : 0;
-      const T* lre = L.re;
-      const T* lim = SPLIT ? L.re : L.im;
       const bool store = MAG < 0 ? p.out_kind == SSR_OUT_MAG : MAG != 0;
       // the two magnitude rows as buffer views: scalar row base + one lane offset + an immediate per bin (a plain pointer
       // costs a 64-bit vector add per store)
       const SsrRwView<float> wa(ra0, store ? F : 0), wb(rb0, (store && rb0 != nullptr) ? F : 0);   // out_b == null: the target rows
       // are not written (ssr_pair_metrics_multi: they exist already) - the stores fall to the buffer range check
-      const int lane4 = 4 * tid;
-      char* mrows = reinterpret_cast<char*>(L.re);                 // ROWS_VIA_LDS: [est row | target row], SSR_W_ROWB bytes apart
       // byte offset of bin j_b + 256 q in a magnitude row: lane part + immediate
-      const int lane4_2 = PAIRED ? 4 * (192 - tid) : 0, lane4_3 = PAIRED ? 4 * ssr_wave_pj3(tid) : 0;
+      const int lane4 = 4 * tid, lane4_2 = 4 * (192 - tid), lane4_3 = 4 * ssr_wave_pj3(tid);
       auto bin_off = [&](int b, int q) -> int {
-        if constexpr (!PAIRED) return lane4 + 4 * (64 * b + 256 * q);
-        else return (b == 0 ? lane4 : b == 1 ? lane4 + 256 : b == 2 ? lane4_2 : lane4_3) + 1024 * q;
+        return (b == 0 ? lane4 : b == 1 ? lane4 + 256 : b == 2 ? lane4_2 : lane4_3) + 1024 * q;
       };
-      const int pr = PAIRED ? 0 : ssr_wave_bases(tid).pr;
       // Lane 0's butterflies 0 and 128 pair with THEMSELVES (q <-> 8 - q, bin 0 and the Nyquist bin with themselves; q <-> 7 - q):
       // its upper halves are rotated once into the registers the general rule (3 - b, 7 - q) reads.  Register 4 - the Nyquist bin
       // Z[1024], which pairs with itself - is taken right after group 0 (32 data registers are free by then), and only then
       // receives its rotated value.
       cx<T> rot4 = {(T)0, (T)0};
-      if constexpr (PAIRED) {
-        if (tid == 0) {
-          rot4 = R.v[28];
-          const cx<T> t29 = R.v[29], t30 = R.v[30], t31 = R.v[31];
-          R.v[31] = R.v[0]; R.v[30] = R.v[7]; R.v[29] = R.v[6]; R.v[28] = R.v[5];
-          R.v[7] = t31; R.v[6] = t30; R.v[5] = t29;
-        }
+      if (tid == 0) {
+        rot4 = R.v[28];
+        const cx<T> t29 = R.v[29], t30 = R.v[30], t31 = R.v[31];
+        R.v[31] = R.v[0]; R.v[30] = R.v[7]; R.v[29] = R.v[6]; R.v[28] = R.v[5];
+        R.v[7] = t31; R.v[6] = t30; R.v[5] = t29;
       }
-#ifdef SSR_WAVE_G                                                   /* developer builds: bins in flight */
-      constexpr int G = SSR_WAVE_G;
-#else
-      constexpr int G = (SUMS || PAIRED) ? 2 : 4;                  // bins in flight (the variant with running sums is tighter; PAIRED: the
-                                                                  // partners are in registers - there is no LDS latency to cover)
-#endif
+      constexpr int G = 2;                                        // bins in flight (the partners are in registers - there is no
+                                                                  // LDS latency to cover)
       // The sixteen bins, two at a time.  FAST (a compile-time fact inside each copy of the loop): both frames hold signal and
       // the mask is the variant's full set - no zero forcing, no per-bin test of the mask, and the float32 arithmetic of a
       // bin pair runs as packed instructions (ssr_pair_bins2_fast).  The wave-uniform choice is made ONCE per frame, outside
       // the loop: taken per bin it split the epilogue into 48 basic blocks with two scalar branches each.
-      constexpr int PF1 = SUMS ? SSR_WAVE_PF1_SUMS : SSR_WAVE_PF1;    // PAIRED: the butterfly group after which the first signal is requested (then the second, then the window)
+      constexpr int PF1 = SUMS ? 1 : 0;    // the butterfly group after which the first signal is requested (then the second, then the window)
       auto bins = [&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
         SSR_UNROLL for (int b = 0; b < 4; ++b) SSR_UNROLL for (int q0 = 0; q0 < 4; q0 += G) {
           cx<T> zn[G];
-          if constexpr (PAIRED) {
-            SSR_UNROLL for (int q = 0; q < G; ++q) zn[q] = R.v[8 * (3 - b) + 7 - (q0 + q)];   // Z[2048 - k] out of butterfly 256 - j
-          } else {
-            SSR_UNROLL for (int q = 0; q < G; ++q)                    // Z[2048 - k] sits at upper-half slot 1024 - k
-              zn[q] = {lre[pr - 66 * b - 264 * (q0 + q)], lim[im_off + pr - 66 * b - 264 * (q0 + q)]};
-            if (b == 0 && q0 == 0 && tid == 0) zn[0] = R.v[0];       // bin 0 pairs with itself
-          }
+          SSR_UNROLL for (int q = 0; q < G; ++q) zn[q] = R.v[8 * (3 - b) + 7 - (q0 + q)];   // Z[2048 - k] out of butterfly 256 - j
           SSR_UNROLL for (int q = 0; q < G; q += 2) {
             const cx<T> zk0 = R.v[8 * b + q0 + q], zk1 = R.v[8 * b + q0 + q + 1];
             f2 e, t;
@@ -501,27 +406,13 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
               e = f2_make(e0, e1); t = f2_make(t0, t1);
             }
             if (store) {
-              if constexpr (ROWS_VIA_LDS) {                          // the two rows in bin order in the exchange array (free until the next exchange)
-                *reinterpret_cast<float*>(mrows + bin_off(b, q0 + q)) = e.x;
-                *reinterpret_cast<float*>(mrows + bin_off(b, q0 + q + 1)) = e.y;
-                *reinterpret_cast<float*>(mrows + SSR_W_ROWB + bin_off(b, q0 + q)) = t.x;
-                *reinterpret_cast<float*>(mrows + SSR_W_ROWB + bin_off(b, q0 + q + 1)) = t.y;
-              } else {
-#ifdef SSR_WAVE_ROWS_NT                                              /* developer build: the rows as streaming (nt) stores */
-                wa.st_raw_nt(bin_off(b, q0 + q), e.x);
-                wa.st_raw_nt(bin_off(b, q0 + q + 1), e.y);
-                wb.st_raw_nt(bin_off(b, q0 + q), t.x);
-                wb.st_raw_nt(bin_off(b, q0 + q + 1), t.y);
-#else
-                wa.st_raw(bin_off(b, q0 + q), e.x);
-                wa.st_raw(bin_off(b, q0 + q + 1), e.y);
-                wb.st_raw(bin_off(b, q0 + q), t.x);
-                wb.st_raw(bin_off(b, q0 + q + 1), t.y);
-#endif
-              }
+              wa.st_raw(bin_off(b, q0 + q), e.x);
+              wa.st_raw(bin_off(b, q0 + q + 1), e.y);
+              wb.st_raw(bin_off(b, q0 + q), t.x);
+              wb.st_raw(bin_off(b, q0 + q + 1), t.y);
             }
           }
-          if (PAIRED && b == 0 && q0 + G == 4) {
+          if (b == 0 && q0 + G == 4) {
             if (tid == 0) {                                           // the Nyquist bin, then register 4's rotated value
               const cx<T> zq = R.v[4];
               float e, t;
@@ -530,74 +421,31 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
               R.v[4] = rot4;
             }
           }
-          if ((PAIRED ? b == PF1 : false) && q0 + G == 4) {
-            SSR_WAVE_EPI_SB();
-            SSR_WAVE_PF(ssr_wave_prefetch<T, 1>(p, R, tid, va, vb, u + S, n, n_frames));
-            SSR_WAVE_EPI_SB();
+          if (b == PF1 && q0 + G == 4) {
+            SSR_SCHED_BARRIER();
+            ssr_wave_prefetch<T, 1>(p, R, tid, va, vb, u + S, n, n_frames);
+            SSR_SCHED_BARRIER();
           }
-          if (b == (PAIRED ? PF1 + 1 : 1) && q0 + G == 4) {
-            SSR_WAVE_EPI_SB();
-            SSR_WAVE_PF(ssr_wave_prefetch<T, 2>(p, R, tid, va, vb, u + S, n, n_frames));
-            SSR_WAVE_EPI_SB();
+          if (b == PF1 + 1 && q0 + G == 4) {
+            SSR_SCHED_BARRIER();
+            ssr_wave_prefetch<T, 2>(p, R, tid, va, vb, u + S, n, n_frames);
+            SSR_SCHED_BARRIER();
           }
-          if ((PAIRED ? b == PF1 + 2 : false) && q0 + G == 4) {
-            SSR_WAVE_EPI_SB();
-            SSR_WAVE_PF(SSR_UNROLL for (int r = 0; r < SSR_W_P / 2; ++r) R.wl[r] = vw.at(SSR_UIDX(tid + 64 * r)));
-            SSR_WAVE_EPI_SB();
+          if (b == PF1 + 2 && q0 + G == 4) {
+            SSR_SCHED_BARRIER();
+            SSR_UNROLL for (int r = 0; r < SSR_W_P / 2; ++r) R.wl[r] = vw.at(SSR_UIDX(tid + 64 * r));
+            SSR_SCHED_BARRIER();
           }
-        }
-        if (PAIRED && PF1 + 2 > 3) {                              // (the window behind the last group)
-          SSR_WAVE_EPI_SB();
-          SSR_WAVE_PF(SSR_UNROLL for (int r = 0; r < SSR_W_P / 2; ++r) R.wl[r] = vw.at(SSR_UIDX(tid + 64 * r)));
-          SSR_WAVE_EPI_SB();
         }
       };
       constexpr int FULL = SUMS ? (SSR_M_LSD | SSR_M_LOG_SISPEC | SSR_M_SISPEC) : SSR_M_LSD;
       if (both && (mask & 7) == FULL) bins(SsrTrue{});
       else bins(SsrFalse{});
-      if (!PAIRED && tid == 0) {                                  // the Nyquist bin: Z[1024] pairs with itself
-        const cx<T> zq = {lre[0], lim[im_off]};
-        float e, t;
-        ssr_pair_bin<T, 0, true>(mask, acc, zq, zq, a_nz, b_nz, e, t);
-        if (store) { wa.st_raw(4 * (N / 2), e); wb.st_raw(4 * (N / 2), t); }
-      }
       if (want_lsd) SSR_WAVE_SUM_STORE(tid, 64, acc[0], L.sc1);
       if constexpr (SUMS)
         for (int q = 0; q < 6; ++q) SSR_LDS_ACCUM(lsum + 64 * q + tid, acc[1 + q]);
-      SSR_CLK(5);
     });
-    if constexpr (ROWS_VIA_LDS) {
-      SSR_WPHASE(blk, regs, {
-        const bool store = MAG < 0 ? p.out_kind == SSR_OUT_MAG : MAG != 0;
-        if (store) {                                                // (wave-uniform)
-          const SsrRwView<float> wa(ra0, F), wb(rb0, rb0 != nullptr ? F : 0);
-          const char* mrows = reinterpret_cast<const char*>(L.re);
-          SSR_UNROLL for (int j = 0; j < 4; ++j) {                  // bins 4 tid + 256 j .. + 3 (bin 1024 went out with lane 0's own store)
-            const int off = 16 * tid + 1024 * j;
-            const float* ea = reinterpret_cast<const float*>(mrows + off);
-            const float* ta = reinterpret_cast<const float*>(mrows + SSR_W_ROWB + off);
-            const float e0 = ea[0], e1 = ea[1], e2 = ea[2], e3 = ea[3], t0 = ta[0], t1 = ta[1], t2 = ta[2], t3 = ta[3];
-            wa.st_raw4(off, e0, e1, e2, e3);
-            wb.st_raw4(off, t0, t1, t2, t3);
-          }
-        }
-      });
-    }
-#ifdef SSR_CLK_NOW
-    for (int q = 0; q < 5; ++q) clk_sum[q] += clk_[q + 1] - clk_[q];
-    clk_top[0] += clk_[6] - clk_[0]; clk_top[1] += clk_[7] - clk_[6];
-    ++clk_frames;
-#endif
   }
-#ifdef SSR_CLK_NOW
-#undef SSR_CLK
-#define SSR_CLK(i)
-  if (blk.tid == 0) {
-    for (int q = 0; q < 5; ++q) atomicAdd(&ssr_dbg_clk[q], clk_sum[q]);
-    atomicAdd(&ssr_dbg_clk[5], clk_frames);
-    atomicAdd(&ssr_dbg_clk[6], clk_top[0]); atomicAdd(&ssr_dbg_clk[7], clk_top[1]);
-  }
-#endif
 
   if (part == nullptr) return;
   // ---- chunk tail: last frame's LSD and the wave-sums of the SISpec accumulators

@@ -27,14 +27,12 @@ inline SsrEngine ssr_pick_engine(int n_fft) {
   if (ssr_is_pow2(n_fft) && n_fft >= 256 && n_fft <= 4096) { e.ok = true; e.logn = ssr_ilog2(n_fft); return e; }
   int m = 256;
   while (m < 2 * n_fft - 1) m <<= 1;
-#ifndef SSR_NO_RADIX3
   if (n_fft % 3 == 0 && m >= 8192) {
     const int q = n_fft / 3;
     int mq = 256;
     while (mq < 2 * q - 1) mq <<= 1;
     if (mq <= 2048) { e.ok = true; e.bluestein = true; e.logn = ssr_ilog2(mq); e.radix = 3; e.q = q; return e; }
   }
-#endif
   if (m > 8192) return e;
   e.ok = true; e.bluestein = true; e.logn = ssr_ilog2(m);
   return e;
@@ -53,12 +51,10 @@ inline SsrEngine ssr_pick_wave_engine(int n_fft) {
   if (e.radix == 3) w = (e.logn == 11 && e.q <= 768) ? e : none;
   else if (e.logn == 11) w = e;                                            // R = 1, q = n_fft
   else if (e.logn == 12 && n_fft % 2 == 0 && n_fft / 2 <= 1024) w = SsrEngine{true, true, 11, 2, n_fft / 2, 0};
-#ifndef SSR_NO_M1536
   // The chirp-z of a sub-sequence of q <= 768 samples only needs M >= 2 q - 1 = 1535: M = 1536 = 24 x 64 (24 points per lane, an
   // in-register radix-24 first pass; ssr_fft24.h) does a quarter less arithmetic than M = 2048.  Every AudioMetrics(rate) size
   // qualifies (q = 743 or 557).
   if (w.ok && w.q <= 768) w.m = 1536;
-#endif
   return w;
 }
 

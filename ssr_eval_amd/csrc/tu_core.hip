@@ -24,28 +24,13 @@ int ssr_check_plan_device(const ssr_plan* pl, bool ex_ok) {
 }
 
 // workgroups per launch aimed for when chunking items
-int ssr_target_wgs() {
-#ifdef SSR_DEV_KNOBS
-  static const int v = getenv("SSR_TARGET_WGS") ? atoi(getenv("SSR_TARGET_WGS")) : 4096;
-  return v;
-#else
-  return 4096;
-#endif
-}
+int ssr_target_wgs() { return 4096; }
 
 bool ssr_stft_uses_wave_engine(const ssr_plan* pl, bool in64) {
-#ifdef SSR_DEV_KNOBS
-  static const int off = getenv("SSR_NO_WAVE") ? atoi(getenv("SSR_NO_WAVE")) : 0;
-  if (off) return false;
-#endif
   return !in64 && !pl->eng.bluestein && pl->eng.radix == 1 && pl->eng.logn == 11;
 }
 
 int ssr_stft_rn_wave_radix(const ssr_plan* pl) {
-#ifdef SSR_DEV_KNOBS
-  static const int off = getenv("SSR_NO_WAVE") ? atoi(getenv("SSR_NO_WAVE")) : 0;
-  if (off) return 0;
-#endif
   return pl->weng.ok ? pl->weng.radix : 0;
 }
 
@@ -58,13 +43,7 @@ int ssr_pair_units_per_chunk(const ssr_plan* pl, int max_units, int n_items, boo
 }
 
 int ssr_pair_interleave(const ssr_plan* pl, bool in64) {
-  if (!ssr_stft_uses_wave_engine(pl, in64)) return 1;
-#ifdef SSR_DEV_KNOBS
-  static const int v = getenv("SSR_WAVE_INTERLEAVE") ? atoi(getenv("SSR_WAVE_INTERLEAVE")) : 8;
-  return v > 1 ? v : 1;
-#else
-  return 8;
-#endif
+  return ssr_stft_uses_wave_engine(pl, in64) ? 8 : 1;
 }
 
 int ssr_units_per_chunk_for(int max_units, int n_items, int target_wgs) {

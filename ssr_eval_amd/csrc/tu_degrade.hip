@@ -21,12 +21,9 @@ __global__ __launch_bounds__(64) void k_xcorr_pick(const double* best_val, const
   if (item < n_items) ssr_xcorr_pick(best_val, best_idx, n_lag_blocks, item, argmax_out);
 }
 
-#ifndef SSR_RESAMPLE_WPE
-#define SSR_RESAMPLE_WPE 3
-#endif
 // float32 signals: 3 workgroups per CU (<= 168 VGPRs; the LDS footprint allows three) - float64 accumulators need the 256
 template <typename S>
-__global__ __launch_bounds__(SSR_RESAMPLE_NT, sizeof(S) == 4 ? SSR_RESAMPLE_WPE : 2) void k_resample(SsrResampleParamsT<S> p, int blocks_per_item, int total) {
+__global__ __launch_bounds__(SSR_RESAMPLE_NT, sizeof(S) == 4 ? 3 : 2) void k_resample(SsrResampleParamsT<S> p, int blocks_per_item, int total) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   SsrBlk blk{(int)threadIdx.x};
   ssr_resample_persistent_body<S>(p, blk, (int)blockIdx.x, (int)gridDim.x, total, blocks_per_item, smem);
@@ -120,10 +117,6 @@ static int ssr_rc_groups(int up) {
   return best;
 }
 static bool resample_rc_eligible(int up, int down, int n_taps) {
-#ifdef SSR_DEV_KNOBS
-  static const int off = getenv("SSR_NO_RC") ? atoi(getenv("SSR_NO_RC")) : 0;
-  if (off) return false;
-#endif
   if (up < 33 || up > 1024 || (n_taps + up - 1) / up != 21) return false;
   return (size_t)4 * (ssr_rc_pairs(up, down, 21, ssr_rc_groups(up)) + 32) * sizeof(float) <= 64 * 1024;      // two stages of (x[i], x[i + down]) pairs
 }
@@ -172,10 +165,6 @@ extern "C" int ssr_resample_poly_chain(const float* in, const int64_t* in_off, c
   // the kernel forms 32-bit byte offsets into an item's output (and parks idle consumer lanes at byte 0x40000000): items of 2^28
   // samples or more take the two-call path (ssr_resample_poly rejects 2^29 itself)
   if (max_out_len >= (1 << 28)) return ssr_fail(SSR_ERR_UNSUPPORTED, "the fused chain handles outputs below 2^28 samples per item");
-#ifdef SSR_DEV_KNOBS
-  static const int off = getenv("SSR_NO_CHAIN") ? atoi(getenv("SSR_NO_CHAIN")) : 0;
-  if (off) return ssr_fail(SSR_ERR_UNSUPPORTED, "fused chain switched off");
-#endif
   // geometry of the fused kernel: 21 taps per phase in both plans, a block of 8 stage-1 steps = 24 stage-2 steps, 441 / 2 x 160 lanes
   const bool ok = (n_taps1 + up1 - 1) / up1 == 21 && (n_taps2 + up2 - 1) / up2 == 21 && up1 >= 33 && up1 <= SSR_RCC_NT1 &&
                   SSR_RCC_G2 * up2 <= SSR_RCC_NT2 && up2 >= 33 &&

@@ -2,11 +2,8 @@
 #include "ssr_host.h"
 #include "ssr_lowpass_group.h"
 
-#ifndef SSR_LOWPASS_WAVES_PER_EU
-#define SSR_LOWPASS_WAVES_PER_EU 3   /* 168 VGPRs, no spill: 3 workgroups per CU instead of 2 */
-#endif
-template <typename T, int LOGN>
-__global__ __launch_bounds__((1 << LOGN) / 8, SSR_LOWPASS_WAVES_PER_EU) void k_lowpass_frames(SsrLowpassParams<T> p) {
+template <typename T, int LOGN>   // (3 waves per EU: 168 VGPRs, no spill - 3 workgroups per CU instead of 2)
+__global__ __launch_bounds__((1 << LOGN) / 8, 3) void k_lowpass_frames(SsrLowpassParams<T> p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   SsrBlk blk{(int)threadIdx.x};
   const int item = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
@@ -61,20 +58,12 @@ __global__ __launch_bounds__(SSR_LG_NT, 2) void k_lowpass_group(SsrLowpassGroupP
 }
 
 bool ssr_lowpass_uses_wave_engine(const ssr_plan* pl) {
-#ifdef SSR_DEV_KNOBS
-  static const int off = getenv("SSR_NO_WAVE") ? atoi(getenv("SSR_NO_WAVE")) : 0;
-  if (off) return false;
-#endif
   return !pl->eng.bluestein && pl->eng.logn == 11;
 }
 
 // The wave engine hands k_ola one segment per frame PAIR (ssr_lowpass_wave.h) when the segments of every item fit the
 // item's frame rows: ceil(T / 2) (n_fft + hop) <= T n_fft for every T a signal longer than n_fft / 2 can have.
 bool ssr_lowpass_pairs_frames(const ssr_plan* pl) {
-#ifdef SSR_DEV_KNOBS
-  static const int off = getenv("SSR_NO_PAIRED") ? atoi(getenv("SSR_NO_PAIRED")) : 0;
-  if (off) return false;
-#endif
   if (!ssr_lowpass_uses_wave_engine(pl) || pl->hop > pl->n_fft / 2 || pl->wss_tab == nullptr) return false;
   int64_t t = 1 + (pl->n_fft / 2 + 1) / pl->hop;          // fewest frames of a signal that passes the reflect-pad check ...
   if (t % 2 == 0) ++t;                                     // ... the tightest case is the smallest odd count from there
@@ -115,10 +104,6 @@ static int launch_lowpass_group(const ssr_plan* pl, const float* in, const int64
   int rpc = ssr_units_per_chunk_for(max_rounds, n_items, 1024);
   if (rpc < 8) rpc = 8;
   if (rpc > max_rounds) rpc = max_rounds;
-#ifdef SSR_DEV_KNOBS
-  static const int rpc_env = getenv("SSR_LG_RPC") ? atoi(getenv("SSR_LG_RPC")) : 0;
-  if (rpc_env > 0) rpc = rpc_env;
-#endif
   gp.rounds_per_chunk = rpc;
   gp.n_chunks = ssr_ceil_div(max_rounds, rpc);
   if ((int64_t)n_items * gp.n_chunks > 0x7fffffff) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
@@ -185,12 +170,7 @@ static int run_inverse(const ssr_plan* pl, const float* in, const int64_t* in_of
   const int max_pairs = (int)((ssr_num_frames(pl, max_len) + 1) / 2);
   const int ppc = ssr_units_per_chunk_for(max_pairs, n_items, ssr_lowpass_uses_wave_engine(pl) ? 4 * ssr_target_wgs() : 0);
   int n_chunks = ssr_ceil_div(max_pairs, ppc);
-#ifdef SSR_DEV_KNOBS
-  static const int il_env = getenv("SSR_LP_INTERLEAVE") ? atoi(getenv("SSR_LP_INTERLEAVE")) : 8;
-#else
-  const int il_env = 8;
-#endif
-  const int interleave = ssr_lowpass_uses_wave_engine(pl) && il_env > 1 ? il_env : 1;     // chunks come in whole groups
+  const int interleave = ssr_lowpass_uses_wave_engine(pl) ? 8 : 1;     // chunks come in whole groups
   n_chunks = ssr_ceil_div(n_chunks, interleave) * interleave;
   int rc;
   if (pl->precision == SSR_F64) {

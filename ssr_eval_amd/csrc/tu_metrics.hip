@@ -3,14 +3,8 @@
 #include "ssr_host.h"
 #include "ssr_metrics.h"
 
-#ifndef SSR_SSIM_WAVES_PER_EU
-#define SSR_SSIM_WAVES_PER_EU 1
-#endif
-#ifndef SSR_SSIM8_WPE
-#define SSR_SSIM8_WPE 2
-#endif
 template <int CPT, bool CONTIG>
-__global__ __launch_bounds__(SSR_SSIM_NT, CPT == 8 ? SSR_SSIM8_WPE : SSR_SSIM_WAVES_PER_EU) void k_ssim(SsrSsimParams p) {      // (eight columns: 256 VGPRs)
+__global__ __launch_bounds__(SSR_SSIM_NT, 1) void k_ssim(SsrSsimParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   SsrBlk blk{(int)threadIdx.x};
   const int tiles = p.n_row_tiles * p.n_strips;
@@ -51,11 +45,6 @@ static SsimGeom ssim_geom(int max_rows, int n_bins, int n_items, bool aligned_ro
       if (strips4 * 5 * 68 < strips_c * (g.cpt + 1) * 100) g.cpt = 4;
     }
   }
-#ifdef SSR_DEV_KNOBS
-  static const int cpt_env = getenv("SSR_SSIM_CPT") ? atoi(getenv("SSR_SSIM_CPT")) : 0;
-  if (cpt_env >= 1 && cpt_env <= SSR_SSIM_MAXCPT) g.cpt = cpt_env;
-  if (cpt_env == 8 && aligned_rows) g.cpt = 8;              // the eight-column CONTIG variant (experiment: VERDICT r3 item 5)
-#endif
   g.n_strips = n_bins > 6 ? ssr_ceil_div(n_bins - 6, ssr_ssim_strip_out(g.cpt)) : 1;
   return g;
 }
@@ -100,12 +89,7 @@ extern "C" size_t ssr_pair_metrics_workspace_bytes(const ssr_plan* pl, int n_ite
 }
 
 template <int CPT, bool CONTIG = false> static int launch_ssim_inst(const SsrSsimParams& p, int grid, hipStream_t s) {
-#ifdef SSR_DEV_KNOBS
-  static const size_t extra = getenv("SSR_SSIM_LDS_EXTRA") ? (size_t)atoi(getenv("SSR_SSIM_LDS_EXTRA")) : 0;   // caps workgroups / CU
-#else
-  const size_t extra = 0;
-#endif
-  const size_t lds = SsrSsimLds<CPT, CONTIG>::bytes() + extra;
+  const size_t lds = SsrSsimLds<CPT, CONTIG>::bytes();
   static thread_local SsrLdsSlot slot;
   if (int rc = ssr_allow_lds((const void*)k_ssim<CPT, CONTIG>, lds, &slot)) return rc;
   hipLaunchKernelGGL((k_ssim<CPT, CONTIG>), dim3(grid), dim3(SSR_SSIM_NT), lds, s, p);
@@ -118,20 +102,9 @@ static int launch_ssim(const float* x, const float* y, const int64_t* frame_off,
                        int F, int pitch, const SsimGeom& g, double* part, hipStream_t s) {
   SsrSsimParams p{x, y, frame_off, n_rows, F, g.rows_per_tile, g.n_row_tiles, g.n_strips, part, pitch};
   const int grid = n_items * g.n_row_tiles * g.n_strips;
-#ifdef SSR_DEV_KNOBS
-  static const int no_contig = getenv("SSR_SSIM_NO_CONTIG") ? atoi(getenv("SSR_SSIM_NO_CONTIG")) : 0;
-#else
-  const int no_contig = 0;
-#endif
   // four consecutive columns per thread through aligned 16-byte loads: rows and both bases 16-byte aligned
-  if (g.cpt == 4 && !no_contig && pitch > 0 && pitch % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0)
+  if (g.cpt == 4 && pitch > 0 && pitch % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0)
     return launch_ssim_inst<4, true>(p, grid, s);
-#ifdef SSR_DEV_KNOBS          /* the eight-column experiment (slower, 80 B of scratch per lane): profiling builds only */
-  if (g.cpt == 8) {
-    if (pitch > 0 && pitch % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) return launch_ssim_inst<8, true>(p, grid, s);
-    return ssr_fail(SSR_ERR_UNSUPPORTED, "the eight-column SSIM kernel needs 16-byte aligned rows");
-  }
-#endif
   switch (g.cpt) {
     case 1: return launch_ssim_inst<1>(p, grid, s);
     case 2: return launch_ssim_inst<2>(p, grid, s);
@@ -283,9 +256,6 @@ static MultiWs multi_ws(const ssr_plan* pl, int n_items, int n_keys, int max_len
   // after the round-4 packing of the float32 sequences (VALU-bound before, close to HBM-bound now): 2 per wave 2.92 ms, 3 per wave
   // 2.77 ms - three where the keys divide by three (cfg-3: 6)
   m.spec_kg = (n_spec > 0 && n_spec % 3 == 0) ? 3 : 2;
-#ifdef SSR_DEV_KNOBS
-  if (getenv("SSR_SPEC_KG")) m.spec_kg = atoi(getenv("SSR_SPEC_KG"));
-#endif
   const int64_t groups = (int64_t)n_items * (n_spec > 0 ? n_spec / m.spec_kg : 1);
   int64_t spc = ((int64_t)16384 + groups - 1) / groups;                       // ~16 k one-wave workgroups
   if (spc > max_T / 8) spc = max_T / 8;
@@ -379,9 +349,6 @@ static int pair_metrics_multi_impl(const ssr_plan* pl, const float* est, const d
                     ssim_part + (size_t)key0 * n_items * m.n_tiles, pitch, n_items, (int64_t)(m.plane / sizeof(float))};
     const int grid = n_items * n_k * m.n_tiles;
     if (m.w.sg.cpt == 4) return launch_ssim_inst<4, true>(p, grid, s);
-#ifdef SSR_DEV_KNOBS
-    if (m.w.sg.cpt == 8) return launch_ssim_inst<8, true>(p, grid, s);
-#endif
     switch (m.w.sg.cpt) {
       case 1: return launch_ssim_inst<1>(p, grid, s);
       case 2: return launch_ssim_inst<2>(p, grid, s);

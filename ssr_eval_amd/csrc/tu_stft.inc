@@ -18,13 +18,7 @@ static_assert(SSR_W24_N == SSR_WAVE24_N && SSR_W24_TWP == SSR_WAVE24_TWP, "ssr_t
 // Minimum waves per SIMD asked of the register allocator.  The 2048-point direct kernel without running
 // SISpec sums fits 128 VGPRs with no spill, which admits a 4th workgroup per CU (-4.5 % time, measured);
 // the variant that carries the six sums would spill at 128, so it stays at 3.
-#ifndef SSR_MINW
-#define SSR_MINW 4
-#endif
-#ifndef SSR_MINW_SUMS
-#define SSR_MINW_SUMS 0
-#endif
-constexpr int ssr_stft_min_waves(int logn, bool blu, bool sums) { return (logn == 11 && !blu && (!sums || SSR_MINW_SUMS)) ? SSR_MINW : 1; }
+constexpr int ssr_stft_min_waves(int logn, bool blu, bool sums) { return (logn == 11 && !blu && !sums) ? 4 : 1; }
 
 #if SSR_TU_PART <= 2
 // E64 (SSR_IN_EST64 / SSR_IN_BOTH64): float64 signals (pair mode only); their float64 epilogue needs more registers,
@@ -41,12 +35,7 @@ void k_stft(SsrStftParams<T> p) {
 template <typename T, int LOGN, bool BLU, int MODE, bool SUMS, int E64 = 0>
 static int launch_stft_mode(SsrStftParams<T>& p, int grid, hipStream_t s) {
   constexpr int PPT = ssr_stft_ppt(LOGN, BLU);
-  size_t lds = SsrStftLds<T, LOGN, PPT>::bytes();
-#ifdef SSR_DEV_KNOBS
-  // SSR_LDS_PAD (bytes): over-allocate LDS to cap workgroups per CU in occupancy experiments
-  static const size_t lds_pad = getenv("SSR_LDS_PAD") ? (size_t)atol(getenv("SSR_LDS_PAD")) : 0;
-  lds += lds_pad;
-#endif
+  const size_t lds = SsrStftLds<T, LOGN, PPT>::bytes();
   static thread_local SsrLdsSlot slot;
   if (int rc = ssr_allow_lds((const void*)k_stft<T, LOGN, BLU, MODE, SUMS, E64>, lds, &slot)) return rc;
   hipLaunchKernelGGL((k_stft<T, LOGN, BLU, MODE, SUMS, E64>), dim3(grid), dim3((1 << LOGN) / PPT), lds, s, p);
@@ -76,21 +65,16 @@ template <typename T, int LOGN, bool BLU> static int launch_stft_inst(SsrStftPar
 // SPLIT = false: 33 KB (float64) of LDS per wave -> 4 waves per CU, 1 per SIMD, register budget 512;
 // SPLIT = true : 17 KB -> 8 waves per CU, 2 per SIMD, register budget 256 (the kernel fits it without a spill).
 // Measured (1024 pairs, LSD + magnitudes): 3.8 ms at one wave per SIMD - every LDS / memory issue slot and wait is exposed -
-// against 2.9 ms at two (profiles/r02_notes.md); the four-waves-per-frame engine it replaces: 3.3 ms.
-#ifndef SSR_WAVE_SPLIT
-#define SSR_WAVE_SPLIT 1
-#endif
+// against 2.9 ms at two (profiles/r02_notes.md); the four-waves-per-frame engine it replaces: 3.3 ms.  The product launches
+// SPLIT = true (the host emulation tests both layouts).
 // Block mapping under interleaving (S = p.interleave > 1): logical workgroup L = item * n_chunks + chunk = G * S + j (group G,
 // member j).  The S members of a group must share an L2 and run together: workgroups are dealt to the 8 XCDs round-robin by
 // blockIdx, so group G takes blockIdx = ((G / 8) * S + j) * 8 + G % 8 - the same XCD for every j, dispatched back to back.
 // The grid is padded to whole rounds of 8 groups (n_groups: the real count; the padding exits).
-// (developer builds: -DSSR_WAVE_MINW_F32=3 / 4 asks the allocator for three / four float32 waves per SIMD - the occupancy
-// experiment of profiles/r06_notes.md; the float64 kernel's 128 data registers allow two)
-#ifndef SSR_WAVE_MINW_F32
-#define SSR_WAVE_MINW_F32 2
-#endif
+// Two waves per SIMD for float32 too: at three the float32 kernel spills (LSD 1.57 ms against 1.54, with magnitudes 2.42 against
+// 2.14), at four far more (profiles/r06_notes.md).
 template <typename T, bool SUMS, bool SPLIT, bool MAG>
-__global__ __launch_bounds__(64, SPLIT ? (sizeof(T) == 4 ? SSR_WAVE_MINW_F32 : 2) : 1) void k_stft_wave(SsrStftParams<T> p, int n_groups) {
+__global__ __launch_bounds__(64, SPLIT ? 2 : 1) void k_stft_wave(SsrStftParams<T> p, int n_groups) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   SsrBlk blk{(int)threadIdx.x};
   int logical = (int)blockIdx.x;
@@ -104,30 +88,15 @@ __global__ __launch_bounds__(64, SPLIT ? (sizeof(T) == 4 ? SSR_WAVE_MINW_F32 : 2
   ssr_stft_wave_body<T, SUMS, SPLIT, MAG ? 1 : 0>(p, blk, chunk, item, smem);
 }
 template <typename T, bool SUMS> static int launch_stft_wave(SsrStftParams<T>& p, int grid, hipStream_t s) {
-  constexpr bool SPLIT = SSR_WAVE_SPLIT != 0;
-  size_t lds = ssr_stft_wave_lds_bytes<T, SPLIT, SUMS>();
-#ifdef SSR_CLK_NOW
-  if (const char* e = getenv("SSR_WAVE_LDS_EXTRA")) lds += (size_t)atoi(e);   // e.g. 20000: one wave per SIMD instead of two
-#endif
+  const size_t lds = ssr_stft_wave_lds_bytes<T, true, SUMS>();
   int n_groups = grid;
   if (p.interleave > 1) {
     if (p.n_chunks % p.interleave) return ssr_fail(SSR_ERR_INVALID_ARG, "interleaved chunks: n_chunks must be a multiple of the group size");
     n_groups = grid / p.interleave;
     grid = ssr_ceil_div(n_groups, 8) * 8 * p.interleave;
   }
-  if (p.out_kind == SSR_OUT_MAG) hipLaunchKernelGGL((k_stft_wave<T, SUMS, SPLIT, true>), dim3(grid), dim3(64), lds, s, p, n_groups);
-  else hipLaunchKernelGGL((k_stft_wave<T, SUMS, SPLIT, false>), dim3(grid), dim3(64), lds, s, p, n_groups);
-#ifdef SSR_CLK_NOW
-  {
-    unsigned long long c[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(c, HIP_SYMBOL(ssr_dbg_clk), sizeof c);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ssr_dbg_clk), z, sizeof z);
-    const double f = c[5] ? (double)c[5] : 1.0;
-    fprintf(stderr, "[k_stft_wave sums=%d mag=%d] cycles/frame: top+pass0 %.0f (votes incl. the wait for the samples %.0f, window %.0f) | exch1+pass1 %.0f | exch2+pass2 %.0f | half-exch+requests %.0f | bins %.0f | frames %llu\n",
-            (int)SUMS, (int)(p.out_kind == SSR_OUT_MAG), c[0] / f, c[6] / f, c[7] / f, c[1] / f, c[2] / f, c[3] / f, c[4] / f, c[5]);
-  }
-#endif
+  if (p.out_kind == SSR_OUT_MAG) hipLaunchKernelGGL((k_stft_wave<T, SUMS, true, true>), dim3(grid), dim3(64), lds, s, p, n_groups);
+  else hipLaunchKernelGGL((k_stft_wave<T, SUMS, true, false>), dim3(grid), dim3(64), lds, s, p, n_groups);
   HIP_TRY(hipGetLastError());
   return SSR_OK;
 }
@@ -241,10 +210,6 @@ template <> int ssr_launch_stft_rn_wave<TT>(const ssr_plan* pl, SsrStftParams<TT
       case 1: return launch_stft_rn_wave_sums<TT, 1, 3, 24>(p, grid, s);
       case 2: return launch_stft_rn_wave_sums<TT, 2, 3, 24>(p, grid, s);
       case 3: {
-#ifdef SSR_DEV_KNOBS
-        static const int three = getenv("SSR_R3_THREE_WAVES") ? atoi(getenv("SSR_R3_THREE_WAVES")) : 0;
-        if (three) return launch_stft_rn_wave_sums<TT, 3, 3, 24>(p, grid, s);      // the three-wave workgroups (A/B)
-#endif
         if constexpr (sizeof(TT) == 8) {
           if (p.a64 != nullptr && p.b64 != nullptr)      // two float64 estimates, images only (ssr_pair_metrics_multi_est64)
             return launch_stft_r3_rot<TT, false, 3, 24, SSR_IN_EST64X2>(p, grid, s);

@@ -197,13 +197,7 @@ static size_t tl_inv_lds(int bm) { return (size_t)3 * (2 * SSR_TL_BK * bm + 2 * 
 
 // rows per workgroup tile of the inverse product: 128 (eight waves, one workgroup per CU) once the launch fills the chip with
 // them, else 64 (four waves, two per CU)
-static int tl_pick_inv(int64_t rows) {
-  int bm = rows >= 4096 ? 128 : 64;
-#ifdef SSR_DEV_KNOBS
-  if (const char* e = getenv("SSR_TL_BM")) bm = atoi(e) == 64 ? 64 : 128;
-#endif
-  return bm;
-}
+static int tl_pick_inv(int64_t rows) { return rows >= 4096 ? 128 : 64; }
 
 template <int MODE> static int tl_launch_fwd(SsrTlParams p, int nt, hipStream_t s) {
   static thread_local SsrLdsSlot slot;

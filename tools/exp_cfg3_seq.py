@@ -1,7 +1,6 @@
 """Developer experiment: cfg-3's launch sequence (low-pass -> STFT + LSD + SISpec -> SSIM -> finalize, per cutoff) with HIP events
 BETWEEN the stages, i.e. each stage timed IN the sequence rather than alone in a loop - does the kind of low-pass kernel change
-what the kernels after it cost (clock / power management state)?  SSR_NO_FUSED_OLA=1 (with a -DSSR_DEV_KNOBS build) selects the
-round-2 low-pass."""
+what the kernels after it cost (clock / power management state)?"""
 import os, sys, json
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,7 +56,7 @@ def main():
             for s in range(3):
                 acc[s] += evs[3 * k + s].elapsed_time(evs[3 * k + s + 1])
     m = reps * len(cuts)
-    print(json.dumps({"no_fused_ola": os.environ.get("SSR_NO_FUSED_OLA", "0"), "cool_MB": COOL, "big_lds_probe": BIGLDS, "rpc": os.environ.get("SSR_LG_RPC", "auto"), "in_sequence_ms": {"fft_lowpass": round(acc[0] / m, 4), "stft+lsd+sispec": round(acc[1] / m, 4), "ssim+finalize": round(acc[2] / m, 4)},
+    print(json.dumps({"cool_MB": COOL, "big_lds_probe": BIGLDS, "in_sequence_ms": {"fft_lowpass": round(acc[0] / m, 4), "stft+lsd+sispec": round(acc[1] / m, 4), "ssim+finalize": round(acc[2] / m, 4)},
                       "ms_per_step_of_7_cutoffs": round(wall * 1e3, 3)}))
 
 

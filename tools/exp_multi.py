@@ -1,5 +1,4 @@
-"""Developer experiment: ssr_pair_metrics_multi alone (7 keys x 1024 targets of 4 s, plan 2048 / 512), HIP-event time per call.
-With a -DSSR_DEV_KNOBS build (SSR_DEV_LIB) SSR_SPEC_KG selects the keys per wave of k_specred_wave."""
+"""Developer experiment: ssr_pair_metrics_multi alone (7 keys x 1024 targets of 4 s, plan 2048 / 512), HIP-event time per call."""
 import os, sys, json
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +23,7 @@ def main():
     e0.record()
     for _ in range(reps): b.run(B.M_ALL)
     e1.record(); torch.cuda.synchronize()
-    print(json.dumps({"kg": os.environ.get("SSR_SPEC_KG", "default"), "n": n, "keys": K, "ms_per_call": round(e0.elapsed_time(e1) / reps, 4)}))
+    print(json.dumps({"n": n, "keys": K, "ms_per_call": round(e0.elapsed_time(e1) / reps, 4)}))
 
 
 main()

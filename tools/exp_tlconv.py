@@ -1,6 +1,5 @@
 """Developer tool: the SSR_LOWPASS_CONV engine against oracle/tl_chain.c and torch-CPU's own conv1d (bit-exact expected) and its
-time per launch.  PARITY=0 skips the checks; UTT = utterances of the timing runs (default 1024 x 4 s @ 48 kHz = BASELINE cfg-3);
-with a -DSSR_DEV_KNOBS build (SSR_DEV_LIB) VARIANTS="128:2,128:3,64:2" times the inverse product's tile variants."""
+time per launch.  PARITY=0 skips the checks; UTT = utterances of the timing runs (default 1024 x 4 s @ 48 kHz = BASELINE cfg-3)."""
 import os
 import sys
 import time
@@ -82,27 +81,20 @@ def main():
     data = 0.1 * torch.randn(n_utt, 192000, device="cuda", generator=g)
     r = B.Ragged.from_uniform(data)
     T = 1 + 192000 // hop
-    variants = [v.split(":") for v in os.environ.get("VARIANTS", "").split(",") if v] or [(None, None)]
-    for bm, ns in variants:
-        if bm is not None:
-            os.environ["SSR_TL_BM"], os.environ["SSR_TL_NS"] = bm, ns
-        print("== inverse tile rows %s, stages %s" % (bm or "default", ns or "default"), flush=True)
-        for cut in [int(v) for v in os.environ.get("CUTS_TIMED", "42,85,170,256,341,512,683,1025").split(",") if v]:
-            b = B.LowpassBatch(plan, r, [cut] * n_utt)
-            dt = timeit(b.run)
-            K = cut + min(cut - 1, 1023)
-            flops = n_utt * T * (2.0 * 2048 * 2 * cut + 2.0 * 2048 * 2 * K)
-            print("cut %4d: %7.2f ms per %d utterances, %.1f TFLOP/s useful" % (cut, dt * 1e3, n_utt, flops / dt / 1e12), flush=True)
-            del b
-        if os.environ.get("MULTI", "1") == "0":
-            continue
+    for cut in [int(v) for v in os.environ.get("CUTS_TIMED", "42,85,170,256,341,512,683,1025").split(",") if v]:
+        b = B.LowpassBatch(plan, r, [cut] * n_utt)
+        dt = timeit(b.run)
+        K = cut + min(cut - 1, 1023)
+        flops = n_utt * T * (2.0 * 2048 * 2 * cut + 2.0 * 2048 * 2 * K)
+        print("cut %4d: %7.2f ms per %d utterances, %.1f TFLOP/s useful" % (cut, dt * 1e3, n_utt, flops / dt / 1e12), flush=True)
+        del b
+    if os.environ.get("MULTI", "1") != "0":
         m = B.MultiLowpassBatch(plan, r, CUTS)
         dt = timeit(m.run, reps=2)
         flops = n_utt * T * (2.0 * 2048 * 2 * max(CUTS) + sum(2.0 * 2048 * 2 * (c + c - 1) for c in CUTS))
         print("multi %s: %.2f ms per %d utterances x %d keys = %.1f k pairs/s of degradation alone, %.1f TFLOP/s" % (
             CUTS, dt * 1e3, n_utt, len(CUTS), n_utt * len(CUTS) / dt / 1e3, flops / dt / 1e12), flush=True)
         del m
-    if os.environ.get("MULTI", "1") != "0":
         p64 = B.get_plan(n_fft, hop, "f64")
         b = B.LowpassBatch(p64, r, [256] * n_utt)
         print("float64 FFT engine: %.2f ms" % (timeit(b.run) * 1e3))
