@@ -258,6 +258,30 @@ int ssr_pair_lsd_bands_est64(const ssr_plan* plan, const double* est, const int6
                              const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
                              const int32_t* edges, int n_bands, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Intelligibility (not in the reference): STOI (Taal, Hendriks, Heusdens, Jensen, IEEE TASLP 19(7), 2011) and ESTOI (Jensen &
+ * Taal, IEEE/ACM TASLP 24(11), 2016) as the pystoi package (0.3.x) computes them - a restatement of that algorithm, not a copy
+ * pinned against it: silent frames of the target (40 dB below its loudest 256-sample frame) removed from both
+ * signals, 512-point STFT, 15 one-third-octave bands from 150 Hz, 30-frame segments; ESTOI without pystoi's EPS-scale random
+ * noise (deterministic), each normalisation divided by (norm + EPS).  Fewer than 30 frames left: 1e-5, as pystoi.
+ * Signals are 10 kHz float64 (resample first: ssr_resample_poly_f64 with the Octave-compatible taps of pystoi.utils.resample_oct).
+ * Pair e scores estimate e (est + est_off[e], est_len[e] samples) against target tgt_index[e]; K estimates of one target share
+ * its voice-activity mask and band image, computed once.  tgt_len, est_len and tgt_index are HOST int32 arrays (like the band
+ * edges of ssr_*_lsd_bands): validated before anything is enqueued - lengths in [0, 2^29), indices in [0, n_tgt), every estimate
+ * as long as its target - and copied into the workspace on `stream`; from page-locked memory the copy is asynchronous and the
+ * caller keeps the values unchanged until the stream has reached it.  which: SSR_STOI, SSR_ESTOI or SSR_STOI_BOTH.
+ * out: double [n_est][1] ([n_est][2] = STOI, ESTOI for SSR_STOI_BOTH).  Deterministic: fixed-order sums, no atomics.
+ * workspace: ssr_stoi_workspace_bytes (0 for invalid lengths or indices). */
+#define SSR_STOI 1
+#define SSR_ESTOI 2
+#define SSR_STOI_BOTH 3
+size_t ssr_stoi_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est);
+int ssr_stoi(const double* tgt, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt, const double* est, const int64_t* est_off,
+             const int32_t* est_len, const int32_t* tgt_index, int n_est, int which, double* out, void* workspace,
+             size_t workspace_bytes, void* stream);
+/* The band matrix of pystoi.utils.thirdoct(10000, 512, 15, 150) as bin ranges: band k sums |X|^2 over bins [lo[k], hi[k]).
+ * lo / hi: HOST int32 [15]. */
+int ssr_stoi_band_edges(int32_t* lo, int32_t* hi);
+
 /* A6.  The tensor helpers of ssr_eval/utils.py as stand-alone calls (inside ssr_pair_metrics /
  * ssr_spectrogram_metrics they are fused; these back `from ssr_eval.utils import to_log, pow_p_norm, ...`).
  *   ssr_to_log      out = log10(x + 1e-12)                       utils.py:43-44

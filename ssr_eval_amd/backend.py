@@ -654,6 +654,124 @@ def pair_lsd_bands(plan, est_lists, tgt_list, edges, deferred=False, keys_per_ch
         return Pending(out) if deferred else out.cpu().numpy()
 
 
+# ---- STOI / ESTOI ----------------------------------------------------------------------------------------------------------
+STOI_FS = 10000                  # pystoi's analysis rate
+
+
+def octave_taps(p, q):
+    """The filter of pystoi.utils.resample_oct for resample_poly(x, p, q) (p / q reduced): Octave's resample() design - a
+    Kaiser-windowed ideal low-pass at 1 / (2 max(p, q)) with 60 dB rejection - normalised to unit sum.  float64."""
+    stop = 1.0 / (2 * max(p, q))
+    roll = stop / 10
+    rej_db = 60.0
+    L = int(np.ceil((rej_db - 8) / (28.714 * roll)))
+    t = np.arange(-L, L + 1)
+    ideal = 2 * p * stop * np.sinc(2 * stop * t)
+    h = np.kaiser(2 * L + 1, 0.1102 * (rej_db - 8.7)) * ideal
+    return h / np.sum(h)
+
+
+class StoiResamplePlan:
+    """scipy.signal.resample_poly(x, 10000, fs, window=octave_taps(...)) as ssr_resample_poly_f64 runs it: with an array window
+    SciPy keeps the taps float64 (a float32 signal is resampled in float64), half_len = (len(h) - 1) // 2 and h *= up.
+    Cached per (rate, device), like ResamplePlan.get."""
+
+    _cache = {}
+
+    def __init__(self, fs, device):
+        g = math.gcd(STOI_FS, int(fs))
+        self.up, self.down = STOI_FS // g, int(fs) // g
+        self.identity = self.up == 1 and self.down == 1      # scipy returns x.copy(); pystoi does not resample at all
+        if self.identity:
+            self.half_len = self.n_pre_pad = self.n_pre_remove = 0
+            self.taps_host, self.taps64 = None, None
+            return
+        h = octave_taps(self.up, self.down) * self.up
+        self.half_len = (len(h) - 1) // 2
+        self.n_pre_pad = self.down - self.half_len % self.down
+        self.n_pre_remove = (self.half_len + self.n_pre_pad) // self.down
+        self.taps_host = np.concatenate((np.zeros(self.n_pre_pad), h))
+        self.taps64 = torch.from_numpy(self.taps_host).to(device)
+
+    @classmethod
+    def get(cls, fs, device):
+        key = (int(fs), str(device))
+        p = cls._cache.get(key)
+        if p is None:
+            p = cls._cache[key] = cls(fs, device)
+        return p
+
+    def n_out(self, n_in):
+        return int(n_in) if self.identity else -(-int(n_in) * self.up // self.down)
+
+    def n_post_pad(self, n_in):
+        """SciPy's trailing zero taps (they add nothing to the kept outputs; the device kernel reads zeros past the table)."""
+        out_len = lambda nh: ((int(n_in) - 1) * self.up + nh - 1) // self.down + 1     # noqa: E731  (upfirdn's _output_len)
+        n = 0
+        while out_len(len(self.taps_host) + n) < self.n_out(n_in) + self.n_pre_remove:
+            n += 1
+        return n
+
+
+def _host_i32(a, dev):
+    """int32 array the library reads from HOST memory: page-locked when it fits the ring (its copy then stays asynchronous)."""
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if dev.type == "cuda" and 0 < a.nbytes <= _DescRing.SIZE // 8:
+        with torch.cuda.device(dev):
+            st = _DescRing.get(torch.cuda.current_device()).stage(a, dev)
+        return st, C.c_void_p(st.data_ptr())
+    return a, a.ctypes.data_as(C.c_void_p)
+
+
+def resample_to_stoi_rate(wavs, fs, device=None):
+    """The 10 kHz float64 signals pystoi analyses: [float32 / float64 waveforms at fs] -> Ragged float64 (ssr_resample_poly_f64 with
+    the Octave taps; bit-identical to scipy.signal.resample_poly(x, 10000, fs, window=h))."""
+    dev = torch.device(device) if device is not None else default_device()
+    with torch.cuda.device(dev):
+        r = wavs if isinstance(wavs, Ragged) else Ragged.from_list(list(wavs), dev, torch.float64)
+        sp = StoiResamplePlan.get(fs, dev)
+        if sp.identity:
+            return r
+        out_len = np.array([sp.n_out(n) for n in r.lens_host], dtype=np.int64)
+        out_off = np.concatenate(([0], np.cumsum(out_len)[:-1])).astype(np.int64) if r.n else np.zeros(0, np.int64)
+        out = torch.empty(int(out_len.sum()), dtype=torch.float64, device=dev)
+        out_off_d, out_len_d = _h2d(out_off, dev), _h2d(out_len.astype(np.int32), dev)
+        if r.n and out_len.max() > 0:
+            _lib.check(_lib.load().ssr_resample_poly_f64(_vp(r.data), _vp(r.off), _vp(r.len), _vp(out_off_d), _vp(out_len_d), r.n,
+                                                         int(out_len.max()), sp.up, sp.down, _vp(sp.taps64), int(sp.taps64.numel()),
+                                                         sp.n_pre_remove, _vp(out), _stream()))
+        return Ragged(out, out_off_d, out_len_d, out_len)
+
+
+def stoi(tgt_list, est_list, tgt_index, fs, which=_lib.STOI, device=None, deferred=False):
+    """STOI / ESTOI of estimate e against target tgt_index[e] (ssr_stoi): waveforms at `fs` (float32 or float64, each estimate as
+    long as its target) -> [n_est, n_out] float64 (which = STOI_BOTH: columns STOI, ESTOI).  Targets and estimates are resampled to
+    10 kHz in one launch; each target's mask and band image are computed once for all its estimates.  deferred: a Pending."""
+    require_gpu()
+    dev = torch.device(device) if device is not None else default_device()
+    n_t, n_e = len(tgt_list), len(est_list)
+    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
+    if idx.shape[0] != n_e:
+        raise ValueError("one target index per estimate")
+    n_out = 2 if which == _lib.STOI_BOTH else 1
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty((n_e, n_out), dtype=torch.float64, device=dev)
+        if n_e:
+            r = resample_to_stoi_rate(list(tgt_list) + list(est_list), fs, dev)
+            lens = r.lens_host.astype(np.int32)
+            if idx.min() < 0 or idx.max() >= n_t:
+                raise ValueError("tgt_index out of range")
+            if not np.array_equal(lens[n_t:], lens[:n_t][idx]):
+                raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+            ws_bytes = int(lib.ssr_stoi_workspace_bytes(lens[:n_t].ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p), n_e))
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            keep = [_host_i32(a, dev) for a in (lens[:n_t], lens[n_t:], idx)]
+            _lib.check(lib.ssr_stoi(_vp(r.data), _vp(r.off), keep[0][1], n_t, _vp(r.data), _vp(r.off[n_t:]), keep[1][1], keep[2][1], n_e,
+                                    int(which), _vp(out), _vp(ws), ws_bytes, _stream()))
+        return Pending(out) if deferred else out.cpu().numpy()
+
+
 def stft(plan, wavs, kind="mag", torch_style_pad=False):
     """STFT of a list of waveforms.  kind "mag": list of [T, F] tensors; "complex": (re list, im list).
     torch_style_pad: refuse signals not longer than n_fft//2 the way torch's reflect padding does (torchlibrosa);

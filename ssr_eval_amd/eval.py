@@ -24,8 +24,11 @@ from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpas
 from .metrics import AudioMetrics
 from .utils import dict_mean, write_json
 
-# the reference's four, then the band-split LSD of SSR_Eval_Helper(lsd_split=...) (only present in runs that ask for it)
-_METRIC_KEYS = ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf")
+# the reference's four, then the band-split LSD of SSR_Eval_Helper(lsd_split=...) and the intelligibility of
+# SSR_Eval_Helper(stoi=...) (only present in runs that ask for them)
+_METRIC_KEYS = ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi", "estoi")
+# SSR_Eval_Helper(stoi=...) -> AudioMetrics.stoi_* `extended`
+_STOI_OPTIONS = {"stoi": False, "estoi": True, "both": "both"}
 
 
 def key_cutoff_hz(key):
@@ -102,9 +105,14 @@ class SSR_Eval_Helper:
     def __init__(self, testee, input_sr, output_sr, evaluation_sr=44100, test_name="test",
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
-                 precision="f64", device=None, download=False, lsd_split=None):
+                 precision="f64", device=None, download=False, lsd_split=None, stoi=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
-        cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included."""
+        cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
+        stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
+        (AudioMetrics.stoi_multi / stoi_batch at evaluation_sr)."""
+        if stoi is not None and not (isinstance(stoi, str) and stoi in _STOI_OPTIONS):
+            raise ValueError("stoi must be None, 'stoi', 'estoi' or 'both'")
+        self.stoi = stoi
         if lsd_split is not None and not (lsd_split is True or (isinstance(lsd_split, numbers.Real) and not isinstance(lsd_split, bool))):
             raise ValueError("lsd_split must be None, True or a split frequency in Hz")
         self.lsd_split = lsd_split
@@ -419,6 +427,14 @@ class SSR_Eval_Helper:
                 flat_splits = lambda: [r for row in splits() for r in row]     # noqa: E731
             else:
                 flat_splits = self.audio_metrics.lsd_split_batch(all_proc, all_tgt, cuts, resident=True, deferred=True)
+        if all_proc and self.stoi is not None:
+            # intelligibility, queued behind the band split in the same deferred batch; the multi path analyses each target once
+            ext = _STOI_OPTIONS[self.stoi]
+            if multi:
+                st = self.audio_metrics.stoi_multi(by_key, [all_tgt[i * K] for i in range(len(items))], ext, resident=True, deferred=True)
+                flat_stoi = lambda: [st_[k] for st_ in st() for k in range(K)]     # noqa: E731
+            else:
+                flat_stoi = self.audio_metrics.stoi_batch(all_proc, all_tgt, ext, resident=True, deferred=True)
         self._last_processed = None
         keep = list(zip(owner, all_keys, all_proc)) if self.save_processed_result else None
 
@@ -430,6 +446,9 @@ class SSR_Eval_Helper:
                 if self.lsd_split is not None:
                     for v, sp in zip(vals, flat_splits()):
                         v.update(sp)
+                if self.stoi is not None:
+                    for v, sv in zip(vals, flat_stoi()):
+                        v.update(sv)
                 for i, k, v, e in zip(owner, all_keys, vals, all_extra):
                     v.update(e)                                 # the testee's extra metrics last, as the reference's update
                     results[i][k] = v

@@ -246,6 +246,63 @@ class AudioMetrics:
             return out
         return finish if deferred else finish()
 
+    # ---- STOI / ESTOI (not in the reference): intelligibility as pystoi computes it, at self.rate
+    @staticmethod
+    def _stoi_which(extended):
+        if extended is False or extended is True:
+            return B._lib.ESTOI if extended else B._lib.STOI
+        if isinstance(extended, str) and extended == "both":
+            return B._lib.STOI_BOTH
+        raise ValueError("extended must be False (STOI), True (ESTOI) or 'both'")
+
+    @staticmethod
+    def _stoi_dicts(vals, which):
+        names = {B._lib.STOI: ("stoi",), B._lib.ESTOI: ("estoi",), B._lib.STOI_BOTH: ("stoi", "estoi")}[which]
+        return [{k: float(v) for k, v in zip(names, row)} for row in vals]
+
+    def stoi(self, est, target, extended=False):
+        """STOI (extended=False), ESTOI (True) of one (estimate, target) pair at self.rate; 'both': {'stoi', 'estoi'}."""
+        d = self.stoi_batch([est], [target], extended)[0]
+        return d if extended == "both" else next(iter(d.values()))
+
+    def stoi_batch(self, ests, targets, extended=False, resident=False, deferred=False):
+        """{'stoi'} / {'estoi'} / both for lists of pairs, with evaluation_batch's input rules (metrics.py:89-90 truncation; float32
+        or float64 signals - resampled to 10 kHz in float64 either way).  A target object passed for several pairs is analysed once.
+        deferred: as evaluation_batch."""
+        which = self._stoi_which(extended)
+        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
+        tgts, index, seen = [], [], {}
+        for e, t in pairs:
+            key = (id(t), int(t.shape[0]))
+            if key not in seen:
+                seen[key] = len(tgts)
+                tgts.append(t)
+            index.append(seen[key])
+        pending = B.stoi(tgts, [e for e, _ in pairs], index, self.rate, which, self._device, deferred=True)
+        finish = lambda: self._stoi_dicts(pending(), which)      # noqa: E731
+        return finish if deferred else finish()
+
+    def stoi_multi(self, ests_by_key, targets, extended=False, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  Each target is resampled, masked and transformed once for its K estimates."""
+        which = self._stoi_which(extended)
+        K, n = len(ests_by_key), len(targets)
+        pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for k in range(K)] for i in range(n)]
+        same_len = all(len({pairs[i][k][1].shape[0] for k in range(K)}) == 1 for i in range(n))
+        if not same_len:                      # truncation cut a target differently per key: one target copy per length
+            flat = self.stoi_batch([pairs[i][k][0] for i in range(n) for k in range(K)],
+                                   [pairs[i][k][1] for i in range(n) for k in range(K)], extended, True, deferred=True)
+            finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
+            return finish if deferred else finish()
+        tgts = [pairs[i][0][1] if K else targets[i] for i in range(n)]
+        pending = B.stoi(tgts, [pairs[i][k][0] for i in range(n) for k in range(K)], np.repeat(np.arange(n), K), self.rate, which,
+                         self._device, deferred=True)
+
+        def finish():
+            rows = self._stoi_dicts(pending(), which)
+            return [rows[i * K:(i + 1) * K] for i in range(n)]
+        return finish if deferred else finish()
+
     # ---- reductions on [B, C, T, F] tensors (est first)
     @staticmethod
     def _images(x):
