@@ -282,6 +282,28 @@ int ssr_stoi(const double* tgt, const int64_t* tgt_off, const int32_t* tgt_len, 
  * lo / hi: HOST int32 [15]. */
 int ssr_stoi_band_edges(int32_t* lo, int32_t* hi);
 
+/* Waveform metrics (not in the reference), float64 throughout, EPS = DBL_EPSILON, x = target, y = estimate:
+ *   SSR_WAVE_SNR      10 log10((Σx² + EPS) / (Σ(x - y)² + EPS))
+ *   SSR_WAVE_SI_SDR   zero-mean SI-SDR (Le Roux et al. 2019): x0 = x - mean(x), y0 = y - mean(y), alpha = (Σx0 y0 + EPS) / (Σx0² + EPS),
+ *                     s = alpha x0, 10 log10((Σs² + EPS) / (Σ(s - y0)² + EPS)), the residual formed sample by sample
+ *   SSR_WAVE_SEG_SNR  Loizou's comp_snr.m: L = (3 fs + 50) / 100, R = L / 4, M = max(0, (n - L) / R) frames [jR, jR + L) under the
+ *                     window 0.5 (1 - cos(2 pi (i + 1) / (L + 1))), seg_j = 10 log10(S_j / (N_j + EPS) + EPS) clamped to [-10, 35],
+ *                     the mean over j; M = 0: NaN
+ * n = 0: NaN for all three.  Pair e scores estimate e (est + est_off[e], as long as its target) against target tgt_index[e];
+ * pairs next to each other that name one target read its tiles once.  tgt / est: float32, or float64 where tgt_f64 / est_f64;
+ * tgt_off / est_off: DEVICE int64 sample offsets.  tgt_len and tgt_index are HOST int32 arrays: validated before anything is
+ * enqueued (which a non-empty subset of 7, fs > 0, lengths >= 0, indices in [0, n_tgt)) and copied into the workspace on `stream`
+ * (from page-locked memory the copy is asynchronous: keep the values until the stream has reached it).  n_est = 0: nothing is
+ * enqueued.  out: double [n_est][popcount(which)], columns in bit order.  Deterministic: fixed-order sums, no atomics; a pair
+ * gives the same bits alone and in any batch.  workspace: ssr_wave_metrics_workspace_bytes (0 for invalid arguments). */
+#define SSR_WAVE_SNR 1
+#define SSR_WAVE_SI_SDR 2
+#define SSR_WAVE_SEG_SNR 4
+size_t ssr_wave_metrics_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int fs, int which);
+int ssr_wave_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt,
+                     const void* est, int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est,
+                     int fs, int which, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* A6.  The tensor helpers of ssr_eval/utils.py as stand-alone calls (inside ssr_pair_metrics /
  * ssr_spectrogram_metrics they are fused; these back `from ssr_eval.utils import to_log, pow_p_norm, ...`).
  *   ssr_to_log      out = log10(x + 1e-12)                       utils.py:43-44

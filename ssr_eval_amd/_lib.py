@@ -18,6 +18,7 @@ PAD_REFLECT, PAD_CONSTANT = 0, 1
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE = -1, -2, -3, -4      # include/ssr_hip.h
 MAX_BANDS = 8                                                                   # SSR_MAX_BANDS
 STOI, ESTOI, STOI_BOTH = 1, 2, 3                                                # SSR_STOI, SSR_ESTOI, SSR_STOI_BOTH
+WAVE_SNR, WAVE_SI_SDR, WAVE_SEG_SNR = 1, 2, 4                                   # SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -56,6 +57,8 @@ SIGNATURES = {
     "ssr_stoi_workspace_bytes": (_sz, [_vp, _i, _vp, _i]),
     "ssr_stoi": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "ssr_stoi_band_edges": (_i, [_vp, _vp]),
+    "ssr_wave_metrics_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i]),
+    "ssr_wave_metrics": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ssr_to_log": (_i, [_vp, _i64, _vp, _vp]),
     "ssr_from_log": (_i, [_vp, _i64, _vp, _vp]),
     "ssr_energy_sums": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),

@@ -772,6 +772,57 @@ def stoi(tgt_list, est_list, tgt_index, fs, which=_lib.STOI, device=None, deferr
         return Pending(out) if deferred else out.cpu().numpy()
 
 
+# ---- waveform metrics: SNR, SI-SDR, segmental SNR ----------------------------------------------------------------------------
+def _ragged_where_they_lie(arrays, dev, dtype):
+    """(data, off, lens_host) of a list of signals for a kernel that only reads them: device views of one buffer are taken where
+    they lie in ANY order (from_list(allow_gaps=True) reads them in address order; the offsets are put back in list order), other
+    inputs are packed as from_list packs them.  off: device int64 [n], item i at data + off[i]."""
+    n = len(arrays)
+    order = list(range(n))
+    if n > 1 and all(isinstance(a, torch.Tensor) and a.is_cuda for a in arrays):
+        order.sort(key=lambda i: arrays[i].data_ptr())
+    r = Ragged.from_list([arrays[i] for i in order], dev, dtype, allow_gaps=True)
+    if order == list(range(n)):
+        return r.data, r.off, r.lens_host
+    inv = np.argsort(np.asarray(order, np.int64))
+    return r.data, r.off[_h2d(inv, r.device)], r.lens_host[inv]
+
+
+def wave_metrics(tgt_list, est_list, tgt_index, fs, which=7, device=None, deferred=False):
+    """SNR / SI-SDR / segmental SNR of estimate e against target tgt_index[e] (ssr_wave_metrics): waveforms at `fs`
+    (float32 or float64, each estimate as long as its target; a list holding both dtypes is widened to float64) -> [n_est, n_out]
+    float64, columns in bit order of `which` (1 snr, 2 si_sdr, 4 seg_snr).  Device views of one buffer are read where they lie;
+    pairs next to each other that name one target read its tiles once.  deferred: a Pending."""
+    require_gpu()
+    dev = torch.device(device) if device is not None else default_device()
+    n_t, n_e = len(tgt_list), len(est_list)
+    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
+    if idx.shape[0] != n_e:
+        raise ValueError("one target index per estimate")
+    which = int(which)
+    if not 1 <= which <= 7:
+        raise ValueError("which must be a non-empty combination of 1 (snr), 2 (si_sdr) and 4 (seg_snr)")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty((n_e, bin(which).count("1")), dtype=torch.float64, device=dev)
+        if n_e:
+            if idx.min() < 0 or idx.max() >= n_t:
+                raise ValueError("tgt_index out of range")
+            t64, e64 = any(_is_f64(t) for t in tgt_list), any(_is_f64(e) for e in est_list)
+            td, toff, tl = _ragged_where_they_lie(list(tgt_list), dev, torch.float64 if t64 else torch.float32)
+            ed, eoff, el = _ragged_where_they_lie(list(est_list), dev, torch.float64 if e64 else torch.float32)
+            if not np.array_equal(el, tl[idx]):
+                raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+            lens = tl.astype(np.int32)
+            ws_bytes = int(lib.ssr_wave_metrics_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p),
+                                                                n_e, int(fs), which))
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            keep = [_host_i32(a, dev) for a in (lens, idx)]
+            _lib.check(lib.ssr_wave_metrics(_vp(td), int(t64), _vp(toff), keep[0][1], n_t, _vp(ed), int(e64), _vp(eoff), keep[1][1],
+                                            n_e, int(fs), which, _vp(out), _vp(ws), ws_bytes, _stream()))
+        return Pending(out) if deferred else out.cpu().numpy()
+
+
 def stft(plan, wavs, kind="mag", torch_style_pad=False):
     """STFT of a list of waveforms.  kind "mag": list of [T, F] tensors; "complex": (re list, im list).
     torch_style_pad: refuse signals not longer than n_fft//2 the way torch's reflect padding does (torchlibrosa);

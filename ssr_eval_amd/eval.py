@@ -29,6 +29,8 @@ from .utils import dict_mean, write_json
 _METRIC_KEYS = ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi", "estoi")
 # SSR_Eval_Helper(stoi=...) -> AudioMetrics.stoi_* `extended`
 _STOI_OPTIONS = {"stoi": False, "estoi": True, "both": "both"}
+# the waveform metrics of SSR_Eval_Helper(waveform=...), after every key of _METRIC_KEYS (only present in runs that ask for them)
+_WAVEFORM_KEYS = ("snr", "si_sdr", "seg_snr")
 
 
 def key_cutoff_hz(key):
@@ -105,11 +107,18 @@ class SSR_Eval_Helper:
     def __init__(self, testee, input_sr, output_sr, evaluation_sr=44100, test_name="test",
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
-                 precision="f64", device=None, download=False, lsd_split=None, stoi=None):
+                 precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
-        (AudioMetrics.stoi_multi / stoi_batch at evaluation_sr)."""
+        (AudioMetrics.stoi_multi / stoi_batch at evaluation_sr).
+        waveform (not in the reference): None = off; True = every key also gets snr / si_sdr / seg_snr; one of those names or a
+        tuple of them = those (AudioMetrics.waveform_multi / waveform_batch at evaluation_sr)."""
+        names = (waveform,) if isinstance(waveform, str) else waveform
+        if not (waveform is None or waveform is True or (isinstance(names, tuple) and names
+                                                         and all(isinstance(m, str) and m in _WAVEFORM_KEYS for m in names))):
+            raise ValueError("waveform must be None, True, one of %s or a tuple of them" % (_WAVEFORM_KEYS,))
+        self.waveform = waveform
         if stoi is not None and not (isinstance(stoi, str) and stoi in _STOI_OPTIONS):
             raise ValueError("stoi must be None, 'stoi', 'estoi' or 'both'")
         self.stoi = stoi
@@ -435,6 +444,15 @@ class SSR_Eval_Helper:
                 flat_stoi = lambda: [st_[k] for st_ in st() for k in range(K)]     # noqa: E731
             else:
                 flat_stoi = self.audio_metrics.stoi_batch(all_proc, all_tgt, ext, resident=True, deferred=True)
+        if all_proc and self.waveform is not None:
+            # the waveform metrics, queued behind the intelligibility in the same deferred batch; the multi path reads each target
+            # tile once for its K estimates
+            wh = "all" if self.waveform is True else self.waveform
+            if multi:
+                wv = self.audio_metrics.waveform_multi(by_key, [all_tgt[i * K] for i in range(len(items))], wh, resident=True, deferred=True)
+                flat_wave = lambda: [w_[k] for w_ in wv() for k in range(K)]     # noqa: E731
+            else:
+                flat_wave = self.audio_metrics.waveform_batch(all_proc, all_tgt, wh, resident=True, deferred=True)
         self._last_processed = None
         keep = list(zip(owner, all_keys, all_proc)) if self.save_processed_result else None
 
@@ -449,6 +467,9 @@ class SSR_Eval_Helper:
                 if self.stoi is not None:
                     for v, sv in zip(vals, flat_stoi()):
                         v.update(sv)
+                if self.waveform is not None:
+                    for v, wv_ in zip(vals, flat_wave()):
+                        v.update(wv_)
                 for i, k, v, e in zip(owner, all_keys, vals, all_extra):
                     v.update(e)                                 # the testee's extra metrics last, as the reference's update
                     results[i][k] = v
@@ -597,7 +618,8 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        mets = sorted(mets, key=lambda m: (_METRIC_KEYS.index(m) if m in _METRIC_KEYS else 99, m))
+        order_keys = _METRIC_KEYS + _WAVEFORM_KEYS
+        mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):
             rows[i] = [r[k][m] for k in keys for m in mets]

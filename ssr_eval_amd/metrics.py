@@ -18,6 +18,7 @@ from . import backend as B
 
 EPS = 1e-12
 _KEYS = ("lsd", "log_sispec", "sispec", "ssim")
+_WAVE_NAMES = ("snr", "si_sdr", "seg_snr")        # SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR: bits 0, 1, 2
 
 
 class AudioMetrics:
@@ -301,6 +302,71 @@ class AudioMetrics:
         def finish():
             rows = self._stoi_dicts(pending(), which)
             return [rows[i * K:(i + 1) * K] for i in range(n)]
+        return finish if deferred else finish()
+
+    # ---- waveform metrics (not in the reference): SNR, SI-SDR, segmental SNR, at self.rate
+    @staticmethod
+    def _wave_which(which):
+        """"all", one of _WAVE_NAMES or a tuple / list of them -> the SSR_WAVE_* bit mask."""
+        names = _WAVE_NAMES if (isinstance(which, str) and which == "all") else ((which,) if isinstance(which, str) else which)
+        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(m, str) and m in _WAVE_NAMES for m in names):
+            raise ValueError("which must be 'all', one of %s or a tuple of them" % (_WAVE_NAMES,))
+        return sum(1 << _WAVE_NAMES.index(m) for m in set(names))
+
+    @staticmethod
+    def _wave_dicts(vals, mask):
+        names = [m for j, m in enumerate(_WAVE_NAMES) if mask & (1 << j)]
+        return [{k: float(v) for k, v in zip(names, row)} for row in vals]
+
+    def waveform(self, est, target, which="all"):
+        """{'snr', 'si_sdr', 'seg_snr'} (or the subset `which` names) of one (estimate, target) pair, in dB."""
+        return self.waveform_batch([est], [target], which)[0]
+
+    def snr(self, est, target):
+        return self.waveform(est, target, "snr")["snr"]
+
+    def si_sdr(self, est, target):
+        return self.waveform(est, target, "si_sdr")["si_sdr"]
+
+    def seg_snr(self, est, target):
+        return self.waveform(est, target, "seg_snr")["seg_snr"]
+
+    def waveform_batch(self, ests, targets, which="all", resident=False, deferred=False):
+        """waveform() for lists of pairs, with stoi_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals, read
+        in their own dtype: one ssr_wave_metrics call per (target dtype, estimate dtype) group).  A target object passed for several
+        pairs is read once for all of them.  deferred: as evaluation_batch."""
+        mask = self._wave_which(which)
+        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
+        groups = {}
+        for i, (e, t) in enumerate(pairs):
+            groups.setdefault((bool(B._is_f64(t)), bool(B._is_f64(e))), []).append(i)
+        pending = []
+        for idx in groups.values():
+            tgts, index, seen = [], [], {}
+            for i in idx:
+                t = pairs[i][1]
+                key = (id(t), int(t.shape[0]))
+                if key not in seen:
+                    seen[key] = len(tgts)
+                    tgts.append(t)
+                index.append(seen[key])
+            pending.append((idx, B.wave_metrics(tgts, [pairs[i][0] for i in idx], index, self.rate, mask, self._device, deferred=True)))
+
+        def finish():
+            out = [None] * len(pairs)
+            for idx, p in pending:
+                for i, d in zip(idx, self._wave_dicts(p(), mask)):
+                    out[i] = d
+            return out
+        return finish if deferred else finish()
+
+    def waveform_multi(self, ests_by_key, targets, which="all", resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  The K pairs of a target sit next to each other in one call: each tile of the target is read once for all of them."""
+        K, n = len(ests_by_key), len(targets)
+        flat = self.waveform_batch([ests_by_key[k][i] for i in range(n) for k in range(K)], [targets[i] for i in range(n) for _ in range(K)],
+                                   which, resident, deferred=True)
+        finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
         return finish if deferred else finish()
 
     # ---- reductions on [B, C, T, F] tensors (est first)
