@@ -304,6 +304,45 @@ int ssr_wave_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const
                      const void* est, int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est,
                      int fs, int which, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mel-spectrogram distances (not in the reference) on magnitude images S [T][n_bins] (power 1):
+ *   M[t][m] = Σ_f S[t][f] fb[f][m]           (float64 sums; E / G: the estimate's / target's mel image)
+ *   SSR_MEL_LSD  mel_lsd = mean_t sqrt( mean_m log10( G² / (E + 1e-12)² + 1e-12 )² )        (AudioMetrics.lsd on mel magnitudes)
+ *   SSR_MEL_L1   mel_l1  = mean_{t,m} | ln⁺E - ln⁺G |,  ln⁺x = ln(max(x, 1e-5))
+ *   SSR_MEL_MCD  mcd     = mean_t (10 / ln 10) sqrt( 2 Σ_{d=1..n_cep} c_d² ),  c = orthonormal DCT-II over m of ln⁺E - ln⁺G
+ *                (MFCC-based, no DTW: not an SPTK mel-cepstrum MCD)
+ * fb: HOST float32 [n_bins][n_mels], row-major (torchaudio's melscale_fbanks layout).  It is validated before anything is
+ * enqueued - finite, >= 0, every filter one contiguous run of non-zero weights and none all zero, 1 <= n_mels <= SSR_MEL_MAX,
+ * 1 <= n_cep < n_mels - then copied into the workspace on `stream` (from page-locked memory asynchronously: keep it unchanged
+ * until the stream has reached it) and packed there as per-filter bin ranges.  which: a non-empty subset of the three bits;
+ * out: double [n_items][n_keys][3] = mel_lsd, mel_l1, mcd, NaN where not asked for.  Deterministic: runs of 16 frames per
+ * image, fixed-order sums, no atomics - a pair gives the same bits alone and in any batch. */
+#define SSR_MEL_LSD 1
+#define SSR_MEL_L1 2
+#define SSR_MEL_MCD 4
+#define SSR_MEL_MAX 256
+/* Projection only (AudioMetrics.mel_spectrogram): image v is the rows [frame_off[v], + n_rows[v]) of sp [*, n_bins]; its mel
+ * rows go to out + (frame_off[v] + r) * n_mels, float32.  workspace: ssr_spectrogram_mel_workspace_bytes(n_bins, n_mels). */
+size_t ssr_spectrogram_mel_workspace_bytes(int n_bins, int n_mels);
+int ssr_spectrogram_mel(const float* sp, const int64_t* frame_off, const int32_t* n_rows, int n_images, int max_rows, int n_bins,
+                        const float* fb, int n_mels, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* Image level, the descriptors of ssr_spectrogram_lsd_bands (n_keys = 1): out double [n_images][3]. */
+size_t ssr_spectrogram_mel_metrics_workspace_bytes(int n_images, int max_rows, int n_bins, int n_mels, int n_cep);
+int ssr_spectrogram_mel_metrics(const float* est_sp, const int64_t* est_frame_off, const float* tgt_sp, const int64_t* tgt_frame_off,
+                                const int32_t* n_rows, int n_images, int max_rows, int n_bins, const float* fb, int n_mels, int n_cep,
+                                int which, double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* Waveform level, the descriptors of ssr_pair_lsd_bands: the K + 1 magnitude images of ssr_pair_lsd_bands (n_bins = the plan's),
+ * then the reduction.  ssr_pair_mel_metrics_workspace_bytes serves both entry points. */
+size_t ssr_pair_mel_metrics_workspace_bytes(const ssr_plan* plan, int n_items, int n_keys, int max_len, int64_t total_rows, int n_mels,
+                                            int n_cep);
+int ssr_pair_mel_metrics(const ssr_plan* plan, const float* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
+                         const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
+                         const float* fb, int n_mels, int n_cep, int which, double* out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int ssr_pair_mel_metrics_est64(const ssr_plan* plan, const double* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
+                               const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
+                               const float* fb, int n_mels, int n_cep, int which, double* out, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 /* A6.  The tensor helpers of ssr_eval/utils.py as stand-alone calls (inside ssr_pair_metrics /
  * ssr_spectrogram_metrics they are fused; these back `from ssr_eval.utils import to_log, pow_p_norm, ...`).
  *   ssr_to_log      out = log10(x + 1e-12)                       utils.py:43-44

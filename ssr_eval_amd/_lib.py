@@ -19,6 +19,7 @@ ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE = -1, -2, -3, -4      #
 MAX_BANDS = 8                                                                   # SSR_MAX_BANDS
 STOI, ESTOI, STOI_BOTH = 1, 2, 3                                                # SSR_STOI, SSR_ESTOI, SSR_STOI_BOTH
 WAVE_SNR, WAVE_SI_SDR, WAVE_SEG_SNR = 1, 2, 4                                   # SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR
+MEL_LSD, MEL_L1, MEL_MCD, MEL_MAX = 1, 2, 4, 256                                # SSR_MEL_LSD, SSR_MEL_L1, SSR_MEL_MCD, SSR_MEL_MAX
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -54,6 +55,13 @@ SIGNATURES = {
     "ssr_pair_lsd_bands_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i64, _i]),
     "ssr_pair_lsd_bands": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
     "ssr_pair_lsd_bands_est64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
+    "ssr_spectrogram_mel_workspace_bytes": (_sz, [_i, _i]),
+    "ssr_spectrogram_mel": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "ssr_spectrogram_mel_metrics_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "ssr_spectrogram_mel_metrics": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssr_pair_mel_metrics_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i64, _i, _i]),
+    "ssr_pair_mel_metrics": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssr_pair_mel_metrics_est64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ssr_stoi_workspace_bytes": (_sz, [_vp, _i, _vp, _i]),
     "ssr_stoi": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "ssr_stoi_band_edges": (_i, [_vp, _vp]),

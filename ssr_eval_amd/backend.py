@@ -658,6 +658,106 @@ def pair_lsd_bands(plan, est_lists, tgt_list, edges, deferred=False, keys_per_ch
 STOI_FS = 10000                  # pystoi's analysis rate
 
 
+# ---- mel-spectrogram distances ----------------------------------------------------------------------------------------------
+# Bytes of magnitude images one ssr_pair_mel_metrics call may hold (as LSD_BANDS_WS_BYTES: the keys run in chunks that fit).
+MEL_WS_BYTES = 1 << 30
+
+
+def _fb_arg(fb):
+    """fb: a float32 [n_bins, n_mels] torch-CPU tensor the caller keeps unchanged (AudioMetrics caches it page-locked: the library's
+    copy out of it is then asynchronous) -> (n_bins, n_mels, pointer)."""
+    if not isinstance(fb, torch.Tensor) or fb.dtype != torch.float32 or fb.dim() != 2 or fb.is_cuda or not fb.is_contiguous():
+        raise ValueError("the filterbank must be a contiguous float32 [n_bins, n_mels] host tensor")
+    return int(fb.shape[0]), int(fb.shape[1]), C.c_void_p(fb.data_ptr())
+
+
+def spectrogram_mel(sp, fb):
+    """sp: [N, T, F] magnitude images (float32, one device), fb: [F, n_mels] host float32 -> [N, T, n_mels] float32 device tensor
+    (ssr_spectrogram_mel)."""
+    require_gpu()
+    lib = _lib.load()
+    dev = sp.device if isinstance(sp, torch.Tensor) and sp.is_cuda else default_device()
+    nb, nm, fp = _fb_arg(fb)
+    with torch.cuda.device(dev):
+        x = _dev_f32(sp, dev).contiguous()
+        if x.dim() != 3 or int(x.shape[2]) != nb:
+            raise ValueError("expected [N, T, %d] images, got %s" % (nb, tuple(x.shape)))
+        N, T, F = (int(v) for v in x.shape)
+        out = torch.empty((N, T, nm), dtype=torch.float32, device=dev)
+        if N and T:
+            off = torch.arange(N, device=dev, dtype=torch.int64) * T
+            rows = torch.full((N,), T, device=dev, dtype=torch.int32)
+            ws_bytes = int(lib.ssr_spectrogram_mel_workspace_bytes(F, nm))
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            _lib.check(lib.ssr_spectrogram_mel(_vp(x), _vp(off), _vp(rows), N, T, F, fp, nm, _vp(out), _vp(ws), ws_bytes, _stream()))
+        return out
+
+
+def spectrogram_mel_metrics(est, target, fb, n_cep, which):
+    """est / target: [N, T, F] magnitude images -> [N, 3] float64 device tensor (mel_lsd, mel_l1, mcd; NaN where `which` does not
+    ask; ssr_spectrogram_mel_metrics)."""
+    require_gpu()
+    lib = _lib.load()
+    dev = est.device if isinstance(est, torch.Tensor) and est.is_cuda else default_device()
+    nb, nm, fp = _fb_arg(fb)
+    with torch.cuda.device(dev):
+        x = _dev_f32(est, dev).contiguous()
+        y = _dev_f32(target, dev).contiguous()
+        if x.dim() != 3 or x.shape != y.shape or int(x.shape[2]) != nb:
+            raise ValueError("expected two [N, T, %d] images, got %s and %s" % (nb, tuple(x.shape), tuple(y.shape)))
+        N, T, F = (int(v) for v in x.shape)
+        out = torch.empty((N, 3), dtype=torch.float64, device=dev)
+        if N:
+            if T < 1:
+                raise ValueError("empty spectrogram")
+            off = torch.arange(N, device=dev, dtype=torch.int64) * T
+            rows = torch.full((N,), T, device=dev, dtype=torch.int32)
+            ws_bytes = int(lib.ssr_spectrogram_mel_metrics_workspace_bytes(N, T, F, nm, int(n_cep)))
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            _lib.check(lib.ssr_spectrogram_mel_metrics(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, fp, nm, int(n_cep), int(which),
+                                                       _vp(out), _vp(ws), ws_bytes, _stream()))
+        return out
+
+
+def pair_mel_metrics(plan, est_lists, tgt_list, fb, n_cep, which, deferred=False, keys_per_chunk=None):
+    """Mel distances of K estimates per target: est_lists = K lists of n waveforms (all float32 or all float64, each as long as its
+    target), tgt_list = n float32 targets, fb: [plan.n_bins, n_mels] host float32 -> [n, K, 3] float64 (deferred: a Pending).
+    The keys run in chunks as in pair_lsd_bands (keys_per_chunk, or as many as fit in MEL_WS_BYTES)."""
+    K, n = len(est_lists), len(tgt_list)
+    nb, nm, fp = _fb_arg(fb)
+    if nb != plan.n_bins:
+        raise ValueError("the filterbank has %d bins, the transform %d" % (nb, plan.n_bins))
+    with torch.cuda.device(plan.device):
+        tgt = Ragged.from_list(tgt_list, plan.device, allow_gaps=True)
+        if any(_is_f64(t) for t in tgt_list):
+            raise ValueError("mel distances take float32 targets (float64 estimates are kept float64)")
+        _check_nonempty(tgt.lens_host)
+        rows = _Rows(plan, tgt.lens_host, tgt.device)
+        out = torch.empty((n, K, 3), dtype=torch.float64, device=tgt.device)
+        if n and K:
+            if keys_per_chunk is None:
+                plane = rows.total * ((plan.n_bins + 3) & ~3) * 4
+                keys_per_chunk = max(1, MEL_WS_BYTES // max(plane, 1) - 1)
+                if keys_per_chunk > 6:
+                    keys_per_chunk -= keys_per_chunk % 6
+            kc = max(1, min(int(keys_per_chunk), K))
+            lib = plan.lib
+            ws_bytes = int(lib.ssr_pair_mel_metrics_workspace_bytes(plan.handle, n, kc, tgt.max_len, rows.total, nm, int(n_cep)))
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=tgt.device)
+            for k0 in range(0, K, kc):
+                k1 = min(K, k0 + kc)
+                est = Ragged.from_list_keep64([w for key in est_lists[k0:k1] for w in key], plan.device, allow_gaps=True)
+                if not np.array_equal(est.lens_host, np.tile(tgt.lens_host, k1 - k0)):
+                    raise ValueError("every estimate must be as long as its target (truncate to min_len first)")
+                o = out if k1 - k0 == K else torch.empty((n, k1 - k0, 3), dtype=torch.float64, device=tgt.device)
+                fn = lib.ssr_pair_mel_metrics_est64 if est.data.dtype == torch.float64 else lib.ssr_pair_mel_metrics
+                _lib.check(fn(plan.handle, _vp(est.data), _vp(est.off), _vp(tgt.data), _vp(tgt.off), _vp(tgt.len), _vp(rows.off), n,
+                              k1 - k0, tgt.max_len, rows.total, fp, nm, int(n_cep), int(which), _vp(o), _vp(ws), ws_bytes, _stream()))
+                if o is not out:
+                    out[:, k0:k1] = o
+        return Pending(out) if deferred else out.cpu().numpy()
+
+
 def octave_taps(p, q):
     """The filter of pystoi.utils.resample_oct for resample_poly(x, p, q) (p / q reduced): Octave's resample() design - a
     Kaiser-windowed ideal low-pass at 1 / (2 max(p, q)) with 60 dB rejection - normalised to unit sum.  float64."""

@@ -2,6 +2,7 @@
 // ssr_pair_lsd_bands, ssr_pair_lsd_bands_est64).
 #include "ssr_host.h"
 #include "ssr_lsd_bands.h"
+#include "ssr_pair_images.h"
 
 template <int KG, int NB, bool VEC> __global__ __launch_bounds__(64) void k_lsd_bands(SsrLsdBandsParams p) {
   ssr_lsd_bands_body<KG, NB, VEC>(p, blockIdx.x % p.n_chunks, blockIdx.x / p.n_chunks);
@@ -108,22 +109,13 @@ extern "C" int ssr_spectrogram_lsd_bands(const float* est_sp, const int64_t* est
 
 // ----------------------------------------------------------------------------------------------------
 // waveform level: K + 1 magnitude images per item (the pair transform of ssr_pair_metrics_multi), then the reduction
-struct BandWs { size_t plane, off_est, off_tgt, off_scratch, off_part, off_edges, off_rows, total; int units_per_chunk, n_chunks, kg; };
+struct BandWs { SsrPairImages im; size_t off_part, off_edges, off_rows, total; int kg; };
 static BandWs band_ws(const ssr_plan* pl, int n_items, int n_keys, int max_len, int64_t total_rows, int n_bands, bool in64) {
   BandWs w;
+  w.im = ssr_pair_images_layout(pl, n_items, n_keys, max_len, total_rows, in64);
   const int max_T = (int)ssr_num_frames(pl, max_len);
-  w.units_per_chunk = ssr_pair_units_per_chunk(pl, max_T, n_items, in64);
-  w.n_chunks = ssr_ceil_div(max_T, w.units_per_chunk);
-  const int S = ssr_pair_interleave(pl, in64);
-  w.n_chunks = ssr_ceil_div(w.n_chunks, S) * S;
   w.kg = band_kg(n_keys);
-  w.plane = ssr_align256((size_t)total_rows * ssr_mag_pitch(pl->n_bins) * sizeof(float));
-  size_t o = 0;
-  w.off_est = o; o += (size_t)n_keys * w.plane;
-  w.off_tgt = o; o += w.plane;
-  // the block engines store both images of a pair (they take no null out_b): keys 1 .. K-1 paired with the target put the target's
-  // rows here, so that the image key 0 wrote stays the one every key is reduced against
-  w.off_scratch = o; o += (n_keys > 1 && !ssr_multi_fast_path(pl, in64)) ? w.plane : 0;
+  size_t o = w.im.end;
   w.off_part = o; o += part_bytes((int64_t)n_keys * n_items, max_T, n_bands, (int64_t)n_items * (n_keys / w.kg));
   w.off_edges = o; o += edges_bytes((int64_t)n_keys * n_items, n_bands);
   w.off_rows = o; o += ssr_align256((size_t)n_items * sizeof(int32_t));
@@ -136,19 +128,6 @@ extern "C" size_t ssr_pair_lsd_bands_workspace_bytes(const ssr_plan* pl, int n_i
   const size_t a = band_ws(pl, n_items, n_keys, max_len, total_rows, n_bands, false).total;
   const size_t b = band_ws(pl, n_items, n_keys, max_len, total_rows, n_bands, true).total;
   return a > b ? a : b;
-}
-
-template <typename T>
-static int band_stft(const ssr_plan* pl, const float* a, const double* a64, const int64_t* a_off, const float* b, const double* b64,
-                     const int64_t* b_off, const int32_t* len, const int64_t* frame_off, int n_items, float* out_a, float* out_b,
-                     const BandWs& w, hipStream_t s) {
-  SsrStftParams<T> p{};
-  p.a = a; p.a64 = a64; p.b = b; p.b64 = b64; p.a_off = a_off; p.b_off = b_off; p.len = len; p.frame_off = frame_off;
-  p.mode = SSR_MODE_PAIR; p.out_kind = SSR_OUT_MAG; p.metric_mask = 0;     // images only, no metric epilogue
-  p.n_fft = pl->n_fft; p.hop = pl->hop; p.n_bins = pl->n_bins;
-  p.units_per_chunk = w.units_per_chunk; p.n_chunks = w.n_chunks; p.interleave = ssr_pair_interleave(pl, a64 != nullptr);
-  p.out_a = out_a; p.out_b = out_b; p.out_pitch = ssr_mag_pitch(pl->n_bins); p.part = nullptr;
-  return ssr_launch_stft<T>(pl, p, n_items * w.n_chunks, s);
 }
 
 static int pair_lsd_bands_impl(const ssr_plan* pl, const float* est, const double* est64, const int64_t* est_off, const float* tgt,
@@ -176,27 +155,9 @@ static int pair_lsd_bands_impl(const ssr_plan* pl, const float* est, const doubl
   HIP_TRY(hipMemcpyAsync(e_dev, edges, (size_t)n_items * n_keys * (n_bands + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_lsd_rows_from_len, dim3(ssr_ceil_div(n_items, 256)), dim3(256), 0, s, len, n_items, pl->n_fft, pl->hop, rows);
   HIP_TRY(hipGetLastError());
-  auto plane_of = [&](int k) { return (float*)(ws + w.off_est + (size_t)k * w.plane); };
-  float* tgt_plane = (float*)(ws + w.off_tgt);
-  auto stft = [&](const float* a, const double* a64, const int64_t* a_off, const float* b, const double* b64, const int64_t* b_off,
-                  float* oa, float* ob) {
-    return pl->precision == SSR_F64 ? band_stft<double>(pl, a, a64, a_off, b, b64, b_off, len, frame_off, n_items, oa, ob, w, s)
-                                    : band_stft<float>(pl, a, a64, a_off, b, b64, b_off, len, frame_off, n_items, oa, ob, w, s);
-  };
-  // key 0 with the target: both images (the target's written once, here)
-  int rc = stft(est, est64, est_off, tgt, nullptr, tgt_off, plane_of(0), tgt_plane);
-  if (rc) return rc;
-  int k = 1;
-  const bool fast = ssr_multi_fast_path(pl, e64);
-  if (fast)                                  // two estimates per complex transform (wave engines)
-    for (; k + 1 < n_keys; k += 2)
-      if ((rc = stft(est, est64, est_off + (size_t)k * n_items, est, est64, est_off + (size_t)(k + 1) * n_items, plane_of(k), plane_of(k + 1))))
-        return rc;
-  // the rest with the target, whose image is not rewritten: the wave engines skip a null out_b, the block engines get the scratch plane
-  float* tgt_sink = fast ? nullptr : (float*)(ws + w.off_scratch);
-  for (; k < n_keys; ++k)
-    if ((rc = stft(est, est64, est_off + (size_t)k * n_items, tgt, nullptr, tgt_off, plane_of(k), tgt_sink))) return rc;
-  SsrLsdBandsParams p{plane_of(0), tgt_plane, frame_off, frame_off, rows, e_dev, (int64_t)(w.plane / sizeof(float)), pl->n_bins,
+  if (int rc = ssr_pair_images(pl, est, est64, est_off, tgt, tgt_off, len, frame_off, n_items, n_keys, w.im, ws, s)) return rc;
+  SsrLsdBandsParams p{(float*)(ws + w.im.off_est), (float*)(ws + w.im.off_tgt), frame_off, frame_off, rows, e_dev,
+                      (int64_t)(w.im.plane / sizeof(float)), pl->n_bins,
                       ssr_mag_pitch(pl->n_bins), n_bands, n_items, 0, 0, (double*)(ws + w.off_part)};
   return launch_bands(p, n_keys, w.kg, max_T, rows, out, s);
 }

@@ -31,6 +31,8 @@ _METRIC_KEYS = ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi
 _STOI_OPTIONS = {"stoi": False, "estoi": True, "both": "both"}
 # the waveform metrics of SSR_Eval_Helper(waveform=...), after every key of _METRIC_KEYS (only present in runs that ask for them)
 _WAVEFORM_KEYS = ("snr", "si_sdr", "seg_snr")
+# the mel-spectrogram distances of SSR_Eval_Helper(mel=...), after the waveform metrics (only present in runs that ask for them)
+_MEL_KEYS = ("mel_lsd", "mel_l1", "mcd")
 
 
 def key_cutoff_hz(key):
@@ -107,13 +109,18 @@ class SSR_Eval_Helper:
     def __init__(self, testee, input_sr, output_sr, evaluation_sr=44100, test_name="test",
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
-                 precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None):
+                 precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
         (AudioMetrics.stoi_multi / stoi_batch at evaluation_sr).
         waveform (not in the reference): None = off; True = every key also gets snr / si_sdr / seg_snr; one of those names or a
-        tuple of them = those (AudioMetrics.waveform_multi / waveform_batch at evaluation_sr)."""
+        tuple of them = those (AudioMetrics.waveform_multi / waveform_batch at evaluation_sr).
+        mel (not in the reference): None = off; True = every key also gets mel_lsd / mel_l1 / mcd (AudioMetrics.mel_distance_multi /
+        mel_distance_batch at evaluation_sr, NVSR's 128-band HTK front end); a dict = front-end options (n_mels, f_min, f_max, norm,
+        mel_scale, n_cep) and optionally `which` ("all", one of those names or a tuple of them)."""
+        if not (mel is None or mel is True or isinstance(mel, dict)):
+            raise ValueError("mel must be None, True or a dict of mel options")
         names = (waveform,) if isinstance(waveform, str) else waveform
         if not (waveform is None or waveform is True or (isinstance(names, tuple) and names
                                                          and all(isinstance(m, str) and m in _WAVEFORM_KEYS for m in names))):
@@ -138,6 +145,11 @@ class SSR_Eval_Helper:
         self.evaluationset_sr = evaluation_sr
         assert self.evaluationset_sr <= 48000, "Our evaluation set only support up to 48 kHz target sampling rate"
         self.audio_metrics = AudioMetrics(self.evaluationset_sr, precision=precision, device=device)
+        self.mel = mel
+        if isinstance(mel, dict):                      # every option checked here, not at the first batch
+            opts = {k: v for k, v in mel.items() if k != "which"}
+            self.audio_metrics._mel_which(mel.get("which", "all"))
+            self.audio_metrics._mel_fb(**opts)
         self.unexpected_symbol_test_folder = "_.*#()_+=!@$%^&~"
         self._device = device
         if test_data_root is not None and not os.path.exists(test_data_root):
@@ -453,6 +465,16 @@ class SSR_Eval_Helper:
                 flat_wave = lambda: [w_[k] for w_ in wv() for k in range(K)]     # noqa: E731
             else:
                 flat_wave = self.audio_metrics.waveform_batch(all_proc, all_tgt, wh, resident=True, deferred=True)
+        if all_proc and self.mel is not None:
+            # the mel distances, queued behind the waveform metrics in the same deferred batch
+            opts = {} if self.mel is True else {k: v for k, v in self.mel.items() if k != "which"}
+            mw = "all" if self.mel is True else self.mel.get("which", "all")
+            if multi:
+                mv = self.audio_metrics.mel_distance_multi(by_key, [all_tgt[i * K] for i in range(len(items))], mw, resident=True,
+                                                           deferred=True, **opts)
+                flat_mel = lambda: [m_[k] for m_ in mv() for k in range(K)]     # noqa: E731
+            else:
+                flat_mel = self.audio_metrics.mel_distance_batch(all_proc, all_tgt, mw, resident=True, deferred=True, **opts)
         self._last_processed = None
         keep = list(zip(owner, all_keys, all_proc)) if self.save_processed_result else None
 
@@ -470,6 +492,9 @@ class SSR_Eval_Helper:
                 if self.waveform is not None:
                     for v, wv_ in zip(vals, flat_wave()):
                         v.update(wv_)
+                if self.mel is not None:
+                    for v, mv_ in zip(vals, flat_mel()):
+                        v.update(mv_)
                 for i, k, v, e in zip(owner, all_keys, vals, all_extra):
                     v.update(e)                                 # the testee's extra metrics last, as the reference's update
                     results[i][k] = v
@@ -618,7 +643,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = _METRIC_KEYS + _WAVEFORM_KEYS
+        order_keys = _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

@@ -15,10 +15,12 @@ import numpy as np
 import torch
 
 from . import backend as B
+from . import mel as M
 
 EPS = 1e-12
 _KEYS = ("lsd", "log_sispec", "sispec", "ssim")
 _WAVE_NAMES = ("snr", "si_sdr", "seg_snr")        # SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR: bits 0, 1, 2
+_MEL_NAMES = ("mel_lsd", "mel_l1", "mcd")         # SSR_MEL_LSD, SSR_MEL_L1, SSR_MEL_MCD: bits 0, 1, 2
 
 
 class AudioMetrics:
@@ -368,6 +370,123 @@ class AudioMetrics:
                                    which, resident, deferred=True)
         finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
         return finish if deferred else finish()
+
+    # ---- mel-spectrogram distances (not in the reference): on this rate's magnitude image, NVSR's 128-band HTK mel
+    # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
+    _fb_cache = {}
+
+    def mel_options(self, **mel):
+        """-> (n_mels, f_min, f_max, norm, mel_scale, n_cep) with the defaults filled in; ValueError for an unknown name or value."""
+        bad = sorted(set(mel) - set(M.MEL_OPTIONS))
+        if bad:
+            raise ValueError("unknown mel option(s) %s (known: %s)" % (bad, M.MEL_OPTIONS))
+        return M.check_options(self.rate, **mel)
+
+    def mel_filterbank(self, **mel):
+        """(float32 [F, n_mels] host tensor, n_cep): a copy of the filterbank at this rate's F = n_fft // 2 + 1."""
+        fb, n_cep = self._mel_fb(**mel)
+        return fb.clone(), n_cep
+
+    def _mel_fb(self, **mel):
+        """mel_filterbank's table itself: page-locked, cached per (rate, F, options, device) and never written again (the library
+        copies it asynchronously).  Internal: callers outside this class get copies."""
+        n_mels, f_min, f_max, norm, scale, n_cep = self.mel_options(**mel)
+        F = self.n_fft // 2 + 1
+        key = (self.rate, F, n_mels, f_min, f_max, norm, scale, str(self._device))
+        fb = AudioMetrics._fb_cache.get(key)
+        if fb is None:
+            fb = M.mel_filterbank(F, f_min, f_max, n_mels, self.rate, norm, scale).contiguous()
+            if torch.cuda.is_available():
+                fb = fb.pin_memory()
+            AudioMetrics._fb_cache[key] = fb
+        return fb, n_cep
+
+    @staticmethod
+    def _mel_which(which):
+        """"all", one of _MEL_NAMES or a tuple / list of them -> the SSR_MEL_* bit mask."""
+        names = _MEL_NAMES if (isinstance(which, str) and which == "all") else ((which,) if isinstance(which, str) else which)
+        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(m, str) and m in _MEL_NAMES for m in names):
+            raise ValueError("which must be 'all', one of %s or a tuple of them" % (_MEL_NAMES,))
+        return sum(1 << _MEL_NAMES.index(m) for m in set(names))
+
+    @staticmethod
+    def _mel_dict(row, mask):
+        return {m: float(row[j]) for j, m in enumerate(_MEL_NAMES) if mask & (1 << j)}
+
+    def mel_spectrogram(self, wav, keep_on_device=False, **mel):
+        """[n] waveform -> mel spectrogram [1, 1, T, n_mels] float32: wav_to_spectrogram's magnitude image times the filterbank."""
+        fb, _ = self._mel_fb(**mel)
+        sp = self.wav_to_spectrogram(wav, keep_on_device=True)
+        out = B.spectrogram_mel(sp[0], fb)[None]
+        return out if keep_on_device else out.cpu()
+
+    def mel_distance(self, est, target, which="all", **mel):
+        """{'mel_lsd', 'mel_l1', 'mcd'} (or the subset `which` names) of one (estimate, target) pair."""
+        return self.mel_distance_batch([est], [target], which, **mel)[0]
+
+    def mel_distance_batch(self, ests, targets, which="all", resident=False, deferred=False, **mel):
+        """mel_distance for lists of pairs, with evaluation_batch's input rules (metrics.py:89-90 truncation, float64 estimates kept
+        float64; float32 targets): one ssr_pair_mel_metrics call per estimate dtype.  deferred: as evaluation_batch."""
+        mask = self._mel_which(which)
+        fb, n_cep = self._mel_fb(**mel)
+        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
+        groups = {}
+        for i, (e, _) in enumerate(pairs):
+            groups.setdefault(bool(B._is_f64(e)), []).append(i)
+        pending = [(idx, B.pair_mel_metrics(self._plan(), [[pairs[i][0] for i in idx]], [pairs[i][1] for i in idx], fb, n_cep, mask,
+                                            deferred=True)) for idx in groups.values()]
+
+        def finish():
+            out = [None] * len(pairs)
+            for idx, p in pending:
+                vals = p()
+                for r, i in enumerate(idx):
+                    out[i] = self._mel_dict(vals[r, 0], mask)
+            return out
+        return finish if deferred else finish()
+
+    def mel_distance_multi(self, ests_by_key, targets, which="all", resident=False, deferred=False, keys_per_chunk=None, **mel):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  Keys of one estimate dtype share one multi-key launch sequence (each target transformed once per chunk of keys);
+        lengths that differ between keys, or a key with both dtypes, send the pairs through mel_distance_batch."""
+        mask = self._mel_which(which)
+        fb, n_cep = self._mel_fb(**mel)
+        K, n = len(ests_by_key), len(targets)
+        pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for i in range(n)] for k in range(K)]
+        same_len = all(len({pairs[k][i][0].shape[0] for k in range(K)}) == 1 for i in range(n))
+        kinds = [{bool(B._is_f64(pairs[k][i][0])) for i in range(n)} for k in range(K)]
+        if n == 0 or not same_len or any(len(kd) != 1 for kd in kinds):
+            flat = self.mel_distance_batch([pairs[k][i][0] for i in range(n) for k in range(K)],
+                                           [pairs[k][i][1] for i in range(n) for k in range(K)], which, True, deferred=True, **mel)
+            finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
+            return finish if deferred else finish()
+        tgts = [pairs[0][i][1] for i in range(n)]
+        groups = {}
+        for k in range(K):
+            groups.setdefault(next(iter(kinds[k])), []).append(k)
+        pending = [(keys, B.pair_mel_metrics(self._plan(), [[pairs[k][i][0] for i in range(n)] for k in keys], tgts, fb, n_cep, mask,
+                                             deferred=True, keys_per_chunk=keys_per_chunk)) for keys in groups.values()]
+
+        def finish():
+            out = [[None] * K for _ in range(n)]
+            for keys, p in pending:
+                vals = p()
+                for i in range(n):
+                    for j, k in enumerate(keys):
+                        out[i][k] = self._mel_dict(vals[i, j], mask)
+            return out
+        return finish if deferred else finish()
+
+    def mel_distance_spectrogram(self, est_sp, tgt_sp, which="all", **mel):
+        """[B, C, T, F] magnitude tensors x2 (F = n_fft // 2 + 1) -> {name: [B, C] float64 tensor} for the names `which` asks for."""
+        if est_sp.shape != tgt_sp.shape or est_sp.dim() != 4:
+            raise ValueError("expected two [B, C, T, F] tensors of one shape, got %s and %s" % (tuple(est_sp.shape), tuple(tgt_sp.shape)))
+        mask = self._mel_which(which)
+        fb, n_cep = self._mel_fb(**mel)
+        Bn, Cn, T, F = (int(v) for v in est_sp.shape)
+        v = B.spectrogram_mel_metrics(est_sp.reshape(Bn * Cn, T, F), tgt_sp.reshape(Bn * Cn, T, F), fb, n_cep, mask)
+        v = v.to(est_sp.device).reshape(Bn, Cn, 3)
+        return {m: v[..., j] for j, m in enumerate(_MEL_NAMES) if mask & (1 << j)}
 
     # ---- reductions on [B, C, T, F] tensors (est first)
     @staticmethod
