@@ -343,6 +343,41 @@ int ssr_pair_mel_metrics_est64(const ssr_plan* plan, const double* est, const in
                                const float* fb, int n_mels, int n_cep, int which, double* out, void* workspace, size_t workspace_bytes,
                                void* stream);
 
+/* Objective quality measures (not in the reference): Loizou's comp_llr.m, comp_cep.m, comp_wss.m and comp_fwseg.m
+ * (Speech Enhancement: Theory and Practice, §11.1-11.2), restated.  Both signals widened to float64 with EPS added to every
+ * sample; frames of §10: L = (3 fs + 50) / 100, R = L / 4, M = max(0, (n - L) / R) frames [jR, jR + L) under the window
+ * 0.5 (1 - cos(2 pi (i + 1) / (L + 1))).
+ *   SSR_QUAL_LLR    per frame min(2, ln(a_y' R_x a_y / a_x' R_x a_x)), order-P LPC by Levinson-Durbin on the autocorrelation
+ *                   (P = 10 below 10 kHz, else 16; lpc_order overrides); mean of the round(0.95 M) smallest frame values
+ *   SSR_QUAL_CEP    per frame min(10, (10 sqrt 2 / ln 10) ||c_x - c_y||), c the LPC cepstrum c_1 .. c_P; the same trimmed mean
+ *   SSR_QUAL_WSS    Klatt's weighted spectral slope on Loizou's 25 critical bands (50 Hz .. about 3.9 kHz at EVERY rate: a
+ *                   measure of the band below 4 kHz), N = 2^ceil(log2(2 L))-point spectra; the same trimmed mean
+ *   SSR_QUAL_FWSEG  frequency-weighted segmental SNR on the same bands (weights B_x^0.2, frame values clamped to [-10, 35]);
+ *                   the plain mean
+ * Guards (the frame value stays finite): Levinson stops at an order whose prediction error is not finite and positive; a
+ * non-finite or non-positive LLR ratio gives 2; fwSNRseg skips bands with B_x = 0 (none left: -10).  M = 0 or n = 0: NaN.
+ * Pair e scores estimate e (est + est_off[e], as long as its target) against target tgt_index[e]; pairs next to each other
+ * that name one target analyse its frames once.  tgt / est: float32, or float64 where tgt_f64 / est_f64; tgt_off / est_off:
+ * DEVICE int64 sample offsets.  tgt_len and tgt_index are HOST int32 arrays: validated before anything is enqueued (which a
+ * non-empty subset of 15, fs in [8000, 48000], lpc_order 0 = default or in [1, 32], lengths >= 0, indices in [0, n_tgt)) and
+ * copied into the workspace on `stream` (from page-locked memory the copy is asynchronous: keep the values until the stream has
+ * reached it).  n_est = 0: nothing is enqueued.  out: double [n_est][popcount(which)], columns in bit order.  No LPC kernel
+ * runs without SSR_QUAL_LLR / SSR_QUAL_CEP, no transform without SSR_QUAL_WSS / SSR_QUAL_FWSEG.  Deterministic: fixed-order
+ * float sums, no floating-point atomics; a pair gives the same bits alone and in any batch.  workspace:
+ * ssr_quality_metrics_workspace_bytes (0 for invalid arguments).
+ * ssr_quality_bands: the transform size at fs, the band centres and widths (Hz, 25 each) and the float64 filters [25][n_fft / 2]
+ * (filters_len doubles at least); any output may be null. */
+#define SSR_QUAL_LLR 1
+#define SSR_QUAL_CEP 2
+#define SSR_QUAL_WSS 4
+#define SSR_QUAL_FWSEG 8
+size_t ssr_quality_metrics_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int fs,
+                                           int lpc_order, int which);
+int ssr_quality_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt,
+                        const void* est, int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est,
+                        int fs, int lpc_order, int which, double* out, void* workspace, size_t workspace_bytes, void* stream);
+int ssr_quality_bands(int fs, int32_t* n_fft, double* cent, double* bw, double* filters, size_t filters_len);
+
 /* A6.  The tensor helpers of ssr_eval/utils.py as stand-alone calls (inside ssr_pair_metrics /
  * ssr_spectrogram_metrics they are fused; these back `from ssr_eval.utils import to_log, pow_p_norm, ...`).
  *   ssr_to_log      out = log10(x + 1e-12)                       utils.py:43-44

@@ -20,6 +20,7 @@ MAX_BANDS = 8                                                                   
 STOI, ESTOI, STOI_BOTH = 1, 2, 3                                                # SSR_STOI, SSR_ESTOI, SSR_STOI_BOTH
 WAVE_SNR, WAVE_SI_SDR, WAVE_SEG_SNR = 1, 2, 4                                   # SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR
 MEL_LSD, MEL_L1, MEL_MCD, MEL_MAX = 1, 2, 4, 256                                # SSR_MEL_LSD, SSR_MEL_L1, SSR_MEL_MCD, SSR_MEL_MAX
+QUAL_LLR, QUAL_CEP, QUAL_WSS, QUAL_FWSEG = 1, 2, 4, 8                           # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -67,6 +68,9 @@ SIGNATURES = {
     "ssr_stoi_band_edges": (_i, [_vp, _vp]),
     "ssr_wave_metrics_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i]),
     "ssr_wave_metrics": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssr_quality_metrics_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i, _i]),
+    "ssr_quality_metrics": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssr_quality_bands": (_i, [_i, _vp, _vp, _vp, _vp, _sz]),
     "ssr_to_log": (_i, [_vp, _i64, _vp, _vp]),
     "ssr_from_log": (_i, [_vp, _i64, _vp, _vp]),
     "ssr_energy_sums": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),

@@ -923,6 +923,59 @@ def wave_metrics(tgt_list, est_list, tgt_index, fs, which=7, device=None, deferr
         return Pending(out) if deferred else out.cpu().numpy()
 
 
+# ---- objective quality measures: LLR, LPC cepstral distance, WSS, fwSNRseg ------------------------------------------------------
+def quality_bands(fs):
+    """(n_fft, cent [25], bw [25], filters [25, n_fft // 2]) float64: the critical bands and filters ssr_quality_metrics uses at fs."""
+    lib = _lib.load()
+    n = C.c_int32(0)
+    _lib.check(lib.ssr_quality_bands(int(fs), C.byref(n), None, None, None, 0))
+    cent, bw = np.zeros(25), np.zeros(25)
+    filt = np.zeros((25, n.value // 2))
+    _lib.check(lib.ssr_quality_bands(int(fs), C.byref(n), cent.ctypes.data_as(C.c_void_p), bw.ctypes.data_as(C.c_void_p),
+                                     filt.ctypes.data_as(C.c_void_p), filt.size))
+    return n.value, cent, bw, filt
+
+
+def quality_metrics(tgt_list, est_list, tgt_index, fs, which=15, lpc_order=0, device=None, deferred=False):
+    """LLR / cepstral distance / WSS / fwSNRseg of estimate e against target tgt_index[e] (ssr_quality_metrics):
+    waveforms at `fs` (float32 or float64, each estimate as long as its target; a list holding both dtypes is widened to float64)
+    -> [n_est, n_out] float64, columns in bit order of `which` (1 llr, 2 cep_dist, 4 wss, 8 fwseg_snr).  lpc_order 0: 10 below
+    10 kHz, else 16.  Device views of one buffer are read where they lie; pairs next to each other that name one target analyse
+    its frames once.  deferred: a Pending."""
+    require_gpu()
+    dev = torch.device(device) if device is not None else default_device()
+    n_t, n_e = len(tgt_list), len(est_list)
+    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
+    if idx.shape[0] != n_e:
+        raise ValueError("one target index per estimate")
+    which, lpc_order = int(which), int(lpc_order)
+    if not 1 <= which <= 15:
+        raise ValueError("which must be a non-empty combination of 1 (llr), 2 (cep_dist), 4 (wss) and 8 (fwseg_snr)")
+    if not 0 <= lpc_order <= 32:
+        raise ValueError("lpc_order must be 0 (default) or in [1, 32]")
+    if not 8000 <= int(fs) <= 48000:
+        raise ValueError("the quality measures need 8000 <= fs <= 48000")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty((n_e, bin(which).count("1")), dtype=torch.float64, device=dev)
+        if n_e:
+            if idx.min() < 0 or idx.max() >= n_t:
+                raise ValueError("tgt_index out of range")
+            t64, e64 = any(_is_f64(t) for t in tgt_list), any(_is_f64(e) for e in est_list)
+            td, toff, tl = _ragged_where_they_lie(list(tgt_list), dev, torch.float64 if t64 else torch.float32)
+            ed, eoff, el = _ragged_where_they_lie(list(est_list), dev, torch.float64 if e64 else torch.float32)
+            if not np.array_equal(el, tl[idx]):
+                raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+            lens = tl.astype(np.int32)
+            ws_bytes = int(lib.ssr_quality_metrics_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p),
+                                                                   n_e, int(fs), lpc_order, which))
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            keep = [_host_i32(a, dev) for a in (lens, idx)]
+            _lib.check(lib.ssr_quality_metrics(_vp(td), int(t64), _vp(toff), keep[0][1], n_t, _vp(ed), int(e64), _vp(eoff), keep[1][1],
+                                               n_e, int(fs), lpc_order, which, _vp(out), _vp(ws), ws_bytes, _stream()))
+        return Pending(out) if deferred else out.cpu().numpy()
+
+
 def stft(plan, wavs, kind="mag", torch_style_pad=False):
     """STFT of a list of waveforms.  kind "mag": list of [T, F] tensors; "complex": (re list, im list).
     torch_style_pad: refuse signals not longer than n_fft//2 the way torch's reflect padding does (torchlibrosa);

@@ -1,0 +1,175 @@
+// libssrhip.so translation unit: LLR, LPC cepstral distance, WSS and fwSNRseg on float32 / float64 signals (ssr_quality.h) and
+// its entry points (ssr_quality_metrics, ssr_quality_metrics_workspace_bytes, ssr_quality_bands).
+#include <map>
+#include <mutex>
+
+#include "ssr_host.h"
+#include "ssr_quality.h"
+
+__global__ __launch_bounds__(SSR_QUAL_NT) void k_qual_geometry(SsrQualParams p) {
+  __shared__ int64_t sums[3 * SSR_QUAL_NT];
+  SsrBlk blk{(int)threadIdx.x};
+  ssr_qual_geometry_body(p, blk, sums);
+}
+
+template <typename TT, typename TE> __global__ __launch_bounds__(64) void k_qual_lpc(SsrQualParams p) {
+  __shared__ SsrQualLpcLds lds;
+  SsrBlk blk{(int)threadIdx.x};
+  ssr_qual_lpc_body<TT, TE>(p, blk, (int64_t)blockIdx.x, lds);
+}
+
+template <typename TT, typename TE, int LOGN> __global__ __launch_bounds__((1 << LOGN) / 8) void k_qual_bands(SsrQualParams p) {
+  __shared__ SsrQualBandLds<LOGN> lds;
+  SsrBlk blk{(int)threadIdx.x};
+  ssr_qual_bands_body<TT, TE, LOGN>(p, blk, (int64_t)blockIdx.x, lds);
+}
+
+__global__ __launch_bounds__(SSR_QUAL_NT) void k_qual_finalize(SsrQualParams p) {
+  __shared__ SsrQualFinLds lds;
+  SsrBlk blk{(int)threadIdx.x};
+  ssr_qual_finalize_body(p, blk, (int)blockIdx.x, lds);
+}
+
+// band filters and twiddles per sample rate: built once on the host, never written again (the workspace copies read them)
+static const SsrQualTables& qual_tables(int fs) {
+  static std::mutex mu;
+  static std::map<int, SsrQualTables> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(fs);
+  if (it == cache.end()) {
+    it = cache.emplace(fs, SsrQualTables{}).first;
+    ssr_qual_tables_host(fs, it->second);
+  }
+  return it->second;
+}
+
+// workspace layout: a deterministic function of the target lengths, the pair -> target map, fs and which
+struct QualWs { size_t off_len, off_idx, off_rs, off_rf, off_pf, off_win, off_tw, off_fw, off_val, total;
+                int n_runs; int64_t run_frames, pair_frames; };
+static QualWs qual_ws(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int fs, int which) {
+  QualWs w{};
+  for (int e = 0; e < n_est; ++e) {
+    const int64_t M = ssr_qual_frames(tgt_len[tgt_index[e]], fs);
+    if (e == 0 || tgt_index[e] != tgt_index[e - 1]) { ++w.n_runs; w.run_frames += M; }
+    w.pair_frames += M;
+  }
+  const bool bands = (which & (SSR_QUAL_WSS | SSR_QUAL_FWSEG)) != 0;
+  const SsrQualTables& t = qual_tables(fs);
+  size_t o = 0;
+  w.off_len = o; o += ssr_align256((size_t)n_tgt * sizeof(int32_t));
+  w.off_idx = o; o += ssr_align256((size_t)n_est * sizeof(int32_t));
+  w.off_rs = o; o += ssr_align256((size_t)(w.n_runs + 1) * sizeof(int32_t));
+  w.off_rf = o; o += ssr_align256((size_t)(w.n_runs + 1) * sizeof(int64_t));
+  w.off_pf = o; o += ssr_align256((size_t)(n_est + 1) * sizeof(int64_t));
+  w.off_win = o; o += ssr_align256((size_t)ssr_qual_frame_len(fs) * sizeof(double));
+  w.off_tw = o; o += bands ? ssr_align256((size_t)t.N * sizeof(cx<double>)) : 0;
+  w.off_fw = o; o += bands ? ssr_align256((t.packed.size() + 1) * sizeof(double)) : 0;
+  w.off_val = o; o += ssr_align256((size_t)w.pair_frames * 4 * sizeof(double));
+  w.total = o;
+  return w;
+}
+
+// host-side validation: nothing is queued unless every argument is usable
+static int check_qual_args(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int fs, int lpc_order, int which) {
+  if (which < 1 || which > 15)
+    return ssr_fail(SSR_ERR_INVALID_ARG, "which must be a non-empty combination of SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG");
+  if (fs < SSR_QUAL_FS_MIN || fs > SSR_QUAL_FS_MAX) return ssr_fail(SSR_ERR_INVALID_ARG, "fs must be in [8000, 48000]");
+  if (lpc_order < 0 || lpc_order > SSR_QUAL_PMAX) return ssr_fail(SSR_ERR_INVALID_ARG, "lpc_order must be 0 (default) or in [1, 32]");
+  if (n_tgt < 0 || n_est < 0) return ssr_fail(SSR_ERR_INVALID_ARG, "n_tgt and n_est must be >= 0");
+  if ((n_tgt > 0 && !tgt_len) || (n_est > 0 && !tgt_index)) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  for (int t = 0; t < n_tgt; ++t)
+    if (tgt_len[t] < 0) return ssr_fail(SSR_ERR_INVALID_ARG, "target lengths must be in [0, 2^31)");
+  for (int e = 0; e < n_est; ++e)
+    if (tgt_index[e] < 0 || tgt_index[e] >= n_tgt) return ssr_fail(SSR_ERR_INVALID_ARG, "tgt_index out of range");
+  return SSR_OK;
+}
+
+extern "C" size_t ssr_quality_metrics_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int fs,
+                                                      int lpc_order, int which) {
+  if (check_qual_args(tgt_len, n_tgt, tgt_index, n_est, fs, lpc_order, which)) return 0;
+  return qual_ws(tgt_len, n_tgt, tgt_index, n_est, fs, which).total;
+}
+
+extern "C" int ssr_quality_bands(int fs, int32_t* n_fft, double* cent, double* bw, double* filters, size_t filters_len) {
+  if (fs < SSR_QUAL_FS_MIN || fs > SSR_QUAL_FS_MAX) return ssr_fail(SSR_ERR_INVALID_ARG, "fs must be in [8000, 48000]");
+  const SsrQualTables& t = qual_tables(fs);
+  if (n_fft) *n_fft = t.N;
+  for (int b = 0; b < SSR_QUAL_BANDS; ++b) {
+    if (cent) cent[b] = SSR_QUAL_CENT[b];
+    if (bw) bw[b] = SSR_QUAL_BW[b];
+  }
+  if (filters) {
+    if (filters_len < t.dense.size()) return ssr_fail(SSR_ERR_INVALID_ARG, "filters must hold 25 * n_fft / 2 doubles");
+    for (size_t i = 0; i < t.dense.size(); ++i) filters[i] = t.dense[i];
+  }
+  return SSR_OK;
+}
+
+template <typename TT, typename TE> static void launch_lpc(const SsrQualParams& p, int64_t grid, hipStream_t s) {
+  hipLaunchKernelGGL((k_qual_lpc<TT, TE>), dim3((unsigned)grid), dim3(64), 0, s, p);
+}
+template <typename TT, typename TE> static void launch_bands(const SsrQualParams& p, int64_t grid, int logn, hipStream_t s) {
+  const dim3 g((unsigned)grid), b((unsigned)((1 << logn) / 8));
+  if (logn == 9) hipLaunchKernelGGL((k_qual_bands<TT, TE, 9>), g, b, 0, s, p);
+  else if (logn == 10) hipLaunchKernelGGL((k_qual_bands<TT, TE, 10>), g, b, 0, s, p);
+  else if (logn == 11) hipLaunchKernelGGL((k_qual_bands<TT, TE, 11>), g, b, 0, s, p);
+  else hipLaunchKernelGGL((k_qual_bands<TT, TE, 12>), g, b, 0, s, p);
+}
+
+extern "C" int ssr_quality_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt,
+                                   const void* est, int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est, int fs,
+                                   int lpc_order, int which, double* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_qual_args(tgt_len, n_tgt, tgt_index, n_est, fs, lpc_order, which)) return rc;
+  if (n_est == 0) return SSR_OK;
+  int64_t samples = 0;
+  for (int t = 0; t < n_tgt; ++t) samples += tgt_len[t];
+  if (!tgt_off || !est_off || !out || (samples > 0 && (!tgt || !est))) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  const QualWs w = qual_ws(tgt_len, n_tgt, tgt_index, n_est, fs, which);
+  if (w.run_frames > 0x7fffffff) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
+  if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
+  const SsrQualTables& t = qual_tables(fs);
+  const bool lpc = (which & (SSR_QUAL_LLR | SSR_QUAL_CEP)) != 0, bands = (which & (SSR_QUAL_WSS | SSR_QUAL_FWSEG)) != 0;
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* len_dev = (int32_t*)(ws + w.off_len);
+  int32_t* idx_dev = (int32_t*)(ws + w.off_idx);
+  // (host arrays: from page-locked memory these copies are asynchronous - the caller keeps them until the stream has passed;
+  // the tables are cached for the life of the process)
+  if (n_tgt) HIP_TRY(hipMemcpyAsync(len_dev, tgt_len, (size_t)n_tgt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(idx_dev, tgt_index, (size_t)n_est * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (bands) {
+    HIP_TRY(hipMemcpyAsync(ws + w.off_tw, t.tw.data(), t.tw.size() * sizeof(cx<double>), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ws + w.off_fw, t.packed.data(), t.packed.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  }
+  SsrQualParams p{};
+  p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = len_dev; p.tgt_index = idx_dev;
+  p.n_tgt = n_tgt; p.n_est = n_est; p.n_runs = w.n_runs; p.which = which; p.fs = fs;
+  p.L = ssr_qual_frame_len(fs); p.R = ssr_qual_hop(fs); p.P = lpc_order ? lpc_order : ssr_qual_default_order(fs); p.N = t.N;
+  p.run_start = (int32_t*)(ws + w.off_rs); p.run_frame = (int64_t*)(ws + w.off_rf);
+  p.pair_frame = (int64_t*)(ws + w.off_pf); p.win = (double*)(ws + w.off_win);
+  p.tw = bands ? (const cx<double>*)(ws + w.off_tw) : nullptr;
+  p.fw = bands ? (const double*)(ws + w.off_fw) : nullptr;
+  for (int b = 0; b < SSR_QUAL_BANDS; ++b) { p.band_lo[b] = t.lo[b]; p.band_hi[b] = t.hi[b]; p.band_off[b] = t.off[b]; }
+  p.val = (double*)(ws + w.off_val); p.n_val = w.pair_frames; p.out = out;
+  hipLaunchKernelGGL(k_qual_geometry, dim3(1), dim3(SSR_QUAL_NT), 0, s, p);
+  HIP_TRY(hipGetLastError());
+  const int kind = (tgt_f64 ? 2 : 0) + (est_f64 ? 1 : 0);
+  if (lpc && w.run_frames > 0) {
+    if (kind == 0) launch_lpc<float, float>(p, w.run_frames, s);
+    else if (kind == 1) launch_lpc<float, double>(p, w.run_frames, s);
+    else if (kind == 2) launch_lpc<double, float>(p, w.run_frames, s);
+    else launch_lpc<double, double>(p, w.run_frames, s);
+    HIP_TRY(hipGetLastError());
+  }
+  if (bands && w.run_frames > 0) {
+    const int logn = ssr_qual_log2_nfft(fs);
+    if (kind == 0) launch_bands<float, float>(p, w.run_frames, logn, s);
+    else if (kind == 1) launch_bands<float, double>(p, w.run_frames, logn, s);
+    else if (kind == 2) launch_bands<double, float>(p, w.run_frames, logn, s);
+    else launch_bands<double, double>(p, w.run_frames, logn, s);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_qual_finalize, dim3((unsigned)n_est), dim3(SSR_QUAL_NT), 0, s, p);
+  HIP_TRY(hipGetLastError());
+  return SSR_OK;
+}

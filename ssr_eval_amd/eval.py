@@ -33,6 +33,8 @@ _STOI_OPTIONS = {"stoi": False, "estoi": True, "both": "both"}
 _WAVEFORM_KEYS = ("snr", "si_sdr", "seg_snr")
 # the mel-spectrogram distances of SSR_Eval_Helper(mel=...), after the waveform metrics (only present in runs that ask for them)
 _MEL_KEYS = ("mel_lsd", "mel_l1", "mcd")
+# the objective quality measures of SSR_Eval_Helper(quality=...), after the mel distances (only present in runs that ask for them)
+_QUALITY_KEYS = ("llr", "cep_dist", "wss", "fwseg_snr")
 
 
 def key_cutoff_hz(key):
@@ -109,7 +111,8 @@ class SSR_Eval_Helper:
     def __init__(self, testee, input_sr, output_sr, evaluation_sr=44100, test_name="test",
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
-                 precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None):
+                 precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
+                 quality=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -118,7 +121,22 @@ class SSR_Eval_Helper:
         tuple of them = those (AudioMetrics.waveform_multi / waveform_batch at evaluation_sr).
         mel (not in the reference): None = off; True = every key also gets mel_lsd / mel_l1 / mcd (AudioMetrics.mel_distance_multi /
         mel_distance_batch at evaluation_sr, NVSR's 128-band HTK front end); a dict = front-end options (n_mels, f_min, f_max, norm,
-        mel_scale, n_cep) and optionally `which` ("all", one of those names or a tuple of them)."""
+        mel_scale, n_cep) and optionally `which` ("all", one of those names or a tuple of them).
+        quality (not in the reference): None = off; True = every key also gets llr / cep_dist / wss / fwseg_snr
+        (AudioMetrics.quality_multi / quality_batch at evaluation_sr; wss and fwseg_snr look at the band below about 3.9 kHz only);
+        one of those names or a tuple of them = those; a dict = `which` ("all", a name or a tuple) and / or `lpc_order`."""
+        if quality is not None and quality is not True:
+            q = quality if isinstance(quality, dict) else {"which": quality}
+            if isinstance(quality, dict) and (not quality or set(quality) - {"which", "lpc_order"}):
+                raise ValueError("a quality dict takes 'which' and / or 'lpc_order'")
+            wq = q.get("which", "all")
+            if not (isinstance(wq, str) or (isinstance(wq, tuple) and wq and all(isinstance(m, str) for m in wq))):
+                raise ValueError("quality must be None, True, one of %s, a tuple of them or a dict" % (_QUALITY_KEYS,))
+            AudioMetrics._quality_which(wq)
+            AudioMetrics._quality_order(q.get("lpc_order"))
+            if evaluation_sr < 8000:
+                raise ValueError("the quality measures need evaluation_sr >= 8000")
+        self.quality = quality
         if not (mel is None or mel is True or isinstance(mel, dict)):
             raise ValueError("mel must be None, True or a dict of mel options")
         names = (waveform,) if isinstance(waveform, str) else waveform
@@ -475,6 +493,17 @@ class SSR_Eval_Helper:
                 flat_mel = lambda: [m_[k] for m_ in mv() for k in range(K)]     # noqa: E731
             else:
                 flat_mel = self.audio_metrics.mel_distance_batch(all_proc, all_tgt, mw, resident=True, deferred=True, **opts)
+        if all_proc and self.quality is not None:
+            # the quality measures, queued behind the mel distances in the same deferred batch; the multi path analyses each
+            # target's frames once for its K estimates
+            q = self.quality if isinstance(self.quality, dict) else {"which": "all" if self.quality is True else self.quality}
+            qw, qo = q.get("which", "all"), q.get("lpc_order")
+            if multi:
+                qv = self.audio_metrics.quality_multi(by_key, [all_tgt[i * K] for i in range(len(items))], qw, qo, resident=True,
+                                                      deferred=True)
+                flat_quality = lambda: [q_[k] for q_ in qv() for k in range(K)]     # noqa: E731
+            else:
+                flat_quality = self.audio_metrics.quality_batch(all_proc, all_tgt, qw, qo, resident=True, deferred=True)
         self._last_processed = None
         keep = list(zip(owner, all_keys, all_proc)) if self.save_processed_result else None
 
@@ -495,6 +524,9 @@ class SSR_Eval_Helper:
                 if self.mel is not None:
                     for v, mv_ in zip(vals, flat_mel()):
                         v.update(mv_)
+                if self.quality is not None:
+                    for v, qv_ in zip(vals, flat_quality()):
+                        v.update(qv_)
                 for i, k, v, e in zip(owner, all_keys, vals, all_extra):
                     v.update(e)                                 # the testee's extra metrics last, as the reference's update
                     results[i][k] = v
@@ -643,7 +675,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS
+        order_keys = _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS + _QUALITY_KEYS
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

@@ -21,6 +21,7 @@ EPS = 1e-12
 _KEYS = ("lsd", "log_sispec", "sispec", "ssim")
 _WAVE_NAMES = ("snr", "si_sdr", "seg_snr")        # SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR: bits 0, 1, 2
 _MEL_NAMES = ("mel_lsd", "mel_l1", "mcd")         # SSR_MEL_LSD, SSR_MEL_L1, SSR_MEL_MCD: bits 0, 1, 2
+_QUALITY_NAMES = ("llr", "cep_dist", "wss", "fwseg_snr")   # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG: bits 0 .. 3
 
 
 class AudioMetrics:
@@ -368,6 +369,88 @@ class AudioMetrics:
         K, n = len(ests_by_key), len(targets)
         flat = self.waveform_batch([ests_by_key[k][i] for i in range(n) for k in range(K)], [targets[i] for i in range(n) for _ in range(K)],
                                    which, resident, deferred=True)
+        finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
+        return finish if deferred else finish()
+
+    # ---- objective quality measures (not in the reference): Loizou's LLR, LPC cepstral distance, WSS and fwSNRseg at
+    # self.rate.  WSS and fwSNRseg look at Loizou's 25 critical bands only, 50 Hz to about 3.9 kHz at every rate: they score the
+    # band a model was given, not the band it restored.
+    @staticmethod
+    def _quality_which(which):
+        """"all", one of _QUALITY_NAMES or a tuple / list of them -> the SSR_QUAL_* bit mask."""
+        names = _QUALITY_NAMES if (isinstance(which, str) and which == "all") else ((which,) if isinstance(which, str) else which)
+        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(m, str) and m in _QUALITY_NAMES for m in names):
+            raise ValueError("which must be 'all', one of %s or a tuple of them" % (_QUALITY_NAMES,))
+        return sum(1 << _QUALITY_NAMES.index(m) for m in set(names))
+
+    @staticmethod
+    def _quality_order(lpc_order):
+        """None (10 below 10 kHz, else 16) or an int in [1, 32] -> the C ABI's lpc_order (0 = default)."""
+        if lpc_order is None:
+            return 0
+        if isinstance(lpc_order, bool) or not isinstance(lpc_order, (int, np.integer)) or not 1 <= int(lpc_order) <= 32:
+            raise ValueError("lpc_order must be None or an integer in [1, 32]")
+        return int(lpc_order)
+
+    @staticmethod
+    def _quality_dicts(vals, mask):
+        names = [m for j, m in enumerate(_QUALITY_NAMES) if mask & (1 << j)]
+        return [{k: float(v) for k, v in zip(names, row)} for row in vals]
+
+    def quality(self, est, target, which="all", lpc_order=None):
+        """{'llr', 'cep_dist', 'wss', 'fwseg_snr'} (or the subset `which` names) of one (estimate, target) pair."""
+        return self.quality_batch([est], [target], which, lpc_order)[0]
+
+    def llr(self, est, target, lpc_order=None):
+        return self.quality(est, target, "llr", lpc_order)["llr"]
+
+    def cep_dist(self, est, target, lpc_order=None):
+        return self.quality(est, target, "cep_dist", lpc_order)["cep_dist"]
+
+    def wss(self, est, target):
+        return self.quality(est, target, "wss")["wss"]
+
+    def fwseg_snr(self, est, target):
+        return self.quality(est, target, "fwseg_snr")["fwseg_snr"]
+
+    def quality_batch(self, ests, targets, which="all", lpc_order=None, resident=False, deferred=False):
+        """quality() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals,
+        read in their own dtype: one ssr_quality_metrics call per (target dtype, estimate dtype) group).  A target object passed for
+        several pairs is analysed once for all of them.  deferred: as evaluation_batch."""
+        mask, order = self._quality_which(which), self._quality_order(lpc_order)
+        if not 8000 <= self.rate <= 48000:
+            raise ValueError("the quality measures need 8000 <= rate <= 48000")
+        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
+        groups = {}
+        for i, (e, t) in enumerate(pairs):
+            groups.setdefault((bool(B._is_f64(t)), bool(B._is_f64(e))), []).append(i)
+        pending = []
+        for idx in groups.values():
+            tgts, index, seen = [], [], {}
+            for i in idx:
+                t = pairs[i][1]
+                key = (id(t), int(t.shape[0]))
+                if key not in seen:
+                    seen[key] = len(tgts)
+                    tgts.append(t)
+                index.append(seen[key])
+            pending.append((idx, B.quality_metrics(tgts, [pairs[i][0] for i in idx], index, self.rate, mask, order, self._device,
+                                                   deferred=True)))
+
+        def finish():
+            out = [None] * len(pairs)
+            for idx, p in pending:
+                for i, d in zip(idx, self._quality_dicts(p(), mask)):
+                    out[i] = d
+            return out
+        return finish if deferred else finish()
+
+    def quality_multi(self, ests_by_key, targets, which="all", lpc_order=None, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  The K pairs of a target sit next to each other in one call: the target's frames are analysed once for all of them."""
+        K, n = len(ests_by_key), len(targets)
+        flat = self.quality_batch([ests_by_key[k][i] for i in range(n) for k in range(K)], [targets[i] for i in range(n) for _ in range(K)],
+                                  which, lpc_order, resident, deferred=True)
         finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
         return finish if deferred else finish()
 
