@@ -378,6 +378,46 @@ int ssr_quality_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, co
                         int fs, int lpc_order, int which, double* out, void* workspace, size_t workspace_bytes, void* stream);
 int ssr_quality_bands(int fs, int32_t* n_fft, double* cent, double* bw, double* filters, size_t filters_len);
 
+/* Pitch metrics (not in the reference): YIN F0 tracking (de Cheveigné & Kawahara, JASA 2002), restated, on 16 kHz
+ * float64 signals (the caller resamples: scipy.signal.resample_poly(x, 16000 / g, fs / g) with ssr_resample_poly_f64).
+ * Frames: hop H = 160, window W = 400; a signal of n > 0 samples has T = n / H + 1 frames (0 for n = 0), frame t covers samples
+ * [t H - W / 2, t H + W / 2) (zeros outside [0, n)).  Lags tau_lo = floor(16000 / fmax) .. tau_hi = ceil(16000 / fmin); the
+ * difference d_t(tau) = Σ_j<W (x[s+j] - x[s+j+tau])^2 in float64, in the direct form, for tau = 1 .. tau_hi;
+ * d'(tau) = tau d(tau) / Σ_k<=tau d(k) (1 where that sum is 0).  tau* = the smallest trough of d' in [tau_lo, tau_hi] below 0.1,
+ * else the smallest tau with the minimum d'; a parabola through d'(tau* - 1 .. tau* + 1) refines it strictly inside the range
+ * (when its denominator is > 0 and |delta| <= 1).  f0 = 16000 / (tau* + delta) (NaN where E_t = 0), aperiodicity d'(tau*),
+ * E_t = Σ_j<W x[s+j]^2; voiced: E_t > 0, E_t >= 1e-4 max_t E_t and aperiodicity < 0.2.
+ * ssr_f0_track: signal i (sig + off[i], len[i] samples) -> its T frames at f0 / aperiodicity / energy / voiced + frame_off[i]
+ * (frame_off: DEVICE int64 [n]).
+ * ssr_f0_metrics: pair e tracks estimate e (est + est_off[e], as long as its target) and target tgt_index[e]; every target
+ * is tracked once, whatever number of estimates name it.  Over the frames voiced in both (B), N_V frames whose voicing differs
+ * and N_G frames of B with |f_y / f_x - 1| > 0.2:
+ *   SSR_PITCH_F0_RMSE  sqrt(mean_B (1200 log2(f_y / f_x))^2), cents (NaN: B empty)
+ *   SSR_PITCH_F0_CORR  Pearson correlation of f_x, f_y over B (NaN: |B| < 2, or every f_x or every f_y of B equal)
+ *   SSR_PITCH_GPE      N_G / |B| (NaN: B empty)
+ *   SSR_PITCH_VDE      N_V / T (NaN: T = 0)
+ *   SSR_PITCH_FFE      (N_V + N_G) / T (NaN: T = 0)
+ * Lengths (len, tgt_len) and tgt_index are HOST int32 arrays: validated before anything is enqueued (which a non-empty subset of
+ * 31, 40 <= fmin < fmax <= 1000 with tau_hi - tau_lo >= 2, lengths in [0, 2^29), indices in [0, n_tgt)) and copied into the
+ * workspace on `stream` (from page-locked memory the copy is asynchronous: keep the values until the stream has reached it).
+ * n = 0 / n_est = 0: nothing is enqueued.  out: double [n_est][popcount(which)], columns in bit order.  Deterministic: fixed-order
+ * float sums, no floating-point atomics; a signal's track and a pair's values are the same bits alone and in any batch.
+ * workspace: the _workspace_bytes queries (0 for invalid arguments). */
+#define SSR_PITCH_F0_RMSE 1
+#define SSR_PITCH_F0_CORR 2
+#define SSR_PITCH_GPE 4
+#define SSR_PITCH_VDE 8
+#define SSR_PITCH_FFE 16
+size_t ssr_f0_track_workspace_bytes(const int32_t* len, int n, double fmin, double fmax);
+int ssr_f0_track(const double* sig, const int64_t* off, const int32_t* len, int n, double fmin, double fmax, double* f0,
+                 double* aperiodicity, double* energy, uint8_t* voiced, const int64_t* frame_off, void* workspace,
+                 size_t workspace_bytes, void* stream);
+size_t ssr_f0_metrics_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, double fmin,
+                                      double fmax, int which);
+int ssr_f0_metrics(const double* tgt, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt, const double* est,
+                   const int64_t* est_off, const int32_t* tgt_index, int n_est, double fmin, double fmax, int which,
+                   double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* A6.  The tensor helpers of ssr_eval/utils.py as stand-alone calls (inside ssr_pair_metrics /
  * ssr_spectrogram_metrics they are fused; these back `from ssr_eval.utils import to_log, pow_p_norm, ...`).
  *   ssr_to_log      out = log10(x + 1e-12)                       utils.py:43-44

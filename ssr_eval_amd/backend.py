@@ -976,6 +976,115 @@ def quality_metrics(tgt_list, est_list, tgt_index, fs, which=15, lpc_order=0, de
         return Pending(out) if deferred else out.cpu().numpy()
 
 
+# ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
+PITCH_FS = 16000                 # the rate every signal is tracked at
+PITCH_HOP = 160
+
+
+def check_pitch_range(fmin, fmax):
+    """(fmin, fmax) as floats, or ValueError: 40 <= fmin < fmax <= 1000 and at least three lags in [floor(16000 / fmax),
+    ceil(16000 / fmin)] (the C ABI's own check)."""
+    fmin, fmax = float(fmin), float(fmax)
+    if not 40.0 <= fmin < fmax <= 1000.0:
+        raise ValueError("fmin / fmax must satisfy 40 <= fmin < fmax <= 1000")
+    if math.ceil(PITCH_FS / fmin) - math.floor(PITCH_FS / fmax) < 2:
+        raise ValueError("fmin / fmax leave fewer than three lags")
+    return fmin, fmax
+
+
+def pitch_frames(n16):
+    """Frames of a 16 kHz signal of n16 samples (10 ms hop, frame t centred on sample 160 t)."""
+    return int(n16) // PITCH_HOP + 1 if int(n16) > 0 else 0
+
+
+def resample_to_pitch_rate(wavs, fs, device=None):
+    """The 16 kHz float64 signals the tracker analyses: [float32 / float64 waveforms at fs] -> Ragged float64, in one
+    ssr_resample_poly_f64 launch with SciPy's default Kaiser design (bit-identical to scipy.signal.resample_poly(x64, 16000 // g,
+    fs // g)); at 16 kHz the signals, widened."""
+    if not 8000 <= int(fs) <= 48000:
+        raise ValueError("the pitch metrics need 8000 <= fs <= 48000")
+    dev = torch.device(device) if device is not None else default_device()
+    with torch.cuda.device(dev):
+        r = wavs if isinstance(wavs, Ragged) else Ragged.from_list(list(wavs), dev, torch.float64)
+        rp = ResamplePlan.get(PITCH_FS, int(fs), dev)
+        if rp.identity:
+            return r
+        out_len = np.array([rp.n_out(n) for n in r.lens_host], dtype=np.int64)
+        out_off = np.concatenate(([0], np.cumsum(out_len)[:-1])).astype(np.int64) if r.n else np.zeros(0, np.int64)
+        out = torch.empty(int(out_len.sum()), dtype=torch.float64, device=dev)
+        out_off_d, out_len_d = _h2d(out_off, dev), _h2d(out_len.astype(np.int32), dev)
+        if r.n and out_len.max() > 0:
+            _lib.check(_lib.load().ssr_resample_poly_f64(_vp(r.data), _vp(r.off), _vp(r.len), _vp(out_off_d), _vp(out_len_d), r.n,
+                                                         int(out_len.max()), rp.up, rp.down, _vp(rp.taps64), int(rp.taps64.numel()),
+                                                         rp.n_pre_remove, _vp(out), _stream()))
+        return Ragged(out, out_off_d, out_len_d, out_len)
+
+
+def f0_track(wavs, fs, fmin=50.0, fmax=500.0, device=None):
+    """YIN F0 tracks (ssr_f0_track) of waveforms at `fs` (float32 or float64; resampled to 16 kHz in one launch) ->
+    one (f0 [T], voiced [T] bool, aperiodicity [T], energy [T]) tuple of float64 / bool ndarrays per signal, 10 ms frames."""
+    require_gpu()
+    fmin, fmax = check_pitch_range(fmin, fmax)
+    dev = torch.device(device) if device is not None else default_device()
+    n = len(wavs)
+    if n == 0:
+        return []
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        r = resample_to_pitch_rate(list(wavs), fs, dev)
+        lens = r.lens_host.astype(np.int32)
+        T = np.array([pitch_frames(m) for m in lens], np.int64)
+        foff = np.concatenate(([0], np.cumsum(T)[:-1])).astype(np.int64)
+        tot = max(int(T.sum()), 1)
+        f0, ap, en = (torch.empty(tot, dtype=torch.float64, device=dev) for _ in range(3))
+        vo = torch.empty(tot, dtype=torch.uint8, device=dev)
+        ws_bytes = int(lib.ssr_f0_track_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n, fmin, fmax))
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        keep = _host_i32(lens, dev)
+        foff_d = _h2d(foff, dev)
+        _lib.check(lib.ssr_f0_track(_vp(r.data), _vp(r.off), keep[1], n, fmin, fmax, _vp(f0), _vp(ap), _vp(en), _vp(vo), _vp(foff_d),
+                                    _vp(ws), ws_bytes, _stream()))
+        f0, ap, en, vo = (t.cpu().numpy() for t in (f0, ap, en, vo))
+    return [(f0[a:a + t], vo[a:a + t].astype(bool), ap[a:a + t], en[a:a + t]) for a, t in zip(foff, T)]
+
+
+def pitch_metrics(tgt_list, est_list, tgt_index, fs, which=31, fmin=50.0, fmax=500.0, device=None, deferred=False):
+    """F0 RMSE / F0 correlation / GPE / VDE / FFE of estimate e against target tgt_index[e] (ssr_f0_metrics): waveforms
+    at `fs` (float32 or float64, each estimate as long as its target) -> [n_est, n_out] float64, columns in bit order of `which`
+    (1 f0_rmse, 2 f0_corr, 4 gpe, 8 vde, 16 ffe).  Targets and estimates are resampled to 16 kHz in one launch; every target is
+    tracked once for all its estimates.  deferred: a Pending."""
+    require_gpu()
+    dev = torch.device(device) if device is not None else default_device()
+    n_t, n_e = len(tgt_list), len(est_list)
+    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
+    if idx.shape[0] != n_e:
+        raise ValueError("one target index per estimate")
+    which = int(which)
+    if not 1 <= which <= 31:
+        raise ValueError("which must be a non-empty combination of 1 (f0_rmse), 2 (f0_corr), 4 (gpe), 8 (vde) and 16 (ffe)")
+    fmin, fmax = check_pitch_range(fmin, fmax)
+    if not 8000 <= int(fs) <= 48000:
+        raise ValueError("the pitch metrics need 8000 <= fs <= 48000")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty((n_e, bin(which).count("1")), dtype=torch.float64, device=dev)
+        if n_e:
+            if idx.min() < 0 or idx.max() >= n_t:
+                raise ValueError("tgt_index out of range")
+            n_in = np.array([int(a.shape[0]) for a in list(tgt_list) + list(est_list)], np.int64)
+            if not np.array_equal(n_in[n_t:], n_in[:n_t][idx]):
+                raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+            r = resample_to_pitch_rate(list(tgt_list) + list(est_list), fs, dev)
+            lens = r.lens_host.astype(np.int32)
+            ws_bytes = int(lib.ssr_f0_metrics_workspace_bytes(lens[:n_t].ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p),
+                                                              n_e, fmin, fmax, which))
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            keep = [_host_i32(a, dev) for a in (lens[:n_t], idx)]
+            _lib.check(lib.ssr_f0_metrics(_vp(r.data), _vp(r.off), keep[0][1], n_t, _vp(r.data), _vp(r.off[n_t:]), keep[1][1], n_e,
+                                          fmin, fmax, which, _vp(out), _vp(ws), ws_bytes, _stream()))
+        return Pending(out) if deferred else out.cpu().numpy()
+
+
 def stft(plan, wavs, kind="mag", torch_style_pad=False):
     """STFT of a list of waveforms.  kind "mag": list of [T, F] tensors; "complex": (re list, im list).
     torch_style_pad: refuse signals not longer than n_fft//2 the way torch's reflect padding does (torchlibrosa);

@@ -35,6 +35,8 @@ _WAVEFORM_KEYS = ("snr", "si_sdr", "seg_snr")
 _MEL_KEYS = ("mel_lsd", "mel_l1", "mcd")
 # the objective quality measures of SSR_Eval_Helper(quality=...), after the mel distances (only present in runs that ask for them)
 _QUALITY_KEYS = ("llr", "cep_dist", "wss", "fwseg_snr")
+# the pitch metrics of SSR_Eval_Helper(pitch=...), after the quality measures (only present in runs that ask for them)
+_PITCH_KEYS = ("f0_rmse", "f0_corr", "gpe", "vde", "ffe")
 
 
 def key_cutoff_hz(key):
@@ -112,7 +114,7 @@ class SSR_Eval_Helper:
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
-                 quality=None):
+                 quality=None, pitch=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -124,7 +126,24 @@ class SSR_Eval_Helper:
         mel_scale, n_cep) and optionally `which` ("all", one of those names or a tuple of them).
         quality (not in the reference): None = off; True = every key also gets llr / cep_dist / wss / fwseg_snr
         (AudioMetrics.quality_multi / quality_batch at evaluation_sr; wss and fwseg_snr look at the band below about 3.9 kHz only);
-        one of those names or a tuple of them = those; a dict = `which` ("all", a name or a tuple) and / or `lpc_order`."""
+        one of those names or a tuple of them = those; a dict = `which` ("all", a name or a tuple) and / or `lpc_order`.
+        pitch (not in the reference): None = off; True = every key also gets f0_rmse / f0_corr / gpe / vde / ffe of the estimate's
+        YIN F0 track against the target's (AudioMetrics.pitch_multi / pitch_batch at evaluation_sr, tracked at 16 kHz); one of those
+        names or a tuple of them = those; a dict = `which` ("all", a name or a tuple) and / or the search range `fmin`, `fmax` (Hz,
+        default 50 and 500)."""
+        if pitch is not None:
+            if pitch is not True:
+                pq = pitch if isinstance(pitch, dict) else {"which": pitch}
+                if isinstance(pitch, dict) and (not pitch or set(pitch) - {"which", "fmin", "fmax"}):
+                    raise ValueError("a pitch dict takes 'which', 'fmin' and / or 'fmax'")
+                wp = pq.get("which", "all")
+                if not (isinstance(wp, str) or (isinstance(wp, tuple) and wp and all(isinstance(m, str) for m in wp))):
+                    raise ValueError("pitch must be None, True, one of %s, a tuple of them or a dict" % (_PITCH_KEYS,))
+                AudioMetrics._pitch_which(wp)
+                AudioMetrics._pitch_range(pq.get("fmin", 50.0), pq.get("fmax", 500.0))
+            if not 8000 <= evaluation_sr <= 48000:
+                raise ValueError("the pitch metrics need 8000 <= evaluation_sr <= 48000")
+        self.pitch = pitch
         if quality is not None and quality is not True:
             q = quality if isinstance(quality, dict) else {"which": quality}
             if isinstance(quality, dict) and (not quality or set(quality) - {"which", "lpc_order"}):
@@ -504,6 +523,17 @@ class SSR_Eval_Helper:
                 flat_quality = lambda: [q_[k] for q_ in qv() for k in range(K)]     # noqa: E731
             else:
                 flat_quality = self.audio_metrics.quality_batch(all_proc, all_tgt, qw, qo, resident=True, deferred=True)
+        if all_proc and self.pitch is not None:
+            # the pitch metrics, queued behind the quality measures in the same deferred batch; the multi path resamples and tracks
+            # each target once for its K estimates
+            pq = self.pitch if isinstance(self.pitch, dict) else {"which": "all" if self.pitch is True else self.pitch}
+            pw, pf = pq.get("which", "all"), (pq.get("fmin", 50.0), pq.get("fmax", 500.0))
+            if multi:
+                pv = self.audio_metrics.pitch_multi(by_key, [all_tgt[i * K] for i in range(len(items))], pw, *pf, resident=True,
+                                                    deferred=True)
+                flat_pitch = lambda: [p_[k] for p_ in pv() for k in range(K)]     # noqa: E731
+            else:
+                flat_pitch = self.audio_metrics.pitch_batch(all_proc, all_tgt, pw, *pf, resident=True, deferred=True)
         self._last_processed = None
         keep = list(zip(owner, all_keys, all_proc)) if self.save_processed_result else None
 
@@ -527,6 +557,9 @@ class SSR_Eval_Helper:
                 if self.quality is not None:
                     for v, qv_ in zip(vals, flat_quality()):
                         v.update(qv_)
+                if self.pitch is not None:
+                    for v, pv_ in zip(vals, flat_pitch()):
+                        v.update(pv_)
                 for i, k, v, e in zip(owner, all_keys, vals, all_extra):
                     v.update(e)                                 # the testee's extra metrics last, as the reference's update
                     results[i][k] = v
@@ -675,7 +708,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS + _QUALITY_KEYS
+        order_keys = _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS + _QUALITY_KEYS + _PITCH_KEYS
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

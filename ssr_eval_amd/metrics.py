@@ -22,6 +22,7 @@ _KEYS = ("lsd", "log_sispec", "sispec", "ssim")
 _WAVE_NAMES = ("snr", "si_sdr", "seg_snr")        # SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR: bits 0, 1, 2
 _MEL_NAMES = ("mel_lsd", "mel_l1", "mcd")         # SSR_MEL_LSD, SSR_MEL_L1, SSR_MEL_MCD: bits 0, 1, 2
 _QUALITY_NAMES = ("llr", "cep_dist", "wss", "fwseg_snr")   # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG: bits 0 .. 3
+_PITCH_NAMES = ("f0_rmse", "f0_corr", "gpe", "vde", "ffe")  # SSR_PITCH_F0_RMSE, _F0_CORR, _GPE, _VDE, _FFE: bits 0 .. 4
 
 
 class AudioMetrics:
@@ -452,6 +453,87 @@ class AudioMetrics:
         flat = self.quality_batch([ests_by_key[k][i] for i in range(n) for k in range(K)], [targets[i] for i in range(n) for _ in range(K)],
                                   which, lpc_order, resident, deferred=True)
         finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
+        return finish if deferred else finish()
+
+    # ---- pitch (not in the reference): YIN F0 tracks on 16 kHz float64 signals, 10 ms frames, and the pair statistics
+    # F0 RMSE (cents), F0 correlation, GPE, VDE and FFE of an estimate's track against its target's
+    @staticmethod
+    def _pitch_which(which):
+        """"all", one of _PITCH_NAMES or a tuple / list of them -> the SSR_PITCH_* bit mask."""
+        names = _PITCH_NAMES if (isinstance(which, str) and which == "all") else ((which,) if isinstance(which, str) else which)
+        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(m, str) and m in _PITCH_NAMES for m in names):
+            raise ValueError("which must be 'all', one of %s or a tuple of them" % (_PITCH_NAMES,))
+        return sum(1 << _PITCH_NAMES.index(m) for m in set(names))
+
+    @staticmethod
+    def _pitch_range(fmin, fmax):
+        """(fmin, fmax) in Hz as floats, or ValueError (40 <= fmin < fmax <= 1000, at least three lags)."""
+        for v in (fmin, fmax):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("fmin and fmax must be numbers (Hz)")
+        return B.check_pitch_range(fmin, fmax)
+
+    def _pitch_rate(self):
+        if not 8000 <= self.rate <= 48000:
+            raise ValueError("the pitch metrics need 8000 <= rate <= 48000")
+
+    @staticmethod
+    def _pitch_dicts(vals, mask):
+        names = [m for j, m in enumerate(_PITCH_NAMES) if mask & (1 << j)]
+        return [{k: float(v) for k, v in zip(names, row)} for row in vals]
+
+    def f0(self, wav, fmin=50.0, fmax=500.0):
+        """YIN F0 track of one waveform at self.rate: {'f0' (Hz, NaN where the frame is digitally silent), 'voiced' (bool),
+        'aperiodicity'}, one value per 10 ms frame of the signal resampled to 16 kHz."""
+        fmin, fmax = self._pitch_range(fmin, fmax)
+        self._pitch_rate()
+        f0, voiced, ap, _ = B.f0_track([wav], self.rate, fmin, fmax, self._device)[0]
+        return {"f0": f0, "voiced": voiced, "aperiodicity": ap}
+
+    def pitch(self, est, target, which="all", fmin=50.0, fmax=500.0):
+        """{'f0_rmse', 'f0_corr', 'gpe', 'vde', 'ffe'} (or the subset `which` names) of one (estimate, target) pair."""
+        return self.pitch_batch([est], [target], which, fmin, fmax)[0]
+
+    def pitch_batch(self, ests, targets, which="all", fmin=50.0, fmax=500.0, resident=False, deferred=False):
+        """pitch() for lists of pairs, with stoi_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals -
+        resampled to 16 kHz in float64 either way).  A target object passed for several pairs is tracked once.  deferred: as
+        evaluation_batch."""
+        mask = self._pitch_which(which)
+        fmin, fmax = self._pitch_range(fmin, fmax)
+        self._pitch_rate()
+        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
+        tgts, index, seen = [], [], {}
+        for e, t in pairs:
+            key = (id(t), int(t.shape[0]))
+            if key not in seen:
+                seen[key] = len(tgts)
+                tgts.append(t)
+            index.append(seen[key])
+        pending = B.pitch_metrics(tgts, [e for e, _ in pairs], index, self.rate, mask, fmin, fmax, self._device, deferred=True)
+        finish = lambda: self._pitch_dicts(pending(), mask)      # noqa: E731
+        return finish if deferred else finish()
+
+    def pitch_multi(self, ests_by_key, targets, which="all", fmin=50.0, fmax=500.0, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  Each target is resampled and tracked once for its K estimates."""
+        mask = self._pitch_which(which)
+        fmin, fmax = self._pitch_range(fmin, fmax)
+        self._pitch_rate()
+        K, n = len(ests_by_key), len(targets)
+        pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for k in range(K)] for i in range(n)]
+        same_len = all(len({pairs[i][k][1].shape[0] for k in range(K)}) == 1 for i in range(n))
+        if not same_len:                      # truncation cut a target differently per key: one target copy per length
+            flat = self.pitch_batch([pairs[i][k][0] for i in range(n) for k in range(K)],
+                                    [pairs[i][k][1] for i in range(n) for k in range(K)], which, fmin, fmax, True, deferred=True)
+            finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
+            return finish if deferred else finish()
+        tgts = [pairs[i][0][1] if K else targets[i] for i in range(n)]
+        pending = B.pitch_metrics(tgts, [pairs[i][k][0] for i in range(n) for k in range(K)], np.repeat(np.arange(n), K), self.rate,
+                                  mask, fmin, fmax, self._device, deferred=True)
+
+        def finish():
+            rows = self._pitch_dicts(pending(), mask)
+            return [rows[i * K:(i + 1) * K] for i in range(n)]
         return finish if deferred else finish()
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
