@@ -65,6 +65,8 @@ template <int CPT> struct SsrSsimRegs {
 // 4-way (CPT = 4) bank conflict on ds_read_b64 (measured: 60 % of the kernel's LDS cycles), so one spare slot
 // is inserted every CPT columns to make the lane stride CPT + 1 (odd).  Odd CPT needs nothing.
 template <int CPT> SSR_DEV int ssr_ssim_slot(int c) { return (CPT % 2 == 0) ? c + c / CPT : c; }
+// the same slot for column CPT tid + d of thread tid (tid >= 0), as ONE lane term plus a constant: a single address register
+template <int CPT> SSR_DEV int ssr_ssim_slot_of(int tid, int d) { return (CPT % 2 == 0) ? (CPT + 1) * tid + (d + d / CPT) : CPT * tid + d; }
 
 // CONTIG (round 3): the four column sums go through ONE array, a quantity at a time (write q, read q, write q + 1 ... - the DS
 // operations of the single wave execute in order), which makes room for a seven-row ring of the y pixels (rows of RW floats:
@@ -139,6 +141,10 @@ template <int CPT, bool CONTIG> SSR_DEV int ssr_ssim_col(int tid, int i) {
   if constexpr (CONTIG) return (i < CPT) ? CPT * tid + i : SSR_SSIM_NT * CPT + tid;
   else return tid + SSR_SSIM_NT * i;
 }
+
+// The row requested ahead of step s is r0 + s + 2 clamped to the image's last row: the request is issued without a condition (a
+// load under a branch makes the compiler wait for it at the join), and the two surplus requests at the end of a tile are never used.
+SSR_DEV int ssr_ssim_row_ahead(int row, int T) { return row < T ? row : T - 1; }
 
 // Row step, split in two so that the loads of the NEXT step are in flight while the current one is consumed:
 // ssr_ssim_row_load issues the loads of the row entering the 7-row window (row_add) and of the row leaving
@@ -227,6 +233,9 @@ SSR_DEV void ssr_ssim_row_apply_contig(SsrSsimRegs<CPT>& R, float* yrow, int tid
     R.cs[i][2] = fma(-dd, dd, fma(-c, c, fma(b, b, fma(a, a, R.cs[i][2]))));
     R.cs[i][3] = fma(-c, dd, fma(a, b, R.cs[i][3]));
     R.ring[SLOT][i] = R.px[SET][0][i];
+    // the ring keeps the float: without this the compiler also keeps the float64 copy `a` of every ring pixel for the conversion it
+    // sees again seven steps later in a straight-line trip - 70 registers for the ring instead of 35
+    ssr_touch(R.ring[SLOT][i]);
   }
 }
 
@@ -279,10 +288,15 @@ SSR_DEV double ssr_ssim_value(double sx, double sy, double sq, double sxy) {
 // sum leaves as its own ds_write_b64.  (tools/ubench/fp64_mix: an exchange written with ds_write_b64 costs a third of the same bytes
 // written with ds_write2_b64; here, where the LDS pipe is ~65 % busy next to the VALU's ~69 %: 0.924 -> 0.908 ms per 1024 pairs, three
 // alternations on one box, the same values - profiles/r05_notes.md section 8.)
+// The loads of the hand-off likewise: the six neighbour sums of a lane sit at ONE address register plus constants
+// (ssr_ssim_slot_of), which the compiler would pair into ds_read2_b64 - measured slower here as well (LDS index pipe 47 % -> 69 % busy
+// with fewer LDS instructions, profiles/ssim_row_loop_notes.md).
 #ifndef SSR_HOST_EMU
 #define SSR_SSIM_ST(arr, idx, val) (*(volatile __attribute__((address_space(3))) double*)(&(arr)[idx]) = (val))
+#define SSR_SSIM_LD(arr, idx) (*(const volatile __attribute__((address_space(3))) double*)(&(arr)[idx]))
 #else
 #define SSR_SSIM_ST(arr, idx, val) ((arr)[idx] = (val))
+#define SSR_SSIM_LD(arr, idx) ((arr)[idx])
 #endif
 template <int CPT, bool CONTIG, typename BLK>
 SSR_BODY void ssr_ssim_body(const SsrSsimParams& p, BLK& blk, int tile, int item, char* lds_base) {
@@ -315,12 +329,17 @@ SSR_BODY void ssr_ssim_body(const SsrSsimParams& p, BLK& blk, int tile, int item
   // r0 + s - 7; from s = 6 on the sums are those of output row r0 + s - 6.  The rows of step s + 2 are requested as soon as
   // step s has consumed its own (two steps in flight: one was not enough to cover the load latency - each wave sat idle
   // ~80 % of its life, and neither fewer LDS bytes nor fewer instructions moved the kernel).
+  // The request carries NO condition: the row is clamped to the image's last one (ssr_ssim_row_ahead), the two surplus requests at
+  // the end of a tile are never consumed.  With the request under `if (s + 2 < n_steps)` and every step under `if (s < n_steps)`
+  // the compiler copied the loaded registers at each join and waited for the loads there: s_waitcnt vmcnt(0) / (1) / (2) in every
+  // step, i.e. a prefetch distance of zero to one instead of two, and ~23 register moves per step
+  // (profiles/ssim_row_loop_notes.md; tests/test_ssim_isa.py keeps the compiled loop honest).
   const int n_steps = (W - 1) + (r1 - r0);
 #define SSR_SSIM_STEP(s_, SET, SLOT)                                                                                         \
   SSR_PHASE(blk, regs, {                                                                                                    \
     ssr_ssim_row_apply<CPT, false, SET, SLOT>(R, tid, (s_) >= W, ncol_in);                                                   \
-    if ((s_) + 2 < n_steps)                                                                                                 \
-      ssr_ssim_row_load<CPT, false, SET>(p, R, tid, x, y, r0 + (s_) + 2, ((s_) + 2 >= W) ? r0 + (s_) + 2 - W : -1, c_in0, ncol_in); \
+    ssr_ssim_row_load<CPT, false, SET>(p, R, tid, x, y, ssr_ssim_row_ahead(r0 + (s_) + 2, T),                               \
+                                       ((s_) + 2 >= W) ? r0 + (s_) + 2 - W : -1, c_in0, ncol_in);                           \
     if ((s_) >= W - 1) {                                                                                                    \
       for (int i = 0; i < VC; ++i) {                                                                                        \
         const int c = ssr_ssim_col<CPT, false>(tid, i);                                                                     \
@@ -372,24 +391,25 @@ SSR_BODY void ssr_ssim_body(const SsrSsimParams& p, BLK& blk, int tile, int item
   if constexpr (CONTIG) {
     // One wave per workgroup and every hand-off inside it: wave-scope phases (no s_waitcnt lgkmcnt(0) at the boundaries).  The
     // column sums cross the lanes one quantity at a time through the single L.col array.
-#define SSR_SSIM_STEP_C(s_, SET, SLOT)                                                                                       \
+#define SSR_SSIM_STEP_C(s_, SET, SLOT, HORIZ)                                                                                     \
     SSR_WPHASE(blk, regs, {                                                                                                  \
       ssr_ssim_row_apply_contig<CPT, SET, SLOT>(R, L.yring + (SLOT) * Lds::RW, tid);                                              \
-      if ((s_) + 2 < n_steps)                                                                                                \
-        ssr_ssim_row_load<CPT, true, SET>(p, R, tid, x, y, r0 + (s_) + 2, -1, c_in0, ncol_in);                               \
+      SSR_SCHED_BARRIER();                                                                                                   \
+      ssr_ssim_row_load<CPT, true, SET>(p, R, tid, x, y, ssr_ssim_row_ahead(r0 + (s_) + 2, T), -1, c_in0, ncol_in);          \
+      SSR_SCHED_BARRIER();   /* the request stays between its step's column sums and hand-off (without the two fences: +1 %) */ \
     });                                                                                                                      \
-    if ((s_) >= W - 1) {                                                                                                     \
+    if (HORIZ) {                                                                                                             \
       SSR_UNROLL for (int q = 0; q < 4; ++q) {                                                                               \
         SSR_WPHASE(blk, regs, {             /* every lane publishes: columns past the strip's end carry finite, unused sums */ \
           /* (a lane's columns are read by its LEFT neighbour only, and only the first six of them) */                      \
-          SSR_UNROLL for (int i = 0; i < (CPT < 6 ? CPT : 6); ++i) SSR_SSIM_ST(L.col, ssr_ssim_slot<CPT>(CPT * tid + i), R.cs[i][q]); \
+          SSR_UNROLL for (int i = 0; i < (CPT < 6 ? CPT : 6); ++i) SSR_SSIM_ST(L.col, ssr_ssim_slot_of<CPT>(tid, i), R.cs[i][q]);     \
           L.col[ssr_ssim_slot<CPT>(NT * CPT + (tid < 7 ? tid : 7))] = R.cs[CPT][q];                                          \
         });                                                                                                                  \
         SSR_WPHASE(blk, regs, {                                                                                              \
           double v[CPT + W - 1];                                                                                             \
           SSR_UNROLL for (int d = 0; d < CPT + W - 1; ++d)                                                                   \
             v[d] = (d < CPT) ? R.cs[d < CPT ? d : 0][q]    /* the thread's own columns: already in its registers */         \
-                             : L.col[ssr_ssim_slot<CPT>(CPT * tid + d)];                                                     \
+                             : SSR_SSIM_LD(L.col, ssr_ssim_slot_of<CPT>(tid, d));                                           \
           /* 7-wide windows in groups of four outputs over ten column sums: the shared core v3..v6, then v1 + v2 and       \
              v7 + v8 (11 additions per group; the eight-column variant shares v5 + v6 and v7 + v8 between its two groups:   \
              20) - the same association for every output whichever variant computes it */                                    \
@@ -424,13 +444,27 @@ SSR_BODY void ssr_ssim_body(const SsrSsimParams& p, BLK& blk, int tile, int item
         });                                                                                                                  \
       }                                                                                                                      \
     }
-    // ring slot = step mod 7, prefetch set = step mod 2: fourteen steps per trip, all indices static
-    for (int s0 = 0; s0 < n_steps; s0 += 14) {
-#define SSR_SSIM_STEP_K(k) if (s0 + (k) < n_steps) { SSR_SSIM_STEP_C(s0 + (k), (k) % 2, (k) % 7) }
+    // ring slot = step mod 7, prefetch set = step mod 2: all indices static.  Steps 0 .. 5 fill the window (n_steps >= 7; no
+    // column-sum hand-off yet); then whole trips of fourteen steps in a loop without a branch inside it - the steady state: every
+    // step waits with vmcnt(7) / (5) / (4), the youngest request (four loads) always stays in flight, 148 VGPRs; then the tile's
+    // last, short trip, which leaves at its first missing step (forward branches to ONE exit: no join on the way, so this copy
+    // keeps its rows in flight as well).  A single loop of fourteen steps with such exits is half the code, but measured 1 %
+    // slower: the compiler routes the exits through the loop latch and the first step of every trip waits vmcnt(0).
+    SSR_SSIM_STEP_C(0, 0, 0, false) SSR_SSIM_STEP_C(1, 1, 1, false) SSR_SSIM_STEP_C(2, 0, 2, false)
+    SSR_SSIM_STEP_C(3, 1, 3, false) SSR_SSIM_STEP_C(4, 0, 4, false) SSR_SSIM_STEP_C(5, 1, 5, false)
+    int s0 = W - 1;
+#define SSR_SSIM_STEP_K(k) SSR_SSIM_STEP_C(s0 + (k), (k) % 2, ((k) + W - 1) % 7, true)
+    for (; s0 + 14 <= n_steps; s0 += 14) {
       SSR_SSIM_STEP_K(0) SSR_SSIM_STEP_K(1) SSR_SSIM_STEP_K(2) SSR_SSIM_STEP_K(3) SSR_SSIM_STEP_K(4) SSR_SSIM_STEP_K(5) SSR_SSIM_STEP_K(6)
       SSR_SSIM_STEP_K(7) SSR_SSIM_STEP_K(8) SSR_SSIM_STEP_K(9) SSR_SSIM_STEP_K(10) SSR_SSIM_STEP_K(11) SSR_SSIM_STEP_K(12) SSR_SSIM_STEP_K(13)
-#undef SSR_SSIM_STEP_K
     }
+#define SSR_SSIM_STEP_T(k) if (s0 + (k) >= n_steps) break; SSR_SSIM_STEP_K(k)
+    do {
+      SSR_SSIM_STEP_T(0) SSR_SSIM_STEP_T(1) SSR_SSIM_STEP_T(2) SSR_SSIM_STEP_T(3) SSR_SSIM_STEP_T(4) SSR_SSIM_STEP_T(5) SSR_SSIM_STEP_T(6)
+      SSR_SSIM_STEP_T(7) SSR_SSIM_STEP_T(8) SSR_SSIM_STEP_T(9) SSR_SSIM_STEP_T(10) SSR_SSIM_STEP_T(11) SSR_SSIM_STEP_T(12)
+    } while (0);
+#undef SSR_SSIM_STEP_T
+#undef SSR_SSIM_STEP_K
 #undef SSR_SSIM_STEP_C
   } else {
     for (int s0 = 0; s0 < n_steps; s0 += 2) {

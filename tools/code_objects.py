@@ -80,22 +80,38 @@ def _notes(elf):
                 yield desc
 
 
-def kernels(path, target="gfx950"):
-    """[{name, vgpr, agpr, sgpr, scratch, lds, vgpr_spill, sgpr_spill, max_threads}] for every kernel of the library."""
+def _code_objects(path, target):
+    """Yield (ELF bytes, its amdhsa.kernels metadata list) for every `target` code object of the library."""
     import msgpack
     blob = open(path, "rb").read()
     fat = b"".join(blob[o:o + s] for (n, t, o, s) in _elf_sections(blob) if n == ".hip_fatbin")
-    out = []
     for triple, code in _bundles(fat):
         if target not in triple or code[:4] != b"\x7fELF":
             continue
         for desc in _notes(code):
-            md = msgpack.unpackb(desc, raw=False, strict_map_key=False)
-            for k in md.get("amdhsa.kernels", []):
-                out.append({"name": k.get(".name", ""), "vgpr": k.get(".vgpr_count", 0), "agpr": k.get(".agpr_count", 0),
-                            "sgpr": k.get(".sgpr_count", 0), "scratch": k.get(".private_segment_fixed_size", 0),
-                            "lds": k.get(".group_segment_fixed_size", 0), "vgpr_spill": k.get(".vgpr_spill_count", 0),
-                            "sgpr_spill": k.get(".sgpr_spill_count", 0), "max_threads": k.get(".max_flat_workgroup_size", 0)})
+            yield code, msgpack.unpackb(desc, raw=False, strict_map_key=False).get("amdhsa.kernels", [])
+
+
+def kernel_elf(path, demangled, target="gfx950"):
+    """(mangled name, raw ELF bytes of the code object that holds it) for the kernel whose demangled name contains `demangled`
+    (e.g. "k_ssim<4, true>") - what a disassembler needs; None when the library has no such kernel."""
+    for code, ks in _code_objects(path, target):
+        names = [k.get(".name", "") for k in ks]
+        for name, d in zip(names, demangle(names)):
+            if demangled in d:
+                return name, code
+    return None
+
+
+def kernels(path, target="gfx950"):
+    """[{name, vgpr, agpr, sgpr, scratch, lds, vgpr_spill, sgpr_spill, max_threads}] for every kernel of the library."""
+    out = []
+    for _code, ks in _code_objects(path, target):
+        for k in ks:
+            out.append({"name": k.get(".name", ""), "vgpr": k.get(".vgpr_count", 0), "agpr": k.get(".agpr_count", 0),
+                        "sgpr": k.get(".sgpr_count", 0), "scratch": k.get(".private_segment_fixed_size", 0),
+                        "lds": k.get(".group_segment_fixed_size", 0), "vgpr_spill": k.get(".vgpr_spill_count", 0),
+                        "sgpr_spill": k.get(".sgpr_spill_count", 0), "max_threads": k.get(".max_flat_workgroup_size", 0)})
     return out
 
 
