@@ -36,6 +36,27 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _device_index(dev):
+    """The index of a torch device (the current device's where it names none)."""
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _workspace(nbytes, dev):
+    """The scratch buffer of one library call (never zero-sized: the library takes a non-null pointer)."""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def _offsets(lens):
+    """Exclusive prefix sums (int64): where each item of a batch packed back to back starts."""
+    lens = np.asarray(lens, dtype=np.int64)
+    return np.cumsum(lens) - lens
+
+
+def _uniform_images(N, T, dev):
+    """(offsets int64 [N], lengths int32 [N]) of N items of T rows (or samples) each, built on the device."""
+    return torch.arange(N, device=dev, dtype=torch.int64) * T, torch.full((N,), T, device=dev, dtype=torch.int32)
+
+
 def num_frames(n, n_fft, hop):
     """T of a centred STFT (bit-exact integer)."""
     return 1 + (int(n) + 2 * (n_fft // 2) - n_fft) // hop
@@ -181,7 +202,7 @@ _plans_ex = {}
 def get_plan_ex(n_fft, hop, window_name, window, center, pad_mode, device=None):
     """The cached PlanEx of (n_fft, hop, window name, center, pad_mode, device); `window` = the float64 array of that name."""
     dev = torch.device(device) if device is not None else default_device()
-    key = (int(n_fft), int(hop), window_name, bool(center), pad_mode, dev.index if dev.index is not None else torch.cuda.current_device())
+    key = (int(n_fft), int(hop), window_name, bool(center), pad_mode, _device_index(dev))
     with _plans_lock:
         p = _plans_ex.get(key)
         if p is None:
@@ -193,7 +214,7 @@ def get_plan_ex(n_fft, hop, window_name, window, center, pad_mode, device=None):
 def get_plan(n_fft, hop, precision="f64", device=None, lowpass_engine="segments"):
     """The cached plan of (n_fft, hop, precision, device, low-pass engine)."""
     dev = torch.device(device) if device is not None else default_device()
-    key = (int(n_fft), int(hop), _PREC[precision], dev.index if dev.index is not None else torch.cuda.current_device(), lowpass_engine)
+    key = (int(n_fft), int(hop), _PREC[precision], _device_index(dev), lowpass_engine)
     with _plans_lock:
         p = _plans.get(key)
         if p is None:
@@ -281,6 +302,21 @@ def _h2d(a, dev):
         return _DescRing.get(torch.cuda.current_device()).put(a, dev)
 
 
+def _host_i32(a, dev):
+    """int32 array the library reads from HOST memory, as a host tensor: page-locked when it fits the ring (the library's copy
+    out of it then stays asynchronous).  The caller keeps the tensor until the call that reads it has been queued."""
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if dev.type == "cuda" and 0 < a.nbytes <= _DescRing.SIZE // 8:
+        with torch.cuda.device(dev):
+            return _DescRing.get(torch.cuda.current_device()).stage(a, dev)
+    return torch.from_numpy(a)
+
+
+def _args(values):
+    """Tensors -> their data pointers; everything else as it is."""
+    return [_vp(v) if isinstance(v, torch.Tensor) else v for v in values]
+
+
 def _is_f64(a):
     return (a.dtype == torch.float64) if isinstance(a, torch.Tensor) else (getattr(a, "dtype", None) == np.float64)
 
@@ -322,14 +358,13 @@ class Ragged:
                 ok = ok and a.data_ptr() == end and a.device == a0.device and a.untyped_storage().data_ptr() == st0
                 end += a.numel() * es
             ok = ok and end <= st0 + a0.untyped_storage().nbytes()
-            if ok and arrays[0].device.index == (dev.index if dev.index is not None else torch.cuda.current_device()):
+            if ok and arrays[0].device.index == (_device_index(dev)):
                 lens = np.array([a.shape[0] for a in arrays], dtype=np.int64)
                 total = int(lens.sum())
                 if 0 < total and lens.max() < 2 ** 31:
                     a0 = arrays[0]
                     data = torch.empty(0, dtype=dtype, device=a0.device).set_(a0.untyped_storage(), a0.storage_offset(), (total,), (1,))
-                    off = np.concatenate(([0], np.cumsum(lens)[:-1]))
-                    desc = _h2d(off.astype(np.int64), a0.device)
+                    desc = _h2d(_offsets(lens), a0.device)
                     return Ragged(data, desc, _h2d(lens.astype(np.int32), a0.device), lens)
         ts = []
         for a in arrays:
@@ -341,15 +376,14 @@ class Ragged:
         if len(ts) and lens.max() >= 2 ** 31:
             raise ValueError("signal too long")
         data = torch.cat(ts) if len(ts) else torch.empty(0, dtype=dtype, device=dev)
-        off = np.concatenate(([0], np.cumsum(lens)[:-1])) if len(ts) else np.zeros(0, np.int64)
-        return Ragged(data, _h2d(off.astype(np.int64), dev), _h2d(lens.astype(np.int32), dev), lens)
+        return Ragged(data, _h2d(_offsets(lens), dev), _h2d(lens.astype(np.int32), dev), lens)
 
     @staticmethod
     def _from_views_with_gaps(arrays, dev, dtype):
         a0 = arrays[0]
         if not (isinstance(a0, torch.Tensor) and a0.is_cuda):
             return None
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        idx = _device_index(dev)
         es, st = a0.element_size(), a0.untyped_storage()
         st0, p0, end = st.data_ptr(), a0.data_ptr(), a0.data_ptr()
         off, lens = [], []
@@ -382,9 +416,7 @@ class Ragged:
         if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
             raise ValueError("from_uniform needs a contiguous float32 [N, n] device tensor")
         N, n = x.shape
-        off = torch.arange(N, device=x.device, dtype=torch.int64) * n
-        lens = torch.full((N,), n, device=x.device, dtype=torch.int32)
-        return Ragged(x.view(-1), off, lens, np.full(N, n, dtype=np.int64))
+        return Ragged(x.view(-1), *_uniform_images(N, n, x.device), np.full(N, n, dtype=np.int64))
 
     def split(self, flat=None):
         if not self.packed:
@@ -401,9 +433,8 @@ class _Rows:
         self.T = np.array([plan.frames(n) for n in lens_host], dtype=np.int64)
         self.total = int(self.T.sum())
         self.max_T = int(self.T.max()) if len(self.T) else 0
-        off = np.concatenate(([0], np.cumsum(self.T)[:-1])) if len(self.T) else np.zeros(0, np.int64)
-        self.off_host = off
-        self.off = _h2d(off.astype(np.int64), device)
+        self.off_host = _offsets(self.T)
+        self.off = _h2d(self.off_host, device)
 
 
 def _check_reflect(plan, lens_host):
@@ -442,7 +473,7 @@ class PairBatch:
             p, e = self.plan, self.est
             self.ws_bytes = int(p.lib.ssr_pair_metrics_workspace_bytes_for(p.handle, e.n, e.max_len, self.rows.total, want))
             self.ws = None                                          # release before the larger allocation
-            self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=e.device)
+            self.ws = _workspace(self.ws_bytes, e.device)
             self._ws_mask = want
 
     def run(self, mask=M_ALL, stages=7):
@@ -492,7 +523,7 @@ class MultiPairBatch:
             size_fn = p.lib.ssr_pair_metrics_multi_est64_workspace_bytes if self.est64 else p.lib.ssr_pair_metrics_multi_workspace_bytes
             self.ws_bytes = int(size_fn(p.handle, t.n, self.n_keys, t.max_len, self.rows.total, want))
             self.ws = None
-            self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=t.device)
+            self.ws = _workspace(self.ws_bytes, t.device)
             self._ws_mask = want
 
     def run(self, mask=M_ALL):
@@ -566,19 +597,48 @@ def pair_metrics(plan, est_list, tgt_list, mask=M_ALL, deferred=False):
 
 
 # ---- band-split LSD ---------------------------------------------------------------------------------------------------------
-# Bytes of magnitude images one ssr_pair_lsd_bands call may hold: K + 1 images per item (8 bytes per bin of the batch per key) are
-# more than HBM holds for 36 keys of a large batch, so the keys run in chunks whose images fit in this.
+# Bytes of magnitude images one ssr_pair_lsd_bands call may hold (_pair_keys_chunked: the keys run in chunks whose images fit).
 LSD_BANDS_WS_BYTES = 1 << 30
 
 
-def _edges_host(edges, n_images, n_bands, dev):
-    """int32 [n_images][n_bands + 1] as the library reads it (host memory, page-locked when it fits the ring: asynchronous copy)."""
-    e = np.ascontiguousarray(np.asarray(edges, dtype=np.int32).reshape(n_images, n_bands + 1))
-    if dev.type == "cuda" and e.nbytes <= _DescRing.SIZE // 8:
-        with torch.cuda.device(dev):
-            st = _DescRing.get(torch.cuda.current_device()).stage(e, dev)
-        return st, C.c_void_p(st.data_ptr())
-    return e, e.ctypes.data_as(C.c_void_p)
+def _pair_keys_chunked(plan, est_lists, tgt_list, n_cols, budget, keys_per_chunk, f64_target_error, ws_bytes_of, entries, extra,
+                       deferred):
+    """The multi-key pair calls that hold K + 1 magnitude images per item (8 bytes per bin of the batch per key - more than HBM holds
+    for 36 keys of a large batch): the keys run in chunks of keys_per_chunk, or as many as fit in `budget` bytes of images (a
+    multiple of six where more than six fit: whole groups of the reduction's three keys per wave), every chunk against the same
+    targets.  ws_bytes_of(n, keys, max_len, total_rows) sizes the workspace, entries = (float32-estimate, float64-estimate) entry
+    points, extra(k0, k1) -> the arguments between total_rows and out for keys k0 .. k1 - 1.
+    -> [n, K, n_cols] float64 (deferred: a Pending)."""
+    K, n = len(est_lists), len(tgt_list)
+    with torch.cuda.device(plan.device):
+        tgt = Ragged.from_list(tgt_list, plan.device, allow_gaps=True)
+        if any(_is_f64(t) for t in tgt_list):
+            raise ValueError(f64_target_error)
+        _check_nonempty(tgt.lens_host)
+        rows = _Rows(plan, tgt.lens_host, tgt.device)
+        out = torch.empty((n, K, n_cols), dtype=torch.float64, device=tgt.device)
+        if n and K:
+            if keys_per_chunk is None:
+                plane = rows.total * ((plan.n_bins + 3) & ~3) * 4
+                keys_per_chunk = max(1, budget // max(plane, 1) - 1)
+                if keys_per_chunk > 6:
+                    keys_per_chunk -= keys_per_chunk % 6
+            kc = max(1, min(int(keys_per_chunk), K))
+            ws_bytes = int(ws_bytes_of(n, kc, tgt.max_len, rows.total))
+            ws = _workspace(ws_bytes, tgt.device)
+            for k0 in range(0, K, kc):
+                k1 = min(K, k0 + kc)
+                est = Ragged.from_list_keep64([w for key in est_lists[k0:k1] for w in key], plan.device, allow_gaps=True)
+                if not np.array_equal(est.lens_host, np.tile(tgt.lens_host, k1 - k0)):
+                    raise ValueError("every estimate must be as long as its target (truncate to min_len first)")
+                o = out if k1 - k0 == K else torch.empty((n, k1 - k0, n_cols), dtype=torch.float64, device=tgt.device)
+                args = extra(k0, k1)
+                _lib.check(entries[est.data.dtype == torch.float64](
+                    plan.handle, _vp(est.data), _vp(est.off), _vp(tgt.data), _vp(tgt.off), _vp(tgt.len), _vp(rows.off), n, k1 - k0,
+                    tgt.max_len, rows.total, *_args(args), _vp(o), _vp(ws), ws_bytes, _stream()))
+                if o is not out:
+                    out[:, k0:k1] = o
+        return Pending(out) if deferred else out.cpu().numpy()
 
 
 def spectrogram_lsd_bands(est, target, edges):
@@ -599,13 +659,12 @@ def spectrogram_lsd_bands(est, target, edges):
         nb = e.shape[1] - 1
         if nb < 1:
             raise ValueError("at least one band (two edges) per image")
-        off = torch.arange(N, device=dev, dtype=torch.int64) * T
-        rows = torch.full((N,), T, device=dev, dtype=torch.int32)
+        off, rows = _uniform_images(N, T, dev)
         out = torch.empty((N, nb), dtype=torch.float64, device=dev)
         ws_bytes = int(lib.ssr_spectrogram_lsd_bands_workspace_bytes(N, T, nb))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        keep, ep = _edges_host(e, N, nb, dev)
-        _lib.check(lib.ssr_spectrogram_lsd_bands(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, ep, nb, _vp(out), _vp(ws),
+        ws = _workspace(ws_bytes, dev)
+        ep = _host_i32(e, dev)
+        _lib.check(lib.ssr_spectrogram_lsd_bands(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, _vp(ep), nb, _vp(out), _vp(ws),
                                                  ws_bytes, _stream()))
         return out
 
@@ -613,8 +672,7 @@ def spectrogram_lsd_bands(est, target, edges):
 def pair_lsd_bands(plan, est_lists, tgt_list, edges, deferred=False, keys_per_chunk=None):
     """Band LSDs of K estimates per target: est_lists = K lists of n waveforms (all float32 or all float64, each as long as its
     target), tgt_list = n float32 targets, edges: int [K][n][n_bands + 1] -> [n, K, n_bands] float64 (deferred: a Pending).
-    The keys run in chunks (ssr_pair_lsd_bands holds K + 1 magnitude images per item): keys_per_chunk, or as many as fit in
-    LSD_BANDS_WS_BYTES (a multiple of six where more than six fit: whole groups of the reduction's three keys per wave)."""
+    The keys run in chunks (_pair_keys_chunked: keys_per_chunk, or as many as fit in LSD_BANDS_WS_BYTES)."""
     K, n = len(est_lists), len(tgt_list)
     e = np.asarray(edges, dtype=np.int32)
     if e.ndim != 3 or e.shape[:2] != (K, n):
@@ -622,36 +680,12 @@ def pair_lsd_bands(plan, est_lists, tgt_list, edges, deferred=False, keys_per_ch
     nb = e.shape[2] - 1
     if nb < 1:
         raise ValueError("at least one band (two edges) per image")
-    with torch.cuda.device(plan.device):
-        tgt = Ragged.from_list(tgt_list, plan.device, allow_gaps=True)
-        if any(_is_f64(t) for t in tgt_list):
-            raise ValueError("band LSD takes float32 targets (float64 estimates are kept float64)")
-        _check_nonempty(tgt.lens_host)
-        rows = _Rows(plan, tgt.lens_host, tgt.device)
-        out = torch.empty((n, K, nb), dtype=torch.float64, device=tgt.device)
-        if n and K:
-            if keys_per_chunk is None:
-                plane = rows.total * ((plan.n_bins + 3) & ~3) * 4
-                keys_per_chunk = max(1, LSD_BANDS_WS_BYTES // max(plane, 1) - 1)
-                if keys_per_chunk > 6:
-                    keys_per_chunk -= keys_per_chunk % 6
-            kc = max(1, min(int(keys_per_chunk), K))
-            lib = plan.lib
-            ws_bytes = int(lib.ssr_pair_lsd_bands_workspace_bytes(plan.handle, n, kc, tgt.max_len, rows.total, nb))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=tgt.device)
-            for k0 in range(0, K, kc):
-                k1 = min(K, k0 + kc)
-                est = Ragged.from_list_keep64([w for key in est_lists[k0:k1] for w in key], plan.device, allow_gaps=True)
-                if not np.array_equal(est.lens_host, np.tile(tgt.lens_host, k1 - k0)):
-                    raise ValueError("every estimate must be as long as its target (truncate to min_len first)")
-                o = out if k1 - k0 == K else torch.empty((n, k1 - k0, nb), dtype=torch.float64, device=tgt.device)
-                keep, ep = _edges_host(e[k0:k1], (k1 - k0) * n, nb, tgt.device)
-                fn = lib.ssr_pair_lsd_bands_est64 if est.data.dtype == torch.float64 else lib.ssr_pair_lsd_bands
-                _lib.check(fn(plan.handle, _vp(est.data), _vp(est.off), _vp(tgt.data), _vp(tgt.off), _vp(tgt.len), _vp(rows.off), n,
-                              k1 - k0, tgt.max_len, rows.total, ep, nb, _vp(o), _vp(ws), ws_bytes, _stream()))
-                if o is not out:
-                    out[:, k0:k1] = o
-        return Pending(out) if deferred else out.cpu().numpy()
+    lib = plan.lib
+    return _pair_keys_chunked(plan, est_lists, tgt_list, nb, LSD_BANDS_WS_BYTES, keys_per_chunk,
+                              "band LSD takes float32 targets (float64 estimates are kept float64)",
+                              lambda n, kc, max_len, total: lib.ssr_pair_lsd_bands_workspace_bytes(plan.handle, n, kc, max_len, total, nb),
+                              (lib.ssr_pair_lsd_bands, lib.ssr_pair_lsd_bands_est64),
+                              lambda k0, k1: (_host_i32(e[k0:k1], plan.device), nb), deferred)
 
 
 # ---- STOI / ESTOI ----------------------------------------------------------------------------------------------------------
@@ -685,10 +719,9 @@ def spectrogram_mel(sp, fb):
         N, T, F = (int(v) for v in x.shape)
         out = torch.empty((N, T, nm), dtype=torch.float32, device=dev)
         if N and T:
-            off = torch.arange(N, device=dev, dtype=torch.int64) * T
-            rows = torch.full((N,), T, device=dev, dtype=torch.int32)
+            off, rows = _uniform_images(N, T, dev)
             ws_bytes = int(lib.ssr_spectrogram_mel_workspace_bytes(F, nm))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            ws = _workspace(ws_bytes, dev)
             _lib.check(lib.ssr_spectrogram_mel(_vp(x), _vp(off), _vp(rows), N, T, F, fp, nm, _vp(out), _vp(ws), ws_bytes, _stream()))
         return out
 
@@ -710,10 +743,9 @@ def spectrogram_mel_metrics(est, target, fb, n_cep, which):
         if N:
             if T < 1:
                 raise ValueError("empty spectrogram")
-            off = torch.arange(N, device=dev, dtype=torch.int64) * T
-            rows = torch.full((N,), T, device=dev, dtype=torch.int32)
+            off, rows = _uniform_images(N, T, dev)
             ws_bytes = int(lib.ssr_spectrogram_mel_metrics_workspace_bytes(N, T, F, nm, int(n_cep)))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            ws = _workspace(ws_bytes, dev)
             _lib.check(lib.ssr_spectrogram_mel_metrics(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, fp, nm, int(n_cep), int(which),
                                                        _vp(out), _vp(ws), ws_bytes, _stream()))
         return out
@@ -723,39 +755,16 @@ def pair_mel_metrics(plan, est_lists, tgt_list, fb, n_cep, which, deferred=False
     """Mel distances of K estimates per target: est_lists = K lists of n waveforms (all float32 or all float64, each as long as its
     target), tgt_list = n float32 targets, fb: [plan.n_bins, n_mels] host float32 -> [n, K, 3] float64 (deferred: a Pending).
     The keys run in chunks as in pair_lsd_bands (keys_per_chunk, or as many as fit in MEL_WS_BYTES)."""
-    K, n = len(est_lists), len(tgt_list)
     nb, nm, fp = _fb_arg(fb)
     if nb != plan.n_bins:
         raise ValueError("the filterbank has %d bins, the transform %d" % (nb, plan.n_bins))
-    with torch.cuda.device(plan.device):
-        tgt = Ragged.from_list(tgt_list, plan.device, allow_gaps=True)
-        if any(_is_f64(t) for t in tgt_list):
-            raise ValueError("mel distances take float32 targets (float64 estimates are kept float64)")
-        _check_nonempty(tgt.lens_host)
-        rows = _Rows(plan, tgt.lens_host, tgt.device)
-        out = torch.empty((n, K, 3), dtype=torch.float64, device=tgt.device)
-        if n and K:
-            if keys_per_chunk is None:
-                plane = rows.total * ((plan.n_bins + 3) & ~3) * 4
-                keys_per_chunk = max(1, MEL_WS_BYTES // max(plane, 1) - 1)
-                if keys_per_chunk > 6:
-                    keys_per_chunk -= keys_per_chunk % 6
-            kc = max(1, min(int(keys_per_chunk), K))
-            lib = plan.lib
-            ws_bytes = int(lib.ssr_pair_mel_metrics_workspace_bytes(plan.handle, n, kc, tgt.max_len, rows.total, nm, int(n_cep)))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=tgt.device)
-            for k0 in range(0, K, kc):
-                k1 = min(K, k0 + kc)
-                est = Ragged.from_list_keep64([w for key in est_lists[k0:k1] for w in key], plan.device, allow_gaps=True)
-                if not np.array_equal(est.lens_host, np.tile(tgt.lens_host, k1 - k0)):
-                    raise ValueError("every estimate must be as long as its target (truncate to min_len first)")
-                o = out if k1 - k0 == K else torch.empty((n, k1 - k0, 3), dtype=torch.float64, device=tgt.device)
-                fn = lib.ssr_pair_mel_metrics_est64 if est.data.dtype == torch.float64 else lib.ssr_pair_mel_metrics
-                _lib.check(fn(plan.handle, _vp(est.data), _vp(est.off), _vp(tgt.data), _vp(tgt.off), _vp(tgt.len), _vp(rows.off), n,
-                              k1 - k0, tgt.max_len, rows.total, fp, nm, int(n_cep), int(which), _vp(o), _vp(ws), ws_bytes, _stream()))
-                if o is not out:
-                    out[:, k0:k1] = o
-        return Pending(out) if deferred else out.cpu().numpy()
+    lib = plan.lib
+    return _pair_keys_chunked(plan, est_lists, tgt_list, 3, MEL_WS_BYTES, keys_per_chunk,
+                              "mel distances take float32 targets (float64 estimates are kept float64)",
+                              lambda n, kc, max_len, total: lib.ssr_pair_mel_metrics_workspace_bytes(plan.handle, n, kc, max_len, total, nm,
+                                                                                                     int(n_cep)),
+                              (lib.ssr_pair_mel_metrics, lib.ssr_pair_mel_metrics_est64),
+                              lambda k0, k1: (fp, nm, int(n_cep), int(which)), deferred)
 
 
 def octave_taps(p, q):
@@ -813,14 +822,21 @@ class StoiResamplePlan:
         return n
 
 
-def _host_i32(a, dev):
-    """int32 array the library reads from HOST memory: page-locked when it fits the ring (its copy then stays asynchronous)."""
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    if dev.type == "cuda" and 0 < a.nbytes <= _DescRing.SIZE // 8:
-        with torch.cuda.device(dev):
-            st = _DescRing.get(torch.cuda.current_device()).stage(a, dev)
-        return st, C.c_void_p(st.data_ptr())
-    return a, a.ctypes.data_as(C.c_void_p)
+def _resample_f64(wavs, plan, dev):
+    """[float32 / float64 waveforms] (or a float64 Ragged) -> Ragged float64, resampled in float64 under `plan` (a StoiResamplePlan
+    or a ResamplePlan: up, down, taps64, n_pre_remove, n_out) in one ssr_resample_poly_f64 launch; the identity plan returns the
+    input batch itself, widened."""
+    r = wavs if isinstance(wavs, Ragged) else Ragged.from_list(list(wavs), dev, torch.float64)
+    if plan.identity:
+        return r
+    out_len = np.array([plan.n_out(n) for n in r.lens_host], dtype=np.int64)
+    out = torch.empty(int(out_len.sum()), dtype=torch.float64, device=dev)
+    out_off_d, out_len_d = _h2d(_offsets(out_len), dev), _h2d(out_len.astype(np.int32), dev)
+    if r.n and out_len.max() > 0:
+        _lib.check(_lib.load().ssr_resample_poly_f64(_vp(r.data), _vp(r.off), _vp(r.len), _vp(out_off_d), _vp(out_len_d), r.n,
+                                                     int(out_len.max()), plan.up, plan.down, _vp(plan.taps64), int(plan.taps64.numel()),
+                                                     plan.n_pre_remove, _vp(out), _stream()))
+    return Ragged(out, out_off_d, out_len_d, out_len)
 
 
 def resample_to_stoi_rate(wavs, fs, device=None):
@@ -828,51 +844,10 @@ def resample_to_stoi_rate(wavs, fs, device=None):
     the Octave taps; bit-identical to scipy.signal.resample_poly(x, 10000, fs, window=h))."""
     dev = torch.device(device) if device is not None else default_device()
     with torch.cuda.device(dev):
-        r = wavs if isinstance(wavs, Ragged) else Ragged.from_list(list(wavs), dev, torch.float64)
-        sp = StoiResamplePlan.get(fs, dev)
-        if sp.identity:
-            return r
-        out_len = np.array([sp.n_out(n) for n in r.lens_host], dtype=np.int64)
-        out_off = np.concatenate(([0], np.cumsum(out_len)[:-1])).astype(np.int64) if r.n else np.zeros(0, np.int64)
-        out = torch.empty(int(out_len.sum()), dtype=torch.float64, device=dev)
-        out_off_d, out_len_d = _h2d(out_off, dev), _h2d(out_len.astype(np.int32), dev)
-        if r.n and out_len.max() > 0:
-            _lib.check(_lib.load().ssr_resample_poly_f64(_vp(r.data), _vp(r.off), _vp(r.len), _vp(out_off_d), _vp(out_len_d), r.n,
-                                                         int(out_len.max()), sp.up, sp.down, _vp(sp.taps64), int(sp.taps64.numel()),
-                                                         sp.n_pre_remove, _vp(out), _stream()))
-        return Ragged(out, out_off_d, out_len_d, out_len)
+        return _resample_f64(wavs, StoiResamplePlan.get(fs, dev), dev)
 
 
-def stoi(tgt_list, est_list, tgt_index, fs, which=_lib.STOI, device=None, deferred=False):
-    """STOI / ESTOI of estimate e against target tgt_index[e] (ssr_stoi): waveforms at `fs` (float32 or float64, each estimate as
-    long as its target) -> [n_est, n_out] float64 (which = STOI_BOTH: columns STOI, ESTOI).  Targets and estimates are resampled to
-    10 kHz in one launch; each target's mask and band image are computed once for all its estimates.  deferred: a Pending."""
-    require_gpu()
-    dev = torch.device(device) if device is not None else default_device()
-    n_t, n_e = len(tgt_list), len(est_list)
-    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
-    if idx.shape[0] != n_e:
-        raise ValueError("one target index per estimate")
-    n_out = 2 if which == _lib.STOI_BOTH else 1
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((n_e, n_out), dtype=torch.float64, device=dev)
-        if n_e:
-            r = resample_to_stoi_rate(list(tgt_list) + list(est_list), fs, dev)
-            lens = r.lens_host.astype(np.int32)
-            if idx.min() < 0 or idx.max() >= n_t:
-                raise ValueError("tgt_index out of range")
-            if not np.array_equal(lens[n_t:], lens[:n_t][idx]):
-                raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
-            ws_bytes = int(lib.ssr_stoi_workspace_bytes(lens[:n_t].ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p), n_e))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-            keep = [_host_i32(a, dev) for a in (lens[:n_t], lens[n_t:], idx)]
-            _lib.check(lib.ssr_stoi(_vp(r.data), _vp(r.off), keep[0][1], n_t, _vp(r.data), _vp(r.off[n_t:]), keep[1][1], keep[2][1], n_e,
-                                    int(which), _vp(out), _vp(ws), ws_bytes, _stream()))
-        return Pending(out) if deferred else out.cpu().numpy()
-
-
-# ---- waveform metrics: SNR, SI-SDR, segmental SNR ----------------------------------------------------------------------------
+# ---- the per-pair metric families: estimate e against target tgt_index[e] ------------------------------------------------------
 def _ragged_where_they_lie(arrays, dev, dtype):
     """(data, off, lens_host) of a list of signals for a kernel that only reads them: device views of one buffer are taken where
     they lie in ANY order (from_list(allow_gaps=True) reads them in address order; the offsets are put back in list order), other
@@ -888,39 +863,79 @@ def _ragged_where_they_lie(arrays, dev, dtype):
     return r.data, r.off[_h2d(inv, r.device)], r.lens_host[inv]
 
 
-def wave_metrics(tgt_list, est_list, tgt_index, fs, which=7, device=None, deferred=False):
-    """SNR / SI-SDR / segmental SNR of estimate e against target tgt_index[e] (ssr_wave_metrics, DESIGN §10): waveforms at `fs`
-    (float32 or float64, each estimate as long as its target; a list holding both dtypes is widened to float64) -> [n_est, n_out]
-    float64, columns in bit order of `which` (1 snr, 2 si_sdr, 4 seg_snr).  Device views of one buffer are read where they lie;
-    pairs next to each other that name one target read its tiles once.  deferred: a Pending."""
+def _placed_where_they_lie(tgts, ests, idx, dev):
+    """The signals as ssr_wave_metrics / ssr_quality_metrics take them - (data, is-float64 flag, offsets) per side, read in their own
+    dtype (a list holding both dtypes is widened to float64) -> (target side, estimate side, target lengths, estimate lengths)."""
+    sides = []
+    for wavs in (tgts, ests):
+        f64 = any(_is_f64(w) for w in wavs)
+        data, off, lens = _ragged_where_they_lie(wavs, dev, torch.float64 if f64 else torch.float32)
+        sides.append(((data, int(f64), off), lens))
+    return sides[0][0], sides[1][0], sides[0][1], sides[1][1]
+
+
+def _placed_resampled(r, n_t):
+    """The signals as ssr_stoi / ssr_f0_metrics take them - (data, offsets) per side of ONE float64 batch r that holds the n_t
+    targets, then the estimates (resampled together, in one launch) -> as _placed_where_they_lie."""
+    return (r.data, r.off), (r.data, r.off[n_t:]), r.lens_host[:n_t], r.lens_host[n_t:]
+
+
+def _pair_index_metrics(tgt_list, est_list, tgt_index, n_cols, place, ws_bytes_of, entry, scalars, device, deferred):
+    """One call of a per-pair family: estimate e is scored against target tgt_index[e], every estimate as long as its target ->
+    [n_est, n_cols] float64 (deferred: a Pending).  place(targets, estimates, tgt_index, dev) puts the signals on the device (see
+    _placed_*).  The C ABI's calls share one shape: ws_bytes_of(tgt_len, n_tgt, tgt_index, n_est) and entry(target side ...,
+    tgt_len, n_tgt, estimate side ..., tgt_index, n_est, scalars ..., out, workspace, bytes, stream), with tgt_len and tgt_index
+    int32 arrays in HOST memory."""
     require_gpu()
     dev = torch.device(device) if device is not None else default_device()
     n_t, n_e = len(tgt_list), len(est_list)
     idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
     if idx.shape[0] != n_e:
         raise ValueError("one target index per estimate")
+    with torch.cuda.device(dev):
+        out = torch.empty((n_e, n_cols), dtype=torch.float64, device=dev)
+        if n_e:
+            if idx.min() < 0 or idx.max() >= n_t:
+                raise ValueError("tgt_index out of range")
+            tgt_side, est_side, tl, el = place(list(tgt_list), list(est_list), idx, dev)
+            if not np.array_equal(el, tl[idx]):
+                raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+            lens = tl.astype(np.int32)
+            ws_bytes = int(ws_bytes_of(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p), n_e))
+            ws = _workspace(ws_bytes, dev)
+            lens_h, idx_h = _host_i32(lens, dev), _host_i32(idx, dev)
+            _lib.check(entry(*_args(tgt_side), _vp(lens_h), n_t, *_args(est_side), _vp(idx_h), n_e, *scalars, _vp(out), _vp(ws), ws_bytes,
+                             _stream()))
+        return Pending(out) if deferred else out.cpu().numpy()
+
+
+def stoi(tgt_list, est_list, tgt_index, fs, which=_lib.STOI, device=None, deferred=False):
+    """STOI / ESTOI of estimate e against target tgt_index[e] (ssr_stoi): waveforms at `fs` (float32 or float64, each estimate as
+    long as its target) -> [n_est, n_out] float64 (which = STOI_BOTH: columns STOI, ESTOI).  Targets and estimates are resampled to
+    10 kHz in one launch; each target's mask and band image are computed once for all its estimates.  deferred: a Pending."""
+    lib = _lib.load()
+
+    def place(tgts, ests, idx, dev):
+        # the lengths are compared (and the estimates' own passed to the library) AFTER resampling
+        tgt_side, est_side, tl, el = _placed_resampled(resample_to_stoi_rate(tgts + ests, fs, dev), len(tgts))
+        return tgt_side, est_side + (_host_i32(el, dev),), tl, el
+    return _pair_index_metrics(tgt_list, est_list, tgt_index, 2 if which == _lib.STOI_BOTH else 1, place, lib.ssr_stoi_workspace_bytes,
+                               lib.ssr_stoi, (int(which),), device, deferred)
+
+
+# ---- waveform metrics: SNR, SI-SDR, segmental SNR ----------------------------------------------------------------------------
+def wave_metrics(tgt_list, est_list, tgt_index, fs, which=7, device=None, deferred=False):
+    """SNR / SI-SDR / segmental SNR of estimate e against target tgt_index[e] (ssr_wave_metrics, DESIGN §10): waveforms at `fs`
+    (float32 or float64, each estimate as long as its target; a list holding both dtypes is widened to float64) -> [n_est, n_out]
+    float64, columns in bit order of `which` (1 snr, 2 si_sdr, 4 seg_snr).  Device views of one buffer are read where they lie;
+    pairs next to each other that name one target read its tiles once.  deferred: a Pending."""
     which = int(which)
     if not 1 <= which <= 7:
         raise ValueError("which must be a non-empty combination of 1 (snr), 2 (si_sdr) and 4 (seg_snr)")
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((n_e, bin(which).count("1")), dtype=torch.float64, device=dev)
-        if n_e:
-            if idx.min() < 0 or idx.max() >= n_t:
-                raise ValueError("tgt_index out of range")
-            t64, e64 = any(_is_f64(t) for t in tgt_list), any(_is_f64(e) for e in est_list)
-            td, toff, tl = _ragged_where_they_lie(list(tgt_list), dev, torch.float64 if t64 else torch.float32)
-            ed, eoff, el = _ragged_where_they_lie(list(est_list), dev, torch.float64 if e64 else torch.float32)
-            if not np.array_equal(el, tl[idx]):
-                raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
-            lens = tl.astype(np.int32)
-            ws_bytes = int(lib.ssr_wave_metrics_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p),
-                                                                n_e, int(fs), which))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-            keep = [_host_i32(a, dev) for a in (lens, idx)]
-            _lib.check(lib.ssr_wave_metrics(_vp(td), int(t64), _vp(toff), keep[0][1], n_t, _vp(ed), int(e64), _vp(eoff), keep[1][1],
-                                            n_e, int(fs), which, _vp(out), _vp(ws), ws_bytes, _stream()))
-        return Pending(out) if deferred else out.cpu().numpy()
+    return _pair_index_metrics(tgt_list, est_list, tgt_index, bin(which).count("1"), _placed_where_they_lie,
+                               lambda *a: lib.ssr_wave_metrics_workspace_bytes(*a, int(fs), which), lib.ssr_wave_metrics,
+                               (int(fs), which), device, deferred)
 
 
 # ---- objective quality measures: LLR, LPC cepstral distance, WSS, fwSNRseg ------------------------------------------------------
@@ -942,12 +957,6 @@ def quality_metrics(tgt_list, est_list, tgt_index, fs, which=15, lpc_order=0, de
     -> [n_est, n_out] float64, columns in bit order of `which` (1 llr, 2 cep_dist, 4 wss, 8 fwseg_snr).  lpc_order 0: 10 below
     10 kHz, else 16.  Device views of one buffer are read where they lie; pairs next to each other that name one target analyse
     its frames once.  deferred: a Pending."""
-    require_gpu()
-    dev = torch.device(device) if device is not None else default_device()
-    n_t, n_e = len(tgt_list), len(est_list)
-    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
-    if idx.shape[0] != n_e:
-        raise ValueError("one target index per estimate")
     which, lpc_order = int(which), int(lpc_order)
     if not 1 <= which <= 15:
         raise ValueError("which must be a non-empty combination of 1 (llr), 2 (cep_dist), 4 (wss) and 8 (fwseg_snr)")
@@ -956,24 +965,9 @@ def quality_metrics(tgt_list, est_list, tgt_index, fs, which=15, lpc_order=0, de
     if not 8000 <= int(fs) <= 48000:
         raise ValueError("the quality measures need 8000 <= fs <= 48000")
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((n_e, bin(which).count("1")), dtype=torch.float64, device=dev)
-        if n_e:
-            if idx.min() < 0 or idx.max() >= n_t:
-                raise ValueError("tgt_index out of range")
-            t64, e64 = any(_is_f64(t) for t in tgt_list), any(_is_f64(e) for e in est_list)
-            td, toff, tl = _ragged_where_they_lie(list(tgt_list), dev, torch.float64 if t64 else torch.float32)
-            ed, eoff, el = _ragged_where_they_lie(list(est_list), dev, torch.float64 if e64 else torch.float32)
-            if not np.array_equal(el, tl[idx]):
-                raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
-            lens = tl.astype(np.int32)
-            ws_bytes = int(lib.ssr_quality_metrics_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p),
-                                                                   n_e, int(fs), lpc_order, which))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-            keep = [_host_i32(a, dev) for a in (lens, idx)]
-            _lib.check(lib.ssr_quality_metrics(_vp(td), int(t64), _vp(toff), keep[0][1], n_t, _vp(ed), int(e64), _vp(eoff), keep[1][1],
-                                               n_e, int(fs), lpc_order, which, _vp(out), _vp(ws), ws_bytes, _stream()))
-        return Pending(out) if deferred else out.cpu().numpy()
+    return _pair_index_metrics(tgt_list, est_list, tgt_index, bin(which).count("1"), _placed_where_they_lie,
+                               lambda *a: lib.ssr_quality_metrics_workspace_bytes(*a, int(fs), lpc_order, which), lib.ssr_quality_metrics,
+                               (int(fs), lpc_order, which), device, deferred)
 
 
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
@@ -1005,19 +999,7 @@ def resample_to_pitch_rate(wavs, fs, device=None):
         raise ValueError("the pitch metrics need 8000 <= fs <= 48000")
     dev = torch.device(device) if device is not None else default_device()
     with torch.cuda.device(dev):
-        r = wavs if isinstance(wavs, Ragged) else Ragged.from_list(list(wavs), dev, torch.float64)
-        rp = ResamplePlan.get(PITCH_FS, int(fs), dev)
-        if rp.identity:
-            return r
-        out_len = np.array([rp.n_out(n) for n in r.lens_host], dtype=np.int64)
-        out_off = np.concatenate(([0], np.cumsum(out_len)[:-1])).astype(np.int64) if r.n else np.zeros(0, np.int64)
-        out = torch.empty(int(out_len.sum()), dtype=torch.float64, device=dev)
-        out_off_d, out_len_d = _h2d(out_off, dev), _h2d(out_len.astype(np.int32), dev)
-        if r.n and out_len.max() > 0:
-            _lib.check(_lib.load().ssr_resample_poly_f64(_vp(r.data), _vp(r.off), _vp(r.len), _vp(out_off_d), _vp(out_len_d), r.n,
-                                                         int(out_len.max()), rp.up, rp.down, _vp(rp.taps64), int(rp.taps64.numel()),
-                                                         rp.n_pre_remove, _vp(out), _stream()))
-        return Ragged(out, out_off_d, out_len_d, out_len)
+        return _resample_f64(wavs, ResamplePlan.get(PITCH_FS, int(fs), dev), dev)
 
 
 def f0_track(wavs, fs, fmin=50.0, fmax=500.0, device=None):
@@ -1034,15 +1016,15 @@ def f0_track(wavs, fs, fmin=50.0, fmax=500.0, device=None):
         r = resample_to_pitch_rate(list(wavs), fs, dev)
         lens = r.lens_host.astype(np.int32)
         T = np.array([pitch_frames(m) for m in lens], np.int64)
-        foff = np.concatenate(([0], np.cumsum(T)[:-1])).astype(np.int64)
+        foff = _offsets(T)
         tot = max(int(T.sum()), 1)
         f0, ap, en = (torch.empty(tot, dtype=torch.float64, device=dev) for _ in range(3))
         vo = torch.empty(tot, dtype=torch.uint8, device=dev)
         ws_bytes = int(lib.ssr_f0_track_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n, fmin, fmax))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        keep = _host_i32(lens, dev)
+        ws = _workspace(ws_bytes, dev)
+        lens_h = _host_i32(lens, dev)
         foff_d = _h2d(foff, dev)
-        _lib.check(lib.ssr_f0_track(_vp(r.data), _vp(r.off), keep[1], n, fmin, fmax, _vp(f0), _vp(ap), _vp(en), _vp(vo), _vp(foff_d),
+        _lib.check(lib.ssr_f0_track(_vp(r.data), _vp(r.off), _vp(lens_h), n, fmin, fmax, _vp(f0), _vp(ap), _vp(en), _vp(vo), _vp(foff_d),
                                     _vp(ws), ws_bytes, _stream()))
         f0, ap, en, vo = (t.cpu().numpy() for t in (f0, ap, en, vo))
     return [(f0[a:a + t], vo[a:a + t].astype(bool), ap[a:a + t], en[a:a + t]) for a, t in zip(foff, T)]
@@ -1053,12 +1035,6 @@ def pitch_metrics(tgt_list, est_list, tgt_index, fs, which=31, fmin=50.0, fmax=5
     at `fs` (float32 or float64, each estimate as long as its target) -> [n_est, n_out] float64, columns in bit order of `which`
     (1 f0_rmse, 2 f0_corr, 4 gpe, 8 vde, 16 ffe).  Targets and estimates are resampled to 16 kHz in one launch; every target is
     tracked once for all its estimates.  deferred: a Pending."""
-    require_gpu()
-    dev = torch.device(device) if device is not None else default_device()
-    n_t, n_e = len(tgt_list), len(est_list)
-    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
-    if idx.shape[0] != n_e:
-        raise ValueError("one target index per estimate")
     which = int(which)
     if not 1 <= which <= 31:
         raise ValueError("which must be a non-empty combination of 1 (f0_rmse), 2 (f0_corr), 4 (gpe), 8 (vde) and 16 (ffe)")
@@ -1066,23 +1042,16 @@ def pitch_metrics(tgt_list, est_list, tgt_index, fs, which=31, fmin=50.0, fmax=5
     if not 8000 <= int(fs) <= 48000:
         raise ValueError("the pitch metrics need 8000 <= fs <= 48000")
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((n_e, bin(which).count("1")), dtype=torch.float64, device=dev)
-        if n_e:
-            if idx.min() < 0 or idx.max() >= n_t:
-                raise ValueError("tgt_index out of range")
-            n_in = np.array([int(a.shape[0]) for a in list(tgt_list) + list(est_list)], np.int64)
-            if not np.array_equal(n_in[n_t:], n_in[:n_t][idx]):
-                raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
-            r = resample_to_pitch_rate(list(tgt_list) + list(est_list), fs, dev)
-            lens = r.lens_host.astype(np.int32)
-            ws_bytes = int(lib.ssr_f0_metrics_workspace_bytes(lens[:n_t].ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p),
-                                                              n_e, fmin, fmax, which))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-            keep = [_host_i32(a, dev) for a in (lens[:n_t], idx)]
-            _lib.check(lib.ssr_f0_metrics(_vp(r.data), _vp(r.off), keep[0][1], n_t, _vp(r.data), _vp(r.off[n_t:]), keep[1][1], n_e,
-                                          fmin, fmax, which, _vp(out), _vp(ws), ws_bytes, _stream()))
-        return Pending(out) if deferred else out.cpu().numpy()
+
+    def place(tgts, ests, idx, dev):
+        # the lengths are compared BEFORE resampling (two lengths at fs can round to one at 16 kHz)
+        n_in = np.array([int(a.shape[0]) for a in tgts + ests], np.int64)
+        if not np.array_equal(n_in[len(tgts):], n_in[:len(tgts)][idx]):
+            raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+        return _placed_resampled(resample_to_pitch_rate(tgts + ests, fs, dev), len(tgts))
+    return _pair_index_metrics(tgt_list, est_list, tgt_index, bin(which).count("1"), place,
+                               lambda *a: lib.ssr_f0_metrics_workspace_bytes(*a, fmin, fmax, which), lib.ssr_f0_metrics,
+                               (fmin, fmax, which), device, deferred)
 
 
 def stft(plan, wavs, kind="mag", torch_style_pad=False):
@@ -1191,11 +1160,11 @@ def spectrogram_metrics(est_sps, tgt_sps, mask=M_ALL):
             raise ValueError("win_size exceeds image extent")
         x = torch.cat([e.reshape(-1) for e in es])
         y = torch.cat([t.reshape(-1) for t in ts])
-        off = _h2d(np.concatenate(([0], np.cumsum(T)[:-1])).astype(np.int64), dev)
+        off = _h2d(_offsets(T), dev)
         rows = _h2d(T.astype(np.int32), dev)
         n, max_T = len(es), int(T.max())
         ws_bytes = int(lib.ssr_spectrogram_metrics_workspace_bytes(n, max_T, F))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ws = _workspace(ws_bytes, dev)
         out = torch.empty((n, 4), dtype=torch.float64, device=dev)
         _lib.check(lib.ssr_spectrogram_metrics(_vp(x), _vp(y), _vp(off), _vp(rows), n, max_T, F, mask, _vp(out), _vp(ws),
                                                ws_bytes, _stream()))
@@ -1215,7 +1184,7 @@ class LowpassBatch:
         self.rows = _Rows(plan, ragged.lens_host, ragged.device)
         self.set_cuts(cut_bins)
         self.ws_bytes = int(plan.lib.ssr_ola_workspace_bytes(plan.handle, self.rows.total))
-        self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=ragged.device)
+        self.ws = _workspace(self.ws_bytes, ragged.device)
         # out: a caller-owned float32 buffer of the batch's size (e.g. one key's slice of a multi-key estimate buffer)
         if out is not None and (out.dtype != torch.float32 or out.numel() != ragged.data.numel() or not out.is_contiguous()):
             raise ValueError("out must be a contiguous float32 buffer of the batch's size")
@@ -1266,7 +1235,7 @@ class MultiLowpassBatch:
         self.cuts = np.asarray(cut_bins, dtype=np.int32).reshape(-1)
         self.n_keys = int(self.cuts.size)
         self.ws_bytes = int(plan.lib.ssr_ola_workspace_bytes(plan.handle, self.rows.total))
-        self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=ragged.device)
+        self.ws = _workspace(self.ws_bytes, ragged.device)
         total = ragged.data.numel()
         if out is not None and (out.dtype != torch.float32 or out.numel() != self.n_keys * total or not out.is_contiguous()):
             raise ValueError("out must be a contiguous float32 buffer of n_keys x the batch's size")
@@ -1319,10 +1288,10 @@ def istft(plan, res, ims, lengths):
                 raise ValueError("spectrogram rows do not match ssr_num_frames(length)")
         re = torch.cat([r_.to(device=dev, dtype=torch.float32).reshape(-1) for r_ in res])
         im = torch.cat([i_.to(device=dev, dtype=torch.float32).reshape(-1) for i_ in ims])
-        out_off = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
+        out_off = _offsets(lens)
         out = torch.empty(int(lens.sum()), dtype=torch.float32, device=dev)
         ws_bytes = int(plan.lib.ssr_ola_workspace_bytes(plan.handle, rows.total))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ws = _workspace(ws_bytes, dev)
         # descriptor tensors must stay referenced until the launch has been enqueued: a temporary would be
         # returned to the caching allocator (and its block re-used by the next temporary) before the call
         lens_d = _h2d(lens.astype(np.int32), dev)
@@ -1383,7 +1352,7 @@ class ResampleBatch:
             self.out_len = ragged.lens_host.copy()
         else:
             self.out_len = np.array([self.rp.n_out(n) for n in ragged.lens_host], dtype=np.int64)
-        self.out_off = np.concatenate(([0], np.cumsum(self.out_len)[:-1])).astype(np.int64) if ragged.n else np.zeros(0, np.int64)
+        self.out_off = _offsets(self.out_len)
         self.out_off_d = _h2d(self.out_off, dev)
         self.out_len_d = _h2d(self.out_len.astype(np.int32), dev)
         self.out = torch.empty(int(self.out_len.sum()), dtype=ragged.data.dtype, device=dev) if alloc else None
@@ -1562,7 +1531,7 @@ def resample_sinc(wavs, sr_orig, sr_new, res_type="kaiser_best", device=None, fi
         sp = SincPlan.get(sr_orig, sr_new, res_type, dev)
         out_len = np.array([sp.n_out(n) for n in r.lens_host], dtype=np.int64)
         want = np.array([int(np.ceil(n * sp.ratio)) for n in r.lens_host], dtype=np.int64) if fix else out_len
-        out_off = np.concatenate(([0], np.cumsum(want)[:-1])).astype(np.int64) if r.n else np.zeros(0, np.int64)
+        out_off = _offsets(want)
         out = torch.zeros(int(want.sum()), dtype=torch.float32, device=dev)       # fix_length pads with zeros
         if r.n and out_len.max() > 0:
             out_off_d = _h2d(out_off, dev)
@@ -1595,8 +1564,7 @@ class _Staging:
         """One arena pair per (resolved device index, role).  role "packed": io.PackedBatch (the prefetching file path);
         "list": upload_decoded() of a list of RawAudio - its own pair, so that a list upload in the middle of an in-flight
         PackedBatch (its non-RIFF `others`) can never flip that batch's arenas."""
-        d = torch.device(dev)
-        idx = d.index if d.index is not None else torch.cuda.current_device()
+        idx = _device_index(torch.device(dev))
         with cls._by_dev_lock:
             return cls._by_dev.setdefault((idx, role), cls())
 
@@ -1628,7 +1596,7 @@ def _h2d_arena(st, k, arena, total, dev):
     twin is a persistent buffer (grown when a batch needs more), so no allocation crosses the two streams' pools.  Ordering, all on
     the GPU: the upload stream waits for the event recorded behind the last kernel that read the twin (consumed()), the current
     stream waits for the copy.  -> (the twin's first `total` elements, consumed)."""
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    idx = _device_index(dev)
     side = _upload_streams.get(idx)
     if side is None:
         side = _upload_streams[idx] = torch.cuda.Stream(device=idx)
@@ -1656,7 +1624,7 @@ def _h2d_arena(st, k, arena, total, dev):
 def _pcm_to_float(d16, in_off, frames, chans, dev):
     """int16 device buffer + host descriptors -> (flat float32 mono device buffer, host out offsets)."""
     n = len(frames)
-    out_off = np.concatenate(([0], np.cumsum(frames)[:-1]))
+    out_off = _offsets(frames)
     desc = _h2d(np.concatenate((in_off, out_off)).astype(np.int64), dev)
     desc32 = _h2d(np.concatenate((frames.astype(np.int32), chans.astype(np.int32))), dev)
     flat = torch.empty(int(frames.sum()), dtype=torch.float32, device=dev)
@@ -1700,7 +1668,7 @@ def upload_decoded(raw, device=None):
             st = _Staging.get(dev, "list")
             k, arena = st.arena(total)
             host = arena.numpy()
-            in_off = np.concatenate(([0], np.cumsum(sizes)[:-1]))
+            in_off = _offsets(sizes)
             for i, o in zip(pcm, in_off):
                 host[o:o + raw[i].pcm.shape[0]] = raw[i].pcm
             d16, consumed = _h2d_arena(st, k, arena, total, dev)
@@ -1732,7 +1700,7 @@ def sosfiltfilt(sos, wavs, device=None):
         sos_d = _h2d(sos, dev)
         zi_d = _h2d(np.ascontiguousarray(sosfilt_zi(sos), dtype=np.float64), dev)
         ws_bytes = int(lib.ssr_sosfiltfilt_workspace_bytes(total, r.n, edge))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ws = _workspace(ws_bytes, dev)
         y = torch.empty(total, dtype=torch.float64, device=dev)
         fn = lib.ssr_sosfiltfilt_f64 if r.data.dtype == torch.float64 else lib.ssr_sosfiltfilt
         _lib.check(fn(_vp(r.data), _vp(r.off), _vp(r.len), r.n, total, _vp(sos_d), _vp(zi_d), n_sections, edge, _vp(y), _vp(ws),
@@ -1796,7 +1764,7 @@ def sosfiltfilt_multi(sos_list, wavs, device=None):
             eg = np.array(edges[d0:d0 + D], dtype=np.int32)
             sos_d, zi_d = _h2d(sos_h, dev), _h2d(zi_h, dev)
             ws_bytes = int(lib.ssr_sosfiltfilt_multi_workspace_bytes(total, r.n, eg.ctypes.data_as(C.c_void_p), D))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            ws = _workspace(ws_bytes, dev)
             y = torch.empty((D, total), dtype=torch.float64, device=dev)
             _lib.check(lib.ssr_sosfiltfilt_multi(_vp(r.data), _vp(r.off), _vp(r.len), r.n, total, _vp(sos_d), _vp(zi_d),
                                                  ns.ctypes.data_as(C.c_void_p), eg.ctypes.data_as(C.c_void_p), D, _vp(y), total, _vp(ws),
@@ -1818,7 +1786,7 @@ def xcorr_argmax(a_list, b_list, device=None):
             raise ValueError("empty signal")
         lib = _lib.load()
         ws_bytes = int(lib.ssr_xcorr_workspace_bytes(ra.n, ra.max_len))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ws = _workspace(ws_bytes, dev)
         out = torch.empty(ra.n, dtype=torch.int64, device=dev)
         _lib.check(lib.ssr_xcorr_argmax(_vp(ra.data), _vp(ra.off), _vp(rb.data), _vp(rb.off), _vp(ra.len), ra.n, ra.max_len,
                                         _vp(out), _vp(ws), ws_bytes, _stream()))

@@ -100,6 +100,34 @@ inline bool ssr_multi_fast_path(const ssr_plan* pl, bool est64) {
   return ssr_stft_uses_wave_engine(pl, false) || ssr_stft_rn_wave_radix(pl) != 0;
 }
 
+// ---- the per-pair families (tu_stoi / tu_wave_metrics / tu_quality / tu_pitch): estimate e is scored against target tgt_index[e] ----
+// host-side validation of the two descriptor arrays (host memory): lengths in [0, len_limit), indices in [0, n_tgt)
+inline int ssr_check_pair_index(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int64_t len_limit,
+                                const char* len_msg, const char* count_msg = "n_tgt and n_est must be >= 0") {
+  if (n_tgt < 0 || n_est < 0) return ssr_fail(SSR_ERR_INVALID_ARG, count_msg);
+  if ((n_tgt > 0 && !tgt_len) || (n_est > 0 && !tgt_index)) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  for (int t = 0; t < n_tgt; ++t)
+    if (tgt_len[t] < 0 || tgt_len[t] >= len_limit) return ssr_fail(SSR_ERR_INVALID_ARG, len_msg);
+  for (int e = 0; e < n_est; ++e)
+    if (tgt_index[e] < 0 || tgt_index[e] >= n_tgt) return ssr_fail(SSR_ERR_INVALID_ARG, "tgt_index out of range");
+  return SSR_OK;
+}
+// the two arrays -> the head of the workspace (host arrays: from page-locked memory these copies are asynchronous - the caller
+// keeps them until the stream has passed)
+inline int ssr_upload_pair_index(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int32_t* len_dev,
+                                 int32_t* idx_dev, hipStream_t s) {
+  if (n_tgt) HIP_TRY(hipMemcpyAsync(len_dev, tgt_len, (size_t)n_tgt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(idx_dev, tgt_index, (size_t)n_est * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  return SSR_OK;
+}
+// f(TT{}, TE{}) with the element types of the target and estimate buffers: (float | double) x (float | double)
+template <typename F> inline void ssr_dispatch_pair_dtypes(bool tgt_f64, bool est_f64, F&& f) {
+  if (!tgt_f64 && !est_f64) f(float{}, float{});
+  else if (!tgt_f64) f(float{}, double{});
+  else if (!est_f64) f(double{}, float{});
+  else f(double{}, double{});
+}
+
 // ---- launchers defined by the kernel translation units --------------------------------------------------------
 template <typename T> struct SsrStftParams;
 template <typename T> struct SsrLowpassParams;

@@ -49,12 +49,7 @@ static int check_metrics_args(const int32_t* tgt_len, int n_tgt, const int32_t* 
                               int which) {
   if (which < 1 || which > 31) return ssr_fail(SSR_ERR_INVALID_ARG, "which must be a non-empty combination of the SSR_PITCH_* bits");
   if (int rc = check_pitch_range(fmin, fmax)) return rc;
-  if (int rc = check_pitch_lens(tgt_len, n_tgt)) return rc;
-  if (n_est < 0) return ssr_fail(SSR_ERR_INVALID_ARG, "signal counts must be >= 0");
-  if (n_est > 0 && !tgt_index) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
-  for (int e = 0; e < n_est; ++e)
-    if (tgt_index[e] < 0 || tgt_index[e] >= n_tgt) return ssr_fail(SSR_ERR_INVALID_ARG, "tgt_index out of range");
-  return SSR_OK;
+  return ssr_check_pair_index(tgt_len, n_tgt, tgt_index, n_est, 1 << 29, "lengths must be in [0, 2^29)", "signal counts must be >= 0");
 }
 
 // workspace layout: a deterministic function of the lengths (and the pair -> target map)
@@ -145,9 +140,7 @@ extern "C" int ssr_f0_metrics(const double* tgt, const int64_t* tgt_off, const i
   hipStream_t s = (hipStream_t)stream;
   int32_t* len_dev = (int32_t*)(ws + w.off_len);
   int32_t* idx_dev = (int32_t*)(ws + w.off_idx);
-  // (host arrays: from page-locked memory these copies are asynchronous - the caller keeps them until the stream has passed)
-  HIP_TRY(hipMemcpyAsync(len_dev, tgt_len, (size_t)n_tgt * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(idx_dev, tgt_index, (size_t)n_est * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (int rc = ssr_upload_pair_index(tgt_len, n_tgt, tgt_index, n_est, len_dev, idx_dev, s)) return rc;
   SsrPitchParams p{};
   p.sig_a = tgt; p.off_a = tgt_off; p.sig_b = est; p.off_b = est_off; p.len_a = len_dev; p.idx_b = idx_dev;
   p.n_a = n_tgt; p.n_b = n_est;

@@ -75,13 +75,7 @@ static int check_qual_args(const int32_t* tgt_len, int n_tgt, const int32_t* tgt
     return ssr_fail(SSR_ERR_INVALID_ARG, "which must be a non-empty combination of SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG");
   if (fs < SSR_QUAL_FS_MIN || fs > SSR_QUAL_FS_MAX) return ssr_fail(SSR_ERR_INVALID_ARG, "fs must be in [8000, 48000]");
   if (lpc_order < 0 || lpc_order > SSR_QUAL_PMAX) return ssr_fail(SSR_ERR_INVALID_ARG, "lpc_order must be 0 (default) or in [1, 32]");
-  if (n_tgt < 0 || n_est < 0) return ssr_fail(SSR_ERR_INVALID_ARG, "n_tgt and n_est must be >= 0");
-  if ((n_tgt > 0 && !tgt_len) || (n_est > 0 && !tgt_index)) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
-  for (int t = 0; t < n_tgt; ++t)
-    if (tgt_len[t] < 0) return ssr_fail(SSR_ERR_INVALID_ARG, "target lengths must be in [0, 2^31)");
-  for (int e = 0; e < n_est; ++e)
-    if (tgt_index[e] < 0 || tgt_index[e] >= n_tgt) return ssr_fail(SSR_ERR_INVALID_ARG, "tgt_index out of range");
-  return SSR_OK;
+  return ssr_check_pair_index(tgt_len, n_tgt, tgt_index, n_est, (int64_t)1 << 31, "target lengths must be in [0, 2^31)");
 }
 
 extern "C" size_t ssr_quality_metrics_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int fs,
@@ -105,9 +99,6 @@ extern "C" int ssr_quality_bands(int fs, int32_t* n_fft, double* cent, double* b
   return SSR_OK;
 }
 
-template <typename TT, typename TE> static void launch_lpc(const SsrQualParams& p, int64_t grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_qual_lpc<TT, TE>), dim3((unsigned)grid), dim3(64), 0, s, p);
-}
 template <typename TT, typename TE> static void launch_bands(const SsrQualParams& p, int64_t grid, int logn, hipStream_t s) {
   const dim3 g((unsigned)grid), b((unsigned)((1 << logn) / 8));
   if (logn == 9) hipLaunchKernelGGL((k_qual_bands<TT, TE, 9>), g, b, 0, s, p);
@@ -133,11 +124,8 @@ extern "C" int ssr_quality_metrics(const void* tgt, int tgt_f64, const int64_t* 
   hipStream_t s = (hipStream_t)stream;
   int32_t* len_dev = (int32_t*)(ws + w.off_len);
   int32_t* idx_dev = (int32_t*)(ws + w.off_idx);
-  // (host arrays: from page-locked memory these copies are asynchronous - the caller keeps them until the stream has passed;
-  // the tables are cached for the life of the process)
-  if (n_tgt) HIP_TRY(hipMemcpyAsync(len_dev, tgt_len, (size_t)n_tgt * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(idx_dev, tgt_index, (size_t)n_est * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  if (bands) {
+  if (int rc = ssr_upload_pair_index(tgt_len, n_tgt, tgt_index, n_est, len_dev, idx_dev, s)) return rc;
+  if (bands) {      // (the tables are cached for the life of the process: the caller need not keep them)
     HIP_TRY(hipMemcpyAsync(ws + w.off_tw, t.tw.data(), t.tw.size() * sizeof(cx<double>), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(ws + w.off_fw, t.packed.data(), t.packed.size() * sizeof(double), hipMemcpyHostToDevice, s));
   }
@@ -153,20 +141,17 @@ extern "C" int ssr_quality_metrics(const void* tgt, int tgt_f64, const int64_t* 
   p.val = (double*)(ws + w.off_val); p.n_val = w.pair_frames; p.out = out;
   hipLaunchKernelGGL(k_qual_geometry, dim3(1), dim3(SSR_QUAL_NT), 0, s, p);
   HIP_TRY(hipGetLastError());
-  const int kind = (tgt_f64 ? 2 : 0) + (est_f64 ? 1 : 0);
   if (lpc && w.run_frames > 0) {
-    if (kind == 0) launch_lpc<float, float>(p, w.run_frames, s);
-    else if (kind == 1) launch_lpc<float, double>(p, w.run_frames, s);
-    else if (kind == 2) launch_lpc<double, float>(p, w.run_frames, s);
-    else launch_lpc<double, double>(p, w.run_frames, s);
+    ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
+      hipLaunchKernelGGL((k_qual_lpc<decltype(tt), decltype(te)>), dim3((unsigned)w.run_frames), dim3(64), 0, s, p);
+    });
     HIP_TRY(hipGetLastError());
   }
   if (bands && w.run_frames > 0) {
     const int logn = ssr_qual_log2_nfft(fs);
-    if (kind == 0) launch_bands<float, float>(p, w.run_frames, logn, s);
-    else if (kind == 1) launch_bands<float, double>(p, w.run_frames, logn, s);
-    else if (kind == 2) launch_bands<double, float>(p, w.run_frames, logn, s);
-    else launch_bands<double, double>(p, w.run_frames, logn, s);
+    ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
+      launch_bands<decltype(tt), decltype(te)>(p, w.run_frames, logn, s);
+    });
     HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(k_qual_finalize, dim3((unsigned)n_est), dim3(SSR_QUAL_NT), 0, s, p);

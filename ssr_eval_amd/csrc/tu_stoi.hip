@@ -77,19 +77,13 @@ static StoiWs stoi_ws(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_inde
 
 // host-side validation: nothing is queued unless every length and index is usable
 static int check_stoi_args(const int32_t* tgt_len, int n_tgt, const int32_t* est_len, const int32_t* tgt_index, int n_est) {
-  if (n_tgt < 0 || n_est < 0) return ssr_fail(SSR_ERR_INVALID_ARG, "n_tgt and n_est must be >= 0");
-  for (int t = 0; t < n_tgt; ++t)
-    if (tgt_len[t] < 0 || tgt_len[t] >= (1 << 29)) return ssr_fail(SSR_ERR_INVALID_ARG, "target lengths must be in [0, 2^29)");
-  for (int e = 0; e < n_est; ++e) {
-    if (tgt_index[e] < 0 || tgt_index[e] >= n_tgt) return ssr_fail(SSR_ERR_INVALID_ARG, "tgt_index out of range");
-    if (est_len && est_len[e] != tgt_len[tgt_index[e]])
-      return ssr_fail(SSR_ERR_INVALID_ARG, "an estimate's length differs from its target's");
-  }
+  if (int rc = ssr_check_pair_index(tgt_len, n_tgt, tgt_index, n_est, 1 << 29, "target lengths must be in [0, 2^29)")) return rc;
+  for (int e = 0; est_len && e < n_est; ++e)
+    if (est_len[e] != tgt_len[tgt_index[e]]) return ssr_fail(SSR_ERR_INVALID_ARG, "an estimate's length differs from its target's");
   return SSR_OK;
 }
 
 extern "C" size_t ssr_stoi_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est) {
-  if ((n_tgt > 0 && !tgt_len) || (n_est > 0 && !tgt_index)) return 0;
   if (check_stoi_args(tgt_len, n_tgt, nullptr, tgt_index, n_est)) return 0;
   return stoi_ws(tgt_len, n_tgt, tgt_index, n_est).total;
 }
@@ -109,10 +103,8 @@ extern "C" int ssr_stoi(const double* tgt, const int64_t* tgt_off, const int32_t
   hipStream_t s = (hipStream_t)stream;
   int32_t* len_dev = (int32_t*)(ws + w.off_len);
   int32_t* idx_dev = (int32_t*)(ws + w.off_idx);
-  // (host arrays: from page-locked memory these copies are asynchronous - the caller keeps them until the stream has passed)
-  if (n_tgt) HIP_TRY(hipMemcpyAsync(len_dev, tgt_len, (size_t)n_tgt * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(len_dev + n_tgt, est_len, (size_t)n_est * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(idx_dev, tgt_index, (size_t)n_est * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (int rc = ssr_upload_pair_index(tgt_len, n_tgt, tgt_index, n_est, len_dev, idx_dev, s)) return rc;
+  HIP_TRY(hipMemcpyAsync(len_dev + n_tgt, est_len, (size_t)n_est * sizeof(int32_t), hipMemcpyHostToDevice, s));   // (as those two)
   SsrStoiParams p{};
   p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.len = len_dev; p.tgt_index = idx_dev;
   p.n_tgt = n_tgt; p.n_est = n_est; p.which = which;

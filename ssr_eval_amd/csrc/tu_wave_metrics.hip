@@ -59,26 +59,13 @@ static WaveWs wave_ws(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_inde
 static int check_wave_args(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int fs, int which) {
   if (which < 1 || which > 7) return ssr_fail(SSR_ERR_INVALID_ARG, "which must be a non-empty combination of SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR");
   if (fs <= 0) return ssr_fail(SSR_ERR_INVALID_ARG, "fs must be > 0");
-  if (n_tgt < 0 || n_est < 0) return ssr_fail(SSR_ERR_INVALID_ARG, "n_tgt and n_est must be >= 0");
-  if ((n_tgt > 0 && !tgt_len) || (n_est > 0 && !tgt_index)) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
-  for (int t = 0; t < n_tgt; ++t)
-    if (tgt_len[t] < 0) return ssr_fail(SSR_ERR_INVALID_ARG, "target lengths must be in [0, 2^31)");
-  for (int e = 0; e < n_est; ++e)
-    if (tgt_index[e] < 0 || tgt_index[e] >= n_tgt) return ssr_fail(SSR_ERR_INVALID_ARG, "tgt_index out of range");
-  return SSR_OK;
+  return ssr_check_pair_index(tgt_len, n_tgt, tgt_index, n_est, (int64_t)1 << 31, "target lengths must be in [0, 2^31)");
 }
 
 extern "C" size_t ssr_wave_metrics_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int fs,
                                                    int which) {
   if (check_wave_args(tgt_len, n_tgt, tgt_index, n_est, fs, which)) return 0;
   return wave_ws(tgt_len, n_tgt, tgt_index, n_est, fs, which).total;
-}
-
-template <typename TT, typename TE> static void launch_pass1(const SsrWaveParams& p, int64_t grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_wave_pass1<TT, TE>), dim3((unsigned)grid), dim3(SSR_WAVE_NT), 0, s, p);
-}
-template <typename TT, typename TE> static void launch_pass2(const SsrWaveParams& p, int64_t grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_wave_pass2<TT, TE>), dim3((unsigned)grid), dim3(SSR_WAVE_NT), 0, s, p);
 }
 
 extern "C" int ssr_wave_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt,
@@ -96,9 +83,7 @@ extern "C" int ssr_wave_metrics(const void* tgt, int tgt_f64, const int64_t* tgt
   hipStream_t s = (hipStream_t)stream;
   int32_t* len_dev = (int32_t*)(ws + w.off_len);
   int32_t* idx_dev = (int32_t*)(ws + w.off_idx);
-  // (host arrays: from page-locked memory these copies are asynchronous - the caller keeps them until the stream has passed)
-  if (n_tgt) HIP_TRY(hipMemcpyAsync(len_dev, tgt_len, (size_t)n_tgt * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(idx_dev, tgt_index, (size_t)n_est * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (int rc = ssr_upload_pair_index(tgt_len, n_tgt, tgt_index, n_est, len_dev, idx_dev, s)) return rc;
   SsrWaveParams p{};
   p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = len_dev; p.tgt_index = idx_dev;
   p.n_tgt = n_tgt; p.n_est = n_est; p.n_runs = w.n_runs; p.which = which; p.fs = fs;
@@ -110,22 +95,20 @@ extern "C" int ssr_wave_metrics(const void* tgt, int tgt_f64, const int64_t* tgt
   p.out = out;
   hipLaunchKernelGGL(k_wave_geometry, dim3(1), dim3(SSR_WAVE_NT), 0, s, p);
   HIP_TRY(hipGetLastError());
-  const int kind = (tgt_f64 ? 2 : 0) + (est_f64 ? 1 : 0);
+  const dim3 tiles((unsigned)w.run_tiles), nt(SSR_WAVE_NT);
   if (w.run_tiles > 0) {
-    if (kind == 0) launch_pass1<float, float>(p, w.run_tiles, s);
-    else if (kind == 1) launch_pass1<float, double>(p, w.run_tiles, s);
-    else if (kind == 2) launch_pass1<double, float>(p, w.run_tiles, s);
-    else launch_pass1<double, double>(p, w.run_tiles, s);
+    ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
+      hipLaunchKernelGGL((k_wave_pass1<decltype(tt), decltype(te)>), tiles, nt, 0, s, p);
+    });
     HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(k_wave_finalize1, dim3((unsigned)ssr_ceil_div(n_est, 256)), dim3(256), 0, s, p);
   HIP_TRY(hipGetLastError());
   if (which & SSR_WAVE_SI_SDR) {
     if (w.run_tiles > 0) {
-      if (kind == 0) launch_pass2<float, float>(p, w.run_tiles, s);
-      else if (kind == 1) launch_pass2<float, double>(p, w.run_tiles, s);
-      else if (kind == 2) launch_pass2<double, float>(p, w.run_tiles, s);
-      else launch_pass2<double, double>(p, w.run_tiles, s);
+      ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
+        hipLaunchKernelGGL((k_wave_pass2<decltype(tt), decltype(te)>), tiles, nt, 0, s, p);
+      });
       HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(k_wave_finalize2, dim3((unsigned)ssr_ceil_div(n_est, 256)), dim3(256), 0, s, p);

@@ -21,7 +21,7 @@ import torch
 from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
-from .metrics import AudioMetrics
+from .metrics import AudioMetrics, which_mask, _MEL_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
 from .utils import dict_mean, write_json
 
 # the reference's four, then the band-split LSD of SSR_Eval_Helper(lsd_split=...) and the intelligibility of
@@ -29,14 +29,57 @@ from .utils import dict_mean, write_json
 _METRIC_KEYS = ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi", "estoi")
 # SSR_Eval_Helper(stoi=...) -> AudioMetrics.stoi_* `extended`
 _STOI_OPTIONS = {"stoi": False, "estoi": True, "both": "both"}
-# the waveform metrics of SSR_Eval_Helper(waveform=...), after every key of _METRIC_KEYS (only present in runs that ask for them)
-_WAVEFORM_KEYS = ("snr", "si_sdr", "seg_snr")
-# the mel-spectrogram distances of SSR_Eval_Helper(mel=...), after the waveform metrics (only present in runs that ask for them)
-_MEL_KEYS = ("mel_lsd", "mel_l1", "mcd")
-# the objective quality measures of SSR_Eval_Helper(quality=...), after the mel distances (only present in runs that ask for them)
-_QUALITY_KEYS = ("llr", "cep_dist", "wss", "fwseg_snr")
-# the pitch metrics of SSR_Eval_Helper(pitch=...), after the quality measures (only present in runs that ask for them)
-_PITCH_KEYS = ("f0_rmse", "f0_corr", "gpe", "vde", "ffe")
+# the keys of SSR_Eval_Helper(waveform=...), (mel=...), (quality=...) and (pitch=...), in that order after every key of _METRIC_KEYS
+# (only present in runs that ask for them)
+_WAVEFORM_KEYS, _MEL_KEYS, _QUALITY_KEYS, _PITCH_KEYS = _WAVE_NAMES, _MEL_NAMES, _QUALITY_NAMES, _PITCH_NAMES
+
+
+def _option_dict(value):
+    """The dict form of a family option: True -> every metric, a name or a tuple of names -> those, a dict -> itself."""
+    return value if isinstance(value, dict) else {"which": "all" if value is True else value}
+
+
+def _which_option(option, value, names, entries):
+    """ValueError unless `value` is one of `names`, "all", a non-empty tuple of names, or a non-empty dict of 'which' and / or
+    `entries`; -> its dict form."""
+    if isinstance(value, dict) and (not value or set(value) - {"which", *entries}):
+        takes = ["'%s'" % k for k in ("which",) + tuple(entries)]
+        raise ValueError("a %s dict takes %s and / or %s" % (option, ", ".join(takes[:-1]), takes[-1]))
+    q = _option_dict(value)
+    w = q.get("which", "all")
+    if not (isinstance(w, str) or (isinstance(w, tuple) and w and all(isinstance(m, str) for m in w))):
+        raise ValueError("%s must be None, True, one of %s, a tuple of them or a dict" % (option, names))
+    which_mask(w, names)
+    return q
+
+
+def _mel_arguments(h, keys):
+    q = _option_dict(h.mel)
+    return (q.get("which", "all"),), {k: v for k, v in q.items() if k != "which"}
+
+
+def _quality_arguments(h, keys):
+    q = _option_dict(h.quality)
+    return (q.get("which", "all"), q.get("lpc_order")), {}
+
+
+def _pitch_arguments(h, keys):
+    q = _option_dict(h.pitch)
+    return (q.get("which", "all"), q.get("fmin", 50.0), q.get("fmax", 500.0)), {}
+
+
+# The optional metric families in the order they are queued on the stream and their keys appear in a result: (SSR_Eval_Helper
+# option, AudioMetrics method for K keys per file, method for a flat list of pairs, (helper, degradation keys of the call) -> the
+# (positional, keyword) arguments after the signals, whether those arguments hold one value per key - such a family takes the
+# multi path only when every file has the same keys).
+_FAMILIES = (
+    ("lsd_split", "lsd_split_multi", "lsd_split_batch", lambda h, keys: (([h.split_cutoff_hz(k) for k in keys],), {}), True),
+    ("stoi", "stoi_multi", "stoi_batch", lambda h, keys: ((_STOI_OPTIONS[h.stoi],), {}), False),
+    ("waveform", "waveform_multi", "waveform_batch", lambda h, keys: ((_option_dict(h.waveform)["which"],), {}), False),
+    ("mel", "mel_distance_multi", "mel_distance_batch", _mel_arguments, False),
+    ("quality", "quality_multi", "quality_batch", _quality_arguments, False),
+    ("pitch", "pitch_multi", "pitch_batch", _pitch_arguments, False),
+)
 
 
 def key_cutoff_hz(key):
@@ -133,35 +176,25 @@ class SSR_Eval_Helper:
         default 50 and 500)."""
         if pitch is not None:
             if pitch is not True:
-                pq = pitch if isinstance(pitch, dict) else {"which": pitch}
-                if isinstance(pitch, dict) and (not pitch or set(pitch) - {"which", "fmin", "fmax"}):
-                    raise ValueError("a pitch dict takes 'which', 'fmin' and / or 'fmax'")
-                wp = pq.get("which", "all")
-                if not (isinstance(wp, str) or (isinstance(wp, tuple) and wp and all(isinstance(m, str) for m in wp))):
-                    raise ValueError("pitch must be None, True, one of %s, a tuple of them or a dict" % (_PITCH_KEYS,))
-                AudioMetrics._pitch_which(wp)
+                pq = _which_option("pitch", pitch, _PITCH_KEYS, ("fmin", "fmax"))
                 AudioMetrics._pitch_range(pq.get("fmin", 50.0), pq.get("fmax", 500.0))
             if not 8000 <= evaluation_sr <= 48000:
                 raise ValueError("the pitch metrics need 8000 <= evaluation_sr <= 48000")
         self.pitch = pitch
         if quality is not None and quality is not True:
-            q = quality if isinstance(quality, dict) else {"which": quality}
-            if isinstance(quality, dict) and (not quality or set(quality) - {"which", "lpc_order"}):
-                raise ValueError("a quality dict takes 'which' and / or 'lpc_order'")
-            wq = q.get("which", "all")
-            if not (isinstance(wq, str) or (isinstance(wq, tuple) and wq and all(isinstance(m, str) for m in wq))):
-                raise ValueError("quality must be None, True, one of %s, a tuple of them or a dict" % (_QUALITY_KEYS,))
-            AudioMetrics._quality_which(wq)
-            AudioMetrics._quality_order(q.get("lpc_order"))
+            AudioMetrics._quality_order(_which_option("quality", quality, _QUALITY_KEYS, ("lpc_order",)).get("lpc_order"))
             if evaluation_sr < 8000:
                 raise ValueError("the quality measures need evaluation_sr >= 8000")
         self.quality = quality
         if not (mel is None or mel is True or isinstance(mel, dict)):
             raise ValueError("mel must be None, True or a dict of mel options")
-        names = (waveform,) if isinstance(waveform, str) else waveform
-        if not (waveform is None or waveform is True or (isinstance(names, tuple) and names
-                                                         and all(isinstance(m, str) and m in _WAVEFORM_KEYS for m in names))):
-            raise ValueError("waveform must be None, True, one of %s or a tuple of them" % (_WAVEFORM_KEYS,))
+        if waveform is not None and waveform is not True:
+            try:                                       # a name or a tuple of names: no "all", no list, no dict
+                ok = isinstance(waveform, (str, tuple)) and waveform != "all" and which_mask(waveform, _WAVEFORM_KEYS) > 0
+            except ValueError:
+                ok = False
+            if not ok:
+                raise ValueError("waveform must be None, True, one of %s or a tuple of them" % (_WAVEFORM_KEYS,))
         self.waveform = waveform
         if stoi is not None and not (isinstance(stoi, str) and stoi in _STOI_OPTIONS):
             raise ValueError("stoi must be None, 'stoi', 'estoi' or 'both'")
@@ -184,8 +217,8 @@ class SSR_Eval_Helper:
         self.audio_metrics = AudioMetrics(self.evaluationset_sr, precision=precision, device=device)
         self.mel = mel
         if isinstance(mel, dict):                      # every option checked here, not at the first batch
-            opts = {k: v for k, v in mel.items() if k != "which"}
-            self.audio_metrics._mel_which(mel.get("which", "all"))
+            (which,), opts = _mel_arguments(self, ())
+            which_mask(which, _MEL_KEYS)
             self.audio_metrics._mel_fb(**opts)
         self.unexpected_symbol_test_folder = "_.*#()_+=!@$%^&~"
         self._device = device
@@ -476,64 +509,22 @@ class SSR_Eval_Helper:
                 values = self.audio_metrics.evaluation_multi(by_key, [all_tgt[i * K] for i in range(len(items))], resident=True, deferred=True)
             else:
                 values = self.audio_metrics.evaluation_batch(all_proc, all_tgt, resident=True, deferred=True)
-        if all_proc and self.lsd_split is not None:
-            # the band-split LSD, queued behind the four metrics in the same deferred batch
-            cuts = [self.split_cutoff_hz(k) for k in all_keys]
-            if multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items))):
-                splits = self.audio_metrics.lsd_split_multi(by_key, [all_tgt[i * K] for i in range(len(items))], cuts[:K],
-                                                            resident=True, deferred=True)
-                flat_splits = lambda: [r for row in splits() for r in row]     # noqa: E731
-            else:
-                flat_splits = self.audio_metrics.lsd_split_batch(all_proc, all_tgt, cuts, resident=True, deferred=True)
-        if all_proc and self.stoi is not None:
-            # intelligibility, queued behind the band split in the same deferred batch; the multi path analyses each target once
-            ext = _STOI_OPTIONS[self.stoi]
-            if multi:
-                st = self.audio_metrics.stoi_multi(by_key, [all_tgt[i * K] for i in range(len(items))], ext, resident=True, deferred=True)
-                flat_stoi = lambda: [st_[k] for st_ in st() for k in range(K)]     # noqa: E731
-            else:
-                flat_stoi = self.audio_metrics.stoi_batch(all_proc, all_tgt, ext, resident=True, deferred=True)
-        if all_proc and self.waveform is not None:
-            # the waveform metrics, queued behind the intelligibility in the same deferred batch; the multi path reads each target
-            # tile once for its K estimates
-            wh = "all" if self.waveform is True else self.waveform
-            if multi:
-                wv = self.audio_metrics.waveform_multi(by_key, [all_tgt[i * K] for i in range(len(items))], wh, resident=True, deferred=True)
-                flat_wave = lambda: [w_[k] for w_ in wv() for k in range(K)]     # noqa: E731
-            else:
-                flat_wave = self.audio_metrics.waveform_batch(all_proc, all_tgt, wh, resident=True, deferred=True)
-        if all_proc and self.mel is not None:
-            # the mel distances, queued behind the waveform metrics in the same deferred batch
-            opts = {} if self.mel is True else {k: v for k, v in self.mel.items() if k != "which"}
-            mw = "all" if self.mel is True else self.mel.get("which", "all")
-            if multi:
-                mv = self.audio_metrics.mel_distance_multi(by_key, [all_tgt[i * K] for i in range(len(items))], mw, resident=True,
-                                                           deferred=True, **opts)
-                flat_mel = lambda: [m_[k] for m_ in mv() for k in range(K)]     # noqa: E731
-            else:
-                flat_mel = self.audio_metrics.mel_distance_batch(all_proc, all_tgt, mw, resident=True, deferred=True, **opts)
-        if all_proc and self.quality is not None:
-            # the quality measures, queued behind the mel distances in the same deferred batch; the multi path analyses each
-            # target's frames once for its K estimates
-            q = self.quality if isinstance(self.quality, dict) else {"which": "all" if self.quality is True else self.quality}
-            qw, qo = q.get("which", "all"), q.get("lpc_order")
-            if multi:
-                qv = self.audio_metrics.quality_multi(by_key, [all_tgt[i * K] for i in range(len(items))], qw, qo, resident=True,
-                                                      deferred=True)
-                flat_quality = lambda: [q_[k] for q_ in qv() for k in range(K)]     # noqa: E731
-            else:
-                flat_quality = self.audio_metrics.quality_batch(all_proc, all_tgt, qw, qo, resident=True, deferred=True)
-        if all_proc and self.pitch is not None:
-            # the pitch metrics, queued behind the quality measures in the same deferred batch; the multi path resamples and tracks
-            # each target once for its K estimates
-            pq = self.pitch if isinstance(self.pitch, dict) else {"which": "all" if self.pitch is True else self.pitch}
-            pw, pf = pq.get("which", "all"), (pq.get("fmin", 50.0), pq.get("fmax", 500.0))
-            if multi:
-                pv = self.audio_metrics.pitch_multi(by_key, [all_tgt[i * K] for i in range(len(items))], pw, *pf, resident=True,
-                                                    deferred=True)
-                flat_pitch = lambda: [p_[k] for p_ in pv() for k in range(K)]     # noqa: E731
-            else:
-                flat_pitch = self.audio_metrics.pitch_batch(all_proc, all_tgt, pw, *pf, resident=True, deferred=True)
+        # the optional families, queued behind the four metrics in the same deferred batch, in _FAMILIES' order; the multi path
+        # analyses each target once for its K estimates
+        queued = []
+        if all_proc:
+            same_keys = multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items)))
+            for option, multi_name, batch_name, arguments, per_key in _FAMILIES:
+                if getattr(self, option) is None:
+                    continue
+                if multi and (same_keys or not per_key):
+                    args, kw = arguments(self, all_keys[:K])
+                    rows = getattr(self.audio_metrics, multi_name)(by_key, [all_tgt[i * K] for i in range(len(items))], *args,
+                                                                   resident=True, deferred=True, **kw)
+                    queued.append(lambda rows=rows: [r for row in rows() for r in row])
+                else:
+                    args, kw = arguments(self, all_keys)
+                    queued.append(getattr(self.audio_metrics, batch_name)(all_proc, all_tgt, *args, resident=True, deferred=True, **kw))
         self._last_processed = None
         keep = list(zip(owner, all_keys, all_proc)) if self.save_processed_result else None
 
@@ -542,24 +533,9 @@ class SSR_Eval_Helper:
             if values is not None:
                 rows = values()
                 vals = [rows[i][k] for i in range(len(items)) for k in range(K)] if multi else rows
-                if self.lsd_split is not None:
-                    for v, sp in zip(vals, flat_splits()):
-                        v.update(sp)
-                if self.stoi is not None:
-                    for v, sv in zip(vals, flat_stoi()):
-                        v.update(sv)
-                if self.waveform is not None:
-                    for v, wv_ in zip(vals, flat_wave()):
-                        v.update(wv_)
-                if self.mel is not None:
-                    for v, mv_ in zip(vals, flat_mel()):
-                        v.update(mv_)
-                if self.quality is not None:
-                    for v, qv_ in zip(vals, flat_quality()):
-                        v.update(qv_)
-                if self.pitch is not None:
-                    for v, pv_ in zip(vals, flat_pitch()):
-                        v.update(pv_)
+                for flat in queued:
+                    for v, x in zip(vals, flat()):
+                        v.update(x)
                 for i, k, v, e in zip(owner, all_keys, vals, all_extra):
                     v.update(e)                                 # the testee's extra metrics last, as the reference's update
                     results[i][k] = v

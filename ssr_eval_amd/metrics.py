@@ -11,6 +11,8 @@ reference.  All arithmetic runs in libssrhip.so (HIP, gfx950):
 Extras (keyword-only, not in the reference): ``precision`` ("f64" parity mode / "f32"), ``device``,
 ``n_fft`` / ``hop_length`` overrides, and ``evaluation_batch`` for lists of pairs.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -23,6 +25,53 @@ _WAVE_NAMES = ("snr", "si_sdr", "seg_snr")        # SSR_WAVE_SNR, SSR_WAVE_SI_SD
 _MEL_NAMES = ("mel_lsd", "mel_l1", "mcd")         # SSR_MEL_LSD, SSR_MEL_L1, SSR_MEL_MCD: bits 0, 1, 2
 _QUALITY_NAMES = ("llr", "cep_dist", "wss", "fwseg_snr")   # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG: bits 0 .. 3
 _PITCH_NAMES = ("f0_rmse", "f0_corr", "gpe", "vde", "ffe")  # SSR_PITCH_F0_RMSE, _F0_CORR, _GPE, _VDE, _FFE: bits 0 .. 4
+
+
+def which_mask(which, names):
+    """"all", one of `names` or a tuple / list of them -> the C ABI's bit mask (bit j asks for names[j])."""
+    asked = names if (isinstance(which, str) and which == "all") else ((which,) if isinstance(which, str) else which)
+    if not isinstance(asked, (tuple, list)) or not asked or not all(isinstance(m, str) and m in names for m in asked):
+        raise ValueError("which must be 'all', one of %s or a tuple of them" % (names,))
+    return sum(1 << names.index(m) for m in set(asked))
+
+
+def rows_dicts(vals, mask, names, packed=True):
+    """Result rows -> one {name: float} per row with the names `mask` asks for.  packed: a row holds one column per name asked
+    for, in bit order; otherwise one column per name of `names` (NaN where not asked)."""
+    cols = [(j, m) for j, m in enumerate(names) if mask & (1 << j)]
+    return [{m: float(row[c if packed else j]) for c, (j, m) in enumerate(cols)} for row in vals]
+
+
+def _item_major(by_key, n, K):
+    """by_key[k][i] -> the flat list with the K entries of item i next to each other."""
+    return [by_key[k][i] for i in range(n) for k in range(K)]
+
+
+def _flat_pairs(ests_by_key, targets):
+    """K lists of n estimates, n targets -> (n * K estimates, n * K targets, n, K), the K pairs of a target next to each other."""
+    K, n = len(ests_by_key), len(targets)
+    return _item_major(ests_by_key, n, K), [t for t in targets for _ in range(K)], n, K
+
+
+def _regroup(flat, n, K, deferred):
+    """flat: a function that returns n * K item-major rows -> the n lists of K (deferred: the function that returns them)."""
+    def finish():
+        rows = flat()
+        return [rows[i * K:(i + 1) * K] for i in range(n)]
+    return finish if deferred else finish()
+
+
+def _shared_targets(targets):
+    """-> (the distinct target objects, the index of every entry among them): a target object passed for several pairs (at one
+    length) is analysed once."""
+    tgts, index, seen = [], [], {}
+    for t in targets:
+        key = (id(t), int(t.shape[0]))
+        if key not in seen:
+            seen[key] = len(tgts)
+            tgts.append(t)
+        index.append(seen[key])
+    return tgts, index
 
 
 class AudioMetrics:
@@ -117,10 +166,8 @@ class AudioMetrics:
         # a key is float64 / float32 if ALL its estimates are; a key with both kinds sends everything through evaluation_batch
         kinds = [{bool(B._is_f64(pairs[k][i][0])) for i in range(n)} for k in range(K)]
         if K < 2 or n == 0 or not same_len or not tgt32 or any(len(kd) != 1 for kd in kinds):
-            flat = self.evaluation_batch([ests_by_key[k][i] for i in range(n) for k in range(K)],
-                                         [targets[i] for i in range(n) for _ in range(K)], mask, resident, deferred=True)
-            finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
-            return finish if deferred else finish()
+            ests, tgts_, _, _ = _flat_pairs(ests_by_key, targets)
+            return _regroup(self.evaluation_batch(ests, tgts_, mask, resident, deferred=True), n, K, deferred)
         tgts = [pairs[0][i][1] for i in range(n)]
 
         def one_key(k):                                              # a group of ONE key: the plain pair path -> [n][1] dicts
@@ -226,11 +273,9 @@ class AudioMetrics:
         same_len = all(len({pairs[k][i][0].shape[0] for k in range(K)}) == 1 for i in range(n))
         kinds = [{bool(B._is_f64(pairs[k][i][0])) for i in range(n)} for k in range(K)]
         if n == 0 or not same_len or any(len(kd) != 1 for kd in kinds):
-            flat = self.lsd_split_batch([pairs[k][i][0] for i in range(n) for k in range(K)],
-                                        [pairs[k][i][1] for i in range(n) for k in range(K)],
-                                        [cutoffs_hz[k] for _ in range(n) for k in range(K)], True, deferred=True)
-            finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
-            return finish if deferred else finish()
+            flat = _item_major(pairs, n, K)
+            return _regroup(self.lsd_split_batch([e for e, _ in flat], [t for _, t in flat], list(cutoffs_hz) * n, True, deferred=True),
+                            n, K, deferred)
         tgts = [pairs[0][i][1] for i in range(n)]
         split = [self._split_edges(c) for c in cutoffs_hz]
         groups = {}
@@ -251,7 +296,44 @@ class AudioMetrics:
             return out
         return finish if deferred else finish()
 
-    # ---- STOI / ESTOI (not in the reference): intelligibility as pystoi computes it, at self.rate
+    # ---- the per-pair metric families (not in the reference): estimate e against target index[e].  A family is two functions -
+    # call(tgts, ests, index) queues its backend call and returns the Pending, dicts(rows) names the columns - and the drivers
+    # below are the same for all of them
+    def _pairs(self, family, ests, targets, resident, deferred, by_dtype):
+        """Lists of pairs with evaluation_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals).  by_dtype:
+        one call per (target dtype, estimate dtype) group - the family reads the signals in their own dtype; otherwise one call
+        (it widens them itself).  A target object passed for several pairs of a call appears once in it."""
+        call, dicts = family
+        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
+        groups = {}
+        for i, (e, t) in enumerate(pairs):
+            groups.setdefault((bool(B._is_f64(t)), bool(B._is_f64(e))) if by_dtype else None, []).append(i)
+        pending = []
+        for idx in groups.values():
+            tgts, index = _shared_targets([pairs[i][1] for i in idx])
+            pending.append((idx, call(tgts, [pairs[i][0] for i in idx], index)))
+
+        def finish():
+            out = [None] * len(pairs)
+            for idx, p in pending:
+                for i, d in zip(idx, dicts(p())):
+                    out[i] = d
+            return out
+        return finish if deferred else finish()
+
+    def _multi_shared(self, family, ests_by_key, targets, resident, deferred):
+        """K estimates per target, as evaluation_multi, in ONE call that names each target once for its K estimates."""
+        call, dicts = family
+        K, n = len(ests_by_key), len(targets)
+        pairs = [self._prepare_pair(ests_by_key[k][i], targets[i], resident) for i in range(n) for k in range(K)]
+        ests, tgts = [e for e, _ in pairs], [t for _, t in pairs]
+        if not all(len({t.shape[0] for t in tgts[i * K:(i + 1) * K]}) == 1 for i in range(n)):
+            # truncation cut a target differently per key: one target copy per length
+            return _regroup(self._pairs(family, ests, tgts, True, True, by_dtype=False), n, K, deferred)
+        pending = call(tgts[::K] if K else [], ests, np.repeat(np.arange(n), K))
+        return _regroup(lambda: dicts(pending()), n, K, deferred)
+
+    # ---- STOI / ESTOI: intelligibility as pystoi computes it (DESIGN §9), at self.rate
     @staticmethod
     def _stoi_which(extended):
         if extended is False or extended is True:
@@ -260,10 +342,11 @@ class AudioMetrics:
             return B._lib.STOI_BOTH
         raise ValueError("extended must be False (STOI), True (ESTOI) or 'both'")
 
-    @staticmethod
-    def _stoi_dicts(vals, which):
+    def _stoi_family(self, extended):
+        which = self._stoi_which(extended)
         names = {B._lib.STOI: ("stoi",), B._lib.ESTOI: ("estoi",), B._lib.STOI_BOTH: ("stoi", "estoi")}[which]
-        return [{k: float(v) for k, v in zip(names, row)} for row in vals]
+        return (lambda tgts, ests, index: B.stoi(tgts, ests, index, self.rate, which, self._device, deferred=True),
+                lambda vals: [{k: float(v) for k, v in zip(names, row)} for row in vals])
 
     def stoi(self, est, target, extended=False):
         """STOI (extended=False), ESTOI (True) of one (estimate, target) pair at self.rate; 'both': {'stoi', 'estoi'}."""
@@ -274,53 +357,21 @@ class AudioMetrics:
         """{'stoi'} / {'estoi'} / both for lists of pairs, with evaluation_batch's input rules (metrics.py:89-90 truncation; float32
         or float64 signals - resampled to 10 kHz in float64 either way).  A target object passed for several pairs is analysed once.
         deferred: as evaluation_batch."""
-        which = self._stoi_which(extended)
-        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
-        tgts, index, seen = [], [], {}
-        for e, t in pairs:
-            key = (id(t), int(t.shape[0]))
-            if key not in seen:
-                seen[key] = len(tgts)
-                tgts.append(t)
-            index.append(seen[key])
-        pending = B.stoi(tgts, [e for e, _ in pairs], index, self.rate, which, self._device, deferred=True)
-        finish = lambda: self._stoi_dicts(pending(), which)      # noqa: E731
-        return finish if deferred else finish()
+        return self._pairs(self._stoi_family(extended), ests, targets, resident, deferred, by_dtype=False)
 
     def stoi_multi(self, ests_by_key, targets, extended=False, resident=False, deferred=False):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  Each target is resampled, masked and transformed once for its K estimates."""
-        which = self._stoi_which(extended)
-        K, n = len(ests_by_key), len(targets)
-        pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for k in range(K)] for i in range(n)]
-        same_len = all(len({pairs[i][k][1].shape[0] for k in range(K)}) == 1 for i in range(n))
-        if not same_len:                      # truncation cut a target differently per key: one target copy per length
-            flat = self.stoi_batch([pairs[i][k][0] for i in range(n) for k in range(K)],
-                                   [pairs[i][k][1] for i in range(n) for k in range(K)], extended, True, deferred=True)
-            finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
-            return finish if deferred else finish()
-        tgts = [pairs[i][0][1] if K else targets[i] for i in range(n)]
-        pending = B.stoi(tgts, [pairs[i][k][0] for i in range(n) for k in range(K)], np.repeat(np.arange(n), K), self.rate, which,
-                         self._device, deferred=True)
+        return self._multi_shared(self._stoi_family(extended), ests_by_key, targets, resident, deferred)
 
-        def finish():
-            rows = self._stoi_dicts(pending(), which)
-            return [rows[i * K:(i + 1) * K] for i in range(n)]
-        return finish if deferred else finish()
+    # ---- waveform metrics: SNR, SI-SDR, segmental SNR (DESIGN §10), at self.rate
+    _wave_which = staticmethod(functools.partial(which_mask, names=_WAVE_NAMES))
+    _wave_dicts = staticmethod(functools.partial(rows_dicts, names=_WAVE_NAMES))
 
-    # ---- waveform metrics (not in the reference): SNR, SI-SDR, segmental SNR (DESIGN §10), at self.rate
-    @staticmethod
-    def _wave_which(which):
-        """"all", one of _WAVE_NAMES or a tuple / list of them -> the SSR_WAVE_* bit mask."""
-        names = _WAVE_NAMES if (isinstance(which, str) and which == "all") else ((which,) if isinstance(which, str) else which)
-        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(m, str) and m in _WAVE_NAMES for m in names):
-            raise ValueError("which must be 'all', one of %s or a tuple of them" % (_WAVE_NAMES,))
-        return sum(1 << _WAVE_NAMES.index(m) for m in set(names))
-
-    @staticmethod
-    def _wave_dicts(vals, mask):
-        names = [m for j, m in enumerate(_WAVE_NAMES) if mask & (1 << j)]
-        return [{k: float(v) for k, v in zip(names, row)} for row in vals]
+    def _wave_family(self, which):
+        mask = self._wave_which(which)
+        return (lambda tgts, ests, index: B.wave_metrics(tgts, ests, index, self.rate, mask, self._device, deferred=True),
+                lambda vals: self._wave_dicts(vals, mask))
 
     def waveform(self, est, target, which="all"):
         """{'snr', 'si_sdr', 'seg_snr'} (or the subset `which` names) of one (estimate, target) pair, in dB."""
@@ -339,50 +390,19 @@ class AudioMetrics:
         """waveform() for lists of pairs, with stoi_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals, read
         in their own dtype: one ssr_wave_metrics call per (target dtype, estimate dtype) group).  A target object passed for several
         pairs is read once for all of them.  deferred: as evaluation_batch."""
-        mask = self._wave_which(which)
-        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
-        groups = {}
-        for i, (e, t) in enumerate(pairs):
-            groups.setdefault((bool(B._is_f64(t)), bool(B._is_f64(e))), []).append(i)
-        pending = []
-        for idx in groups.values():
-            tgts, index, seen = [], [], {}
-            for i in idx:
-                t = pairs[i][1]
-                key = (id(t), int(t.shape[0]))
-                if key not in seen:
-                    seen[key] = len(tgts)
-                    tgts.append(t)
-                index.append(seen[key])
-            pending.append((idx, B.wave_metrics(tgts, [pairs[i][0] for i in idx], index, self.rate, mask, self._device, deferred=True)))
-
-        def finish():
-            out = [None] * len(pairs)
-            for idx, p in pending:
-                for i, d in zip(idx, self._wave_dicts(p(), mask)):
-                    out[i] = d
-            return out
-        return finish if deferred else finish()
+        return self._pairs(self._wave_family(which), ests, targets, resident, deferred, by_dtype=True)
 
     def waveform_multi(self, ests_by_key, targets, which="all", resident=False, deferred=False):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  The K pairs of a target sit next to each other in one call: each tile of the target is read once for all of them."""
-        K, n = len(ests_by_key), len(targets)
-        flat = self.waveform_batch([ests_by_key[k][i] for i in range(n) for k in range(K)], [targets[i] for i in range(n) for _ in range(K)],
-                                   which, resident, deferred=True)
-        finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
-        return finish if deferred else finish()
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        return _regroup(self.waveform_batch(ests, tgts, which, resident, deferred=True), n, K, deferred)
 
-    # ---- objective quality measures (not in the reference; DESIGN §12): Loizou's LLR, LPC cepstral distance, WSS and fwSNRseg at
-    # self.rate.  WSS and fwSNRseg look at Loizou's 25 critical bands only, 50 Hz to about 3.9 kHz at every rate: they score the
-    # band a model was given, not the band it restored.
-    @staticmethod
-    def _quality_which(which):
-        """"all", one of _QUALITY_NAMES or a tuple / list of them -> the SSR_QUAL_* bit mask."""
-        names = _QUALITY_NAMES if (isinstance(which, str) and which == "all") else ((which,) if isinstance(which, str) else which)
-        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(m, str) and m in _QUALITY_NAMES for m in names):
-            raise ValueError("which must be 'all', one of %s or a tuple of them" % (_QUALITY_NAMES,))
-        return sum(1 << _QUALITY_NAMES.index(m) for m in set(names))
+    # ---- objective quality measures (DESIGN §12): Loizou's LLR, LPC cepstral distance, WSS and fwSNRseg at self.rate.  WSS and
+    # fwSNRseg look at Loizou's 25 critical bands only, 50 Hz to about 3.9 kHz at every rate: they score the band a model was
+    # given, not the band it restored.
+    _quality_which = staticmethod(functools.partial(which_mask, names=_QUALITY_NAMES))
+    _quality_dicts = staticmethod(functools.partial(rows_dicts, names=_QUALITY_NAMES))
 
     @staticmethod
     def _quality_order(lpc_order):
@@ -393,10 +413,12 @@ class AudioMetrics:
             raise ValueError("lpc_order must be None or an integer in [1, 32]")
         return int(lpc_order)
 
-    @staticmethod
-    def _quality_dicts(vals, mask):
-        names = [m for j, m in enumerate(_QUALITY_NAMES) if mask & (1 << j)]
-        return [{k: float(v) for k, v in zip(names, row)} for row in vals]
+    def _quality_family(self, which, lpc_order):
+        mask, order = self._quality_which(which), self._quality_order(lpc_order)
+        if not 8000 <= self.rate <= 48000:
+            raise ValueError("the quality measures need 8000 <= rate <= 48000")
+        return (lambda tgts, ests, index: B.quality_metrics(tgts, ests, index, self.rate, mask, order, self._device, deferred=True),
+                lambda vals: self._quality_dicts(vals, mask))
 
     def quality(self, est, target, which="all", lpc_order=None):
         """{'llr', 'cep_dist', 'wss', 'fwseg_snr'} (or the subset `which` names) of one (estimate, target) pair."""
@@ -418,52 +440,18 @@ class AudioMetrics:
         """quality() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals,
         read in their own dtype: one ssr_quality_metrics call per (target dtype, estimate dtype) group).  A target object passed for
         several pairs is analysed once for all of them.  deferred: as evaluation_batch."""
-        mask, order = self._quality_which(which), self._quality_order(lpc_order)
-        if not 8000 <= self.rate <= 48000:
-            raise ValueError("the quality measures need 8000 <= rate <= 48000")
-        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
-        groups = {}
-        for i, (e, t) in enumerate(pairs):
-            groups.setdefault((bool(B._is_f64(t)), bool(B._is_f64(e))), []).append(i)
-        pending = []
-        for idx in groups.values():
-            tgts, index, seen = [], [], {}
-            for i in idx:
-                t = pairs[i][1]
-                key = (id(t), int(t.shape[0]))
-                if key not in seen:
-                    seen[key] = len(tgts)
-                    tgts.append(t)
-                index.append(seen[key])
-            pending.append((idx, B.quality_metrics(tgts, [pairs[i][0] for i in idx], index, self.rate, mask, order, self._device,
-                                                   deferred=True)))
-
-        def finish():
-            out = [None] * len(pairs)
-            for idx, p in pending:
-                for i, d in zip(idx, self._quality_dicts(p(), mask)):
-                    out[i] = d
-            return out
-        return finish if deferred else finish()
+        return self._pairs(self._quality_family(which, lpc_order), ests, targets, resident, deferred, by_dtype=True)
 
     def quality_multi(self, ests_by_key, targets, which="all", lpc_order=None, resident=False, deferred=False):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  The K pairs of a target sit next to each other in one call: the target's frames are analysed once for all of them."""
-        K, n = len(ests_by_key), len(targets)
-        flat = self.quality_batch([ests_by_key[k][i] for i in range(n) for k in range(K)], [targets[i] for i in range(n) for _ in range(K)],
-                                  which, lpc_order, resident, deferred=True)
-        finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
-        return finish if deferred else finish()
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        return _regroup(self.quality_batch(ests, tgts, which, lpc_order, resident, deferred=True), n, K, deferred)
 
-    # ---- pitch (not in the reference; DESIGN §13): YIN F0 tracks on 16 kHz float64 signals, 10 ms frames, and the pair statistics
-    # F0 RMSE (cents), F0 correlation, GPE, VDE and FFE of an estimate's track against its target's
-    @staticmethod
-    def _pitch_which(which):
-        """"all", one of _PITCH_NAMES or a tuple / list of them -> the SSR_PITCH_* bit mask."""
-        names = _PITCH_NAMES if (isinstance(which, str) and which == "all") else ((which,) if isinstance(which, str) else which)
-        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(m, str) and m in _PITCH_NAMES for m in names):
-            raise ValueError("which must be 'all', one of %s or a tuple of them" % (_PITCH_NAMES,))
-        return sum(1 << _PITCH_NAMES.index(m) for m in set(names))
+    # ---- pitch (DESIGN §13): YIN F0 tracks on 16 kHz float64 signals, 10 ms frames, and the pair statistics F0 RMSE (cents), F0
+    # correlation, GPE, VDE and FFE of an estimate's track against its target's
+    _pitch_which = staticmethod(functools.partial(which_mask, names=_PITCH_NAMES))
+    _pitch_dicts = staticmethod(functools.partial(rows_dicts, names=_PITCH_NAMES))
 
     @staticmethod
     def _pitch_range(fmin, fmax):
@@ -477,10 +465,12 @@ class AudioMetrics:
         if not 8000 <= self.rate <= 48000:
             raise ValueError("the pitch metrics need 8000 <= rate <= 48000")
 
-    @staticmethod
-    def _pitch_dicts(vals, mask):
-        names = [m for j, m in enumerate(_PITCH_NAMES) if mask & (1 << j)]
-        return [{k: float(v) for k, v in zip(names, row)} for row in vals]
+    def _pitch_family(self, which, fmin, fmax):
+        mask = self._pitch_which(which)
+        fmin, fmax = self._pitch_range(fmin, fmax)
+        self._pitch_rate()
+        return (lambda tgts, ests, index: B.pitch_metrics(tgts, ests, index, self.rate, mask, fmin, fmax, self._device, deferred=True),
+                lambda vals: self._pitch_dicts(vals, mask))
 
     def f0(self, wav, fmin=50.0, fmax=500.0):
         """YIN F0 track of one waveform at self.rate: {'f0' (Hz, NaN where the frame is digitally silent), 'voiced' (bool),
@@ -498,43 +488,12 @@ class AudioMetrics:
         """pitch() for lists of pairs, with stoi_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals -
         resampled to 16 kHz in float64 either way).  A target object passed for several pairs is tracked once.  deferred: as
         evaluation_batch."""
-        mask = self._pitch_which(which)
-        fmin, fmax = self._pitch_range(fmin, fmax)
-        self._pitch_rate()
-        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
-        tgts, index, seen = [], [], {}
-        for e, t in pairs:
-            key = (id(t), int(t.shape[0]))
-            if key not in seen:
-                seen[key] = len(tgts)
-                tgts.append(t)
-            index.append(seen[key])
-        pending = B.pitch_metrics(tgts, [e for e, _ in pairs], index, self.rate, mask, fmin, fmax, self._device, deferred=True)
-        finish = lambda: self._pitch_dicts(pending(), mask)      # noqa: E731
-        return finish if deferred else finish()
+        return self._pairs(self._pitch_family(which, fmin, fmax), ests, targets, resident, deferred, by_dtype=False)
 
     def pitch_multi(self, ests_by_key, targets, which="all", fmin=50.0, fmax=500.0, resident=False, deferred=False):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  Each target is resampled and tracked once for its K estimates."""
-        mask = self._pitch_which(which)
-        fmin, fmax = self._pitch_range(fmin, fmax)
-        self._pitch_rate()
-        K, n = len(ests_by_key), len(targets)
-        pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for k in range(K)] for i in range(n)]
-        same_len = all(len({pairs[i][k][1].shape[0] for k in range(K)}) == 1 for i in range(n))
-        if not same_len:                      # truncation cut a target differently per key: one target copy per length
-            flat = self.pitch_batch([pairs[i][k][0] for i in range(n) for k in range(K)],
-                                    [pairs[i][k][1] for i in range(n) for k in range(K)], which, fmin, fmax, True, deferred=True)
-            finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
-            return finish if deferred else finish()
-        tgts = [pairs[i][0][1] if K else targets[i] for i in range(n)]
-        pending = B.pitch_metrics(tgts, [pairs[i][k][0] for i in range(n) for k in range(K)], np.repeat(np.arange(n), K), self.rate,
-                                  mask, fmin, fmax, self._device, deferred=True)
-
-        def finish():
-            rows = self._pitch_dicts(pending(), mask)
-            return [rows[i * K:(i + 1) * K] for i in range(n)]
-        return finish if deferred else finish()
+        return self._multi_shared(self._pitch_family(which, fmin, fmax), ests_by_key, targets, resident, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
@@ -566,17 +525,11 @@ class AudioMetrics:
             AudioMetrics._fb_cache[key] = fb
         return fb, n_cep
 
-    @staticmethod
-    def _mel_which(which):
-        """"all", one of _MEL_NAMES or a tuple / list of them -> the SSR_MEL_* bit mask."""
-        names = _MEL_NAMES if (isinstance(which, str) and which == "all") else ((which,) if isinstance(which, str) else which)
-        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(m, str) and m in _MEL_NAMES for m in names):
-            raise ValueError("which must be 'all', one of %s or a tuple of them" % (_MEL_NAMES,))
-        return sum(1 << _MEL_NAMES.index(m) for m in set(names))
+    _mel_which = staticmethod(functools.partial(which_mask, names=_MEL_NAMES))
 
     @staticmethod
     def _mel_dict(row, mask):
-        return {m: float(row[j]) for j, m in enumerate(_MEL_NAMES) if mask & (1 << j)}
+        return rows_dicts([row], mask, _MEL_NAMES, packed=False)[0]      # the library writes all three columns, NaN where not asked
 
     def mel_spectrogram(self, wav, keep_on_device=False, **mel):
         """[n] waveform -> mel spectrogram [1, 1, T, n_mels] float32: wav_to_spectrogram's magnitude image times the filterbank."""
@@ -621,10 +574,9 @@ class AudioMetrics:
         same_len = all(len({pairs[k][i][0].shape[0] for k in range(K)}) == 1 for i in range(n))
         kinds = [{bool(B._is_f64(pairs[k][i][0])) for i in range(n)} for k in range(K)]
         if n == 0 or not same_len or any(len(kd) != 1 for kd in kinds):
-            flat = self.mel_distance_batch([pairs[k][i][0] for i in range(n) for k in range(K)],
-                                           [pairs[k][i][1] for i in range(n) for k in range(K)], which, True, deferred=True, **mel)
-            finish = lambda: (lambda rows: [rows[i * K:(i + 1) * K] for i in range(n)])(flat())    # noqa: E731
-            return finish if deferred else finish()
+            flat = _item_major(pairs, n, K)
+            return _regroup(self.mel_distance_batch([e for e, _ in flat], [t for _, t in flat], which, True, deferred=True, **mel),
+                            n, K, deferred)
         tgts = [pairs[0][i][1] for i in range(n)]
         groups = {}
         for k in range(K):

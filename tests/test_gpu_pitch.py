@@ -181,7 +181,8 @@ def test_bits_alone_in_a_batch_multi_and_repeat():
 def test_evaluate_with_pitch_from_wav_files(tmp_path, monkeypatch):
     """SSR_Eval_Helper(pitch=True).evaluate() on a small wav tree (identity testee, two FFT keys and two IIR keys: float32 and
     float64 estimates, 44.1 kHz): the per-file values are AudioMetrics.pitch on the same estimates, the earlier metrics are those of a
-    run without the option, bit for bit, pitch=None is that run, and the pitch metrics come last in the metric order."""
+    run without the option, bit for bit, pitch=None is that run, and the pitch metrics come last in the metric order.  With all six
+    optional families on, the keys of a result come in the order the families run and the pitch values are the pitch=True run's bits."""
     from ssr_eval_amd import SSR_Eval_Helper, BasicTestee, AudioMetrics
     from ssr_eval_amd.io import write_wav, read_audio
     from ssr_eval_amd.lowpass import lowpass
@@ -225,3 +226,13 @@ def test_evaluate_with_pitch_from_wav_files(tmp_path, monkeypatch):
     sub = run(pitch={"which": ("vde", "f0_rmse"), "fmin": 60.0}, waveform=("snr",))
     fn = next(iter(sub["p360"]))
     assert list(sub["p360"][fn]["proc_fft_8000_44100"])[-3:] == ["snr", "f0_rmse", "vde"]
+    # every optional family at once: the result keys in the order the families run, the pitch values those of the pitch=True run
+    full = run(lsd_split=True, stoi="both", waveform=True, mel=True, quality=True, pitch=True)
+    order = ["lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi", "estoi", "snr", "si_sdr", "seg_snr", "mel_lsd", "mel_l1",
+             "mcd", "llr", "cep_dist", "wss", "fwseg_snr", "f0_rmse", "f0_corr", "gpe", "vde", "ffe"]
+    for spk in counts:
+        for fn in res[spk]:
+            for key in keys:
+                got = full[spk][fn][key]
+                assert list(got) == order
+                assert np.array([got[m] for m in NAMES]).tobytes() == np.array([res[spk][fn][key][m] for m in NAMES]).tobytes()
