@@ -593,6 +593,33 @@ int ssr_sosfiltfilt_multi(const float* x, const int64_t* off, const int32_t* len
                           const double* sos, const double* zi, const int32_t* n_sections, const int32_t* edge, int n_designs,
                           double* y, int64_t y_stride, void* workspace, size_t workspace_bytes, void* stream);
 
+/* N1-fast.  The same n_designs filters over one batch PARALLEL IN TIME - the opt-in second arithmetic of the IIR keys
+ * (backend.sosfiltfilt_multi(exact=False), SSR_Eval_Helper(iir_exact=False)); ssr_sosfiltfilt_multi stays the default everywhere.
+ * Method (ssr_iir_pit.h): the cascade of S sections is one linear system with 2S states, so every utterance's odd-extended signal is
+ * cut into segments of 128 samples, counted from its first extended sample, that run side by side - one lane per (design, utterance,
+ * segment) filters its segment from the zero state; a short scan per (design, utterance) hands the states on,
+ * z_in[k+1] = z_end[k] + M z_in[k], from SciPy's zi * ext[0]; the zero-input response H[n mod 128] z_in[n / 128] is added in a fixed
+ * order where the backward pass reads the forward output; the backward pass does the same over the same segments downwards from
+ * zi * fwd[-1], its second sweep starting every segment from its handed-on state and writing y once.  H (128 x 2S) and M (2S x 2S)
+ * are built on the device by this call, on `stream`, inside `workspace`: no allocation, no host synchronisation.
+ * Accuracy contract: float64 throughout, max|y - scipy.signal.sosfiltfilt| <= 1e-10 max|scipy| per signal (measured: below 1e-12 for
+ * butter / cheby1 / ellip / bessel of order 2-10 at 1-12 kHz, fs 44.1 kHz) - NOT SciPy's bits: the sums are re-associated across
+ * segments and multiply-adds may be fused.  No atomics and no order that depends on the launch: two calls give the same bits, and a
+ * signal alone gives the same bits as inside a batch or beside other designs.
+ * Arguments as ssr_sosfiltfilt_multi's (sos [n_designs][8][6], zi [n_designs][8][2] DEVICE; n_sections, edge HOST; n_sections <= 8,
+ * n_designs <= 48, every item len > edge, items back to back or apart but not overlapping), the same error codes for the same
+ * argument faults, returned before any launch.  ONE RESTRICTION ssr_sosfiltfilt_multi DOES NOT MAKE: off[] must ascend with the item
+ * index (what Ragged packs) - the segment-to-item map is a binary search over it, and it is on the device where this call cannot
+ * check it: descending or shuffled offsets give wrong output, not an error.  A batch with items needs total_len > 0
+ * (SSR_ERR_INVALID_ARG).  _f64: float64 signals (extended and filtered as float64). */
+size_t ssr_sosfiltfilt_fast_workspace_bytes(int64_t total_len, int n_items, const int32_t* edge, int n_designs);
+int ssr_sosfiltfilt_fast(const float* x, const int64_t* off, const int32_t* len, int n_items, int64_t total_len,
+                         const double* sos, const double* zi, const int32_t* n_sections, const int32_t* edge, int n_designs,
+                         double* y, int64_t y_stride, void* workspace, size_t workspace_bytes, void* stream);
+int ssr_sosfiltfilt_fast_f64(const double* x, const int64_t* off, const int32_t* len, int n_items, int64_t total_len,
+                             const double* sos, const double* zi, const int32_t* n_sections, const int32_t* edge, int n_designs,
+                             double* y, int64_t y_stride, void* workspace, size_t workspace_bytes, void* stream);
+
 /* A12 / SURVEY 8(e).  The path's one collective: the per-speaker [metric sums ..., count] buffer summed over ranks in
  * float64 (what SSR_Eval_Helper.evaluate's mean-of-speaker-means needs from the other shards, ssr_eval/eval.py:200-216) -
  * ncclAllReduce(sum, double) over RCCL / xGMI, in place, on `stream`.  RCCL is resolved with dlopen at the first call

@@ -1679,10 +1679,15 @@ def upload_decoded(raw, device=None):
     return out
 
 
-def sosfiltfilt(sos, wavs, device=None):
+def sosfiltfilt(sos, wavs, device=None, exact=True):
     """scipy.signal.sosfiltfilt(sos, x) for a list of float32 (or float64) waveforms on the GPU (N1); float64 tensors out.
-    The section coefficients and sosfilt_zi come from SciPy on the host (filter design, as in the reference)."""
+    The section coefficients and sosfilt_zi come from SciPy on the host (filter design, as in the reference).
+    exact=True: SciPy's bits.  exact=False: the segment-parallel kernel (ssr_sosfiltfilt_fast: the same filter evaluated parallel in
+    time, within 1e-10 of each signal's peak of SciPy's result, not its bits; the same bits as this design's slot of
+    sosfiltfilt_multi(exact=False)); a design of more than 8 sections takes the exact kernel whatever `exact` says."""
     from scipy.signal import sosfilt_zi
+    if not exact and np.ndim(sos) == 2 and np.shape(sos)[0] <= SOS_FAST_MAX_SECTIONS:
+        return sosfiltfilt_multi([sos], wavs, device, exact=False)[0]
     dev = torch.device(device) if device is not None else default_device()
     sos = np.ascontiguousarray(sos, dtype=np.float64)
     if sos.ndim != 2 or sos.shape[1] != 6:
@@ -1714,6 +1719,7 @@ def _sos_edge(sos):
     return 3 * ntaps
 
 
+SOS_FAST_MAX_SECTIONS = 8                                        # ssr_sosfiltfilt_fast's limit
 SOS_MULTI_MAX_DESIGNS = 48                                       # designs per launch (the C ABI's limit)
 # Output doubles per launch.  A launch lasts as long as its LONGEST utterance (a serial recurrence, ~195 cycles per sample step) whatever
 # the number of (design, utterance) recurrences beside it, until the chip's wave slots are full (4 recurrences per wave, ~2.5 waves per
@@ -1723,12 +1729,16 @@ SOS_MULTI_MAX_DESIGNS = 48                                       # designs per l
 SOS_MULTI_MAX_DOUBLES = int(os.environ.get("SSR_SOS_MULTI_MAX_DOUBLES", 1 << 31))
 
 
-def sosfiltfilt_multi(sos_list, wavs, device=None):
+def sosfiltfilt_multi(sos_list, wavs, device=None, exact=True):
     """scipy.signal.sosfiltfilt(sos, x) for EVERY design of sos_list over one list of float32 waveforms: ssr_sosfiltfilt_multi, the
     designs side by side in one launch (a launch is latency-bound - the recurrence is serial in time - and fills an eighth of a wave
     per utterance: one design after the other costs the same latency each time).  -> [design][signal] float64 device tensors, every one
-    bit-identical to sosfiltfilt(sos, ...).  Designs of more than 8 sections and float64 signals go through sosfiltfilt()."""
-    from scipy.signal import sosfilt_zi
+    bit-identical to sosfiltfilt(sos, ...).  Designs of more than 8 sections and float64 signals go through sosfiltfilt().
+    exact=False: ssr_sosfiltfilt_fast / _f64 instead - every design evaluated parallel in time (segments of the signal side by side,
+    their states handed on by a short scan), float32 and float64 signals alike, designs chunked per launch the same way.  The
+    result is within 1e-10 of each signal's peak of SciPy's, NOT its bits; it is deterministic and does not depend on what a signal
+    is batched with.  A design of more than 8 sections (a band-pass of order > 8) falls back to the exact kernel - the only
+    fallback: a Ragged of views with gaps (not `packed`) raises ValueError."""
     dev = torch.device(device) if device is not None else default_device()
     sos_list = [np.ascontiguousarray(s_, dtype=np.float64) for s_ in sos_list]
     for s_ in sos_list:
@@ -1740,37 +1750,64 @@ def sosfiltfilt_multi(sos_list, wavs, device=None):
         r = wavs if isinstance(wavs, Ragged) else Ragged.from_list_keep64(wavs, dev)
         if r.n == 0:
             return [[] for _ in sos_list]
+        if not exact:
+            if not r.packed:           # (the exact path refuses it too, in split(); here before anything runs, not by another kernel)
+                raise ValueError("a batch of views with gaps has no packed layout to split")
+            small = [k for k, s_ in enumerate(sos_list) if s_.shape[0] <= SOS_FAST_MAX_SECTIONS]
+            out = [None] * len(sos_list)
+            for k, ys in zip(small, _sosfiltfilt_fast([sos_list[k] for k in small], r, dev)):
+                out[k] = ys
+            return [ys if ys is not None else sosfiltfilt(s_, r, dev) for s_, ys in zip(sos_list, out)]
         if r.data.dtype != torch.float32 or any(s_.shape[0] > 8 for s_ in sos_list) or not r.packed:
             return [sosfiltfilt(s_, r if r.packed else wavs, dev) for s_ in sos_list]
         edges = [_sos_edge(s_) for s_ in sos_list]
         if int(r.lens_host.min()) <= max(edges):
             raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % max(edges))
-        lib = _lib.load()
-        total = int(r.lens_host.sum())
-        try:
-            free_doubles = int(torch.cuda.mem_get_info(dev)[0]) // 8 // 4
-        except Exception:
-            free_doubles = SOS_MULTI_MAX_DOUBLES
-        per_launch = max(1, min(SOS_MULTI_MAX_DESIGNS, min(SOS_MULTI_MAX_DOUBLES, free_doubles) // max(total, 1)))
-        out = []
-        for d0 in range(0, len(sos_list), per_launch):
-            chunk = sos_list[d0:d0 + per_launch]
-            D = len(chunk)
-            sos_h, zi_h = np.zeros((D, 8, 6)), np.zeros((D, 8, 2))
-            for d, s_ in enumerate(chunk):
-                sos_h[d, :s_.shape[0]] = s_
-                zi_h[d, :s_.shape[0]] = sosfilt_zi(s_)
-            ns = np.array([s_.shape[0] for s_ in chunk], dtype=np.int32)
-            eg = np.array(edges[d0:d0 + D], dtype=np.int32)
-            sos_d, zi_d = _h2d(sos_h, dev), _h2d(zi_h, dev)
-            ws_bytes = int(lib.ssr_sosfiltfilt_multi_workspace_bytes(total, r.n, eg.ctypes.data_as(C.c_void_p), D))
-            ws = _workspace(ws_bytes, dev)
-            y = torch.empty((D, total), dtype=torch.float64, device=dev)
-            _lib.check(lib.ssr_sosfiltfilt_multi(_vp(r.data), _vp(r.off), _vp(r.len), r.n, total, _vp(sos_d), _vp(zi_d),
-                                                 ns.ctypes.data_as(C.c_void_p), eg.ctypes.data_as(C.c_void_p), D, _vp(y), total, _vp(ws),
-                                                 ws_bytes, _stream()))
-            out += [r.split(y[d]) for d in range(D)]
-        return out
+        return _sosfiltfilt_launches(sos_list, edges, r, dev, "ssr_sosfiltfilt_multi_workspace_bytes", "ssr_sosfiltfilt_multi")
+
+
+def _sosfiltfilt_launches(sos_list, edges, r, dev, ws_name, fn_name):
+    """The designs of sos_list (<= 8 sections each) over the packed batch r, SOS_MULTI_MAX_DESIGNS and SOS_MULTI_MAX_DOUBLES output
+    doubles per launch at most, through one of the multi-design entry points -> [design][signal]."""
+    from scipy.signal import sosfilt_zi
+    lib = _lib.load()
+    ws_fn, fn = getattr(lib, ws_name), getattr(lib, fn_name)
+    total = int(r.lens_host.sum())
+    try:
+        free_doubles = int(torch.cuda.mem_get_info(dev)[0]) // 8 // 4
+    except Exception:
+        free_doubles = SOS_MULTI_MAX_DOUBLES
+    per_launch = max(1, min(SOS_MULTI_MAX_DESIGNS, min(SOS_MULTI_MAX_DOUBLES, free_doubles) // max(total, 1)))
+    out = []
+    for d0 in range(0, len(sos_list), per_launch):
+        chunk = sos_list[d0:d0 + per_launch]
+        D = len(chunk)
+        sos_h, zi_h = np.zeros((D, 8, 6)), np.zeros((D, 8, 2))
+        for d, s_ in enumerate(chunk):
+            sos_h[d, :s_.shape[0]] = s_
+            zi_h[d, :s_.shape[0]] = sosfilt_zi(s_)
+        ns = np.array([s_.shape[0] for s_ in chunk], dtype=np.int32)
+        eg = np.array(edges[d0:d0 + D], dtype=np.int32)
+        sos_d, zi_d = _h2d(sos_h, dev), _h2d(zi_h, dev)
+        ws_bytes = int(ws_fn(total, r.n, eg.ctypes.data_as(C.c_void_p), D))
+        ws = _workspace(ws_bytes, dev)
+        y = torch.empty((D, total), dtype=torch.float64, device=dev)
+        _lib.check(fn(_vp(r.data), _vp(r.off), _vp(r.len), r.n, total, _vp(sos_d), _vp(zi_d), ns.ctypes.data_as(C.c_void_p),
+                      eg.ctypes.data_as(C.c_void_p), D, _vp(y), total, _vp(ws), ws_bytes, _stream()))
+        out += [r.split(y[d]) for d in range(D)]
+    return out
+
+
+def _sosfiltfilt_fast(sos_list, r, dev):
+    """sosfiltfilt_multi(exact=False) for designs of <= 8 sections over a packed float32 or float64 batch."""
+    if not sos_list:
+        return []
+    edges = [_sos_edge(s_) for s_ in sos_list]
+    if int(r.lens_host.min()) <= max(edges):
+        raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % max(edges))
+    f64 = r.data.dtype == torch.float64
+    return _sosfiltfilt_launches(sos_list, edges, r, dev, "ssr_sosfiltfilt_fast_workspace_bytes",
+                                 "ssr_sosfiltfilt_fast_f64" if f64 else "ssr_sosfiltfilt_fast")
 
 
 def xcorr_argmax(a_list, b_list, device=None):

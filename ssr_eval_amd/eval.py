@@ -157,7 +157,7 @@ class SSR_Eval_Helper:
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
-                 quality=None, pitch=None):
+                 quality=None, pitch=None, iir_exact=True):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -173,7 +173,13 @@ class SSR_Eval_Helper:
         pitch (not in the reference): None = off; True = every key also gets f0_rmse / f0_corr / gpe / vde / ffe of the estimate's
         YIN F0 track against the target's (AudioMetrics.pitch_multi / pitch_batch at evaluation_sr, tracked at 16 kHz); one of those
         names or a tuple of them = those; a dict = `which` ("all", a name or a tuple) and / or the search range `fmin`, `fmax` (Hz,
-        default 50 and 500)."""
+        default 50 and 500).
+        iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
+        scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
+        within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14)."""
+        if not isinstance(iir_exact, bool):
+            raise ValueError("iir_exact must be True or False")
+        self.iir_exact = iir_exact
         if pitch is not None:
             if pitch is not True:
                 pq = _which_option("pitch", pitch, _PITCH_KEYS, ("fmin", "fmax"))
@@ -408,7 +414,7 @@ class SSR_Eval_Helper:
                             low_rate -= 1
                         keys.append("proc_%s_%s_%s_%s" % (tag, low_rate, order, sr))
                         specs.append((low_rate // 2, order, ftype))
-            for key, ys in zip(keys, lowpass_iir_multi(xs, specs, sr, keep_on_device=keep_on_device)):
+            for key, ys in zip(keys, lowpass_iir_multi(xs, specs, sr, keep_on_device=keep_on_device, exact=self.iir_exact)):
                 put(key, ys)
         if self.setting_subsampling is not None:
             for low_rate in self.setting_subsampling["cutoff_freq"]:

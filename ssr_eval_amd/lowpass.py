@@ -124,24 +124,27 @@ def _design_cached(highcut, fs, order, ftype, lowcut):
     return design[ftype]()
 
 
-def _iir_batch(xs, highcut, fs, order, ftype, lowcut=None, keep_on_device=False):
-    """lowpass.py:54-131 for a list of signals: one ssr_sosfiltfilt launch (GPU, float64, bit-exact with SciPy)."""
+def _iir_batch(xs, highcut, fs, order, ftype, lowcut=None, keep_on_device=False, exact=True):
+    """lowpass.py:54-131 for a list of signals: one ssr_sosfiltfilt launch (GPU, float64, bit-exact with SciPy; exact=False: the
+    segment-parallel kernel, backend.sosfiltfilt)."""
     sos = _design(highcut, fs, order, ftype, lowcut)
     xs = [x if isinstance(x, torch.Tensor) else np.asarray(x) for x in xs]
     outs = [None] * len(xs)
     for want64 in (False, True):                     # float64 signals are filtered on their float64 values
         idx = [i for i, x in enumerate(xs) if B._is_f64(x) == want64]
         if idx:
-            ys = B.sosfiltfilt(sos, [_f32_unless_f64(xs[i]) for i in idx])
+            ys = B.sosfiltfilt(sos, [_f32_unless_f64(xs[i]) for i in idx], exact=exact)
             for i, y in zip(idx, ys):
                 outs[i] = align_length(xs[i], y if keep_on_device else y.cpu().numpy())
     return outs
 
 
-def lowpass_iir_multi(datas, specs, fs, keep_on_device=False):
+def lowpass_iir_multi(datas, specs, fs, keep_on_device=False, exact=True):
     """lowpass(d, highcut, fs, order, _type) for every (highcut, order, _type) of `specs` over one list of signals - what
     SSR_Eval_Helper.preprocess's three nested loops apply to a waveform (ssr_eval/eval.py:243-258) - with the designs side by side in
-    one launch (backend.sosfiltfilt_multi).  -> [spec][signal]; each entry equals lowpass_batch(datas, highcut, fs, order, _type)."""
+    one launch (backend.sosfiltfilt_multi).  -> [spec][signal]; each entry equals lowpass_batch(datas, highcut, fs, order, _type).
+    exact=False: the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): within 1e-10 of each signal's peak of the
+    default, not SciPy's bits)."""
     plans = []                         # (int(highcut), clamped order, design name) per spec: BOTH paths below use these
     for highcut, order, _type in specs:
         name = next((n for n in ("butter", "cheby1", "ellip", "bessel") if _type in n), None)
@@ -156,9 +159,9 @@ def lowpass_iir_multi(datas, specs, fs, keep_on_device=False):
     if not xs or any(B._is_f64(x) for x in xs):
         # float64 signals are filtered on their float64 values: the per-design path handles the mix (same integer cutoff,
         # clamped order and design name as the one-launch path)
-        return [_iir_batch(xs, hc, fs, order, name, keep_on_device=keep_on_device) for hc, order, name in plans]
+        return [_iir_batch(xs, hc, fs, order, name, keep_on_device=keep_on_device, exact=exact) for hc, order, name in plans]
     designs = [_design(hc, fs, order, name) for hc, order, name in plans]
-    ys = B.sosfiltfilt_multi(designs, [_f32_unless_f64(x) for x in xs])
+    ys = B.sosfiltfilt_multi(designs, [_f32_unless_f64(x) for x in xs], exact=exact)
     return [[align_length(x, y if keep_on_device else y.cpu().numpy()) for x, y in zip(xs, per_design)] for per_design in ys]
 
 
@@ -194,15 +197,16 @@ def lowpass(data, highcut, fs, order=5, _type="butter"):
     raise ValueError("Error: Unexpected filter type " + _type)
 
 
-def lowpass_batch(datas, highcut, fs, order=5, _type="butter", keep_on_device=False):
+def lowpass_batch(datas, highcut, fs, order=5, _type="butter", keep_on_device=False, exact=True):
     """lowpass() for a LIST of 1-D signals with one batched launch sequence per call (same dispatch semantics).
-    keep_on_device: results stay device tensors (inputs may be device tensors too) - the resident evaluation path."""
+    keep_on_device: results stay device tensors (inputs may be device tensors too) - the resident evaluation path.
+    exact=False: the IIR types take the segment-parallel kernel (backend.sosfiltfilt(exact=False)); the others ignore it."""
     order = limit(order, high=10, low=2)
     for d in datas:
         _check_1d(d)
     for name in ("butter", "cheby1", "ellip", "bessel"):
         if _type in name:
-            return _iir_batch(datas, int(highcut), fs, order, name, keep_on_device=keep_on_device)
+            return _iir_batch(datas, int(highcut), fs, order, name, keep_on_device=keep_on_device, exact=exact)
     if _type in "subsampling":
         ratio = highcut / int(fs / 2)
         fs_down = int(ratio * 44100)
