@@ -92,6 +92,20 @@ int ssr_pair_interleave(const ssr_plan* pl, bool in64);
 
 // row pitch of the pair pipeline's magnitude images: rows padded to 16 bytes (k_ssim's aligned loads, ssr_metrics.h CONTIG)
 inline int ssr_mag_pitch(int n_bins) { return (n_bins + 3) & ~3; }
+// such images through 16-byte loads: rows, both bases and the stride between estimate planes 16-byte aligned
+inline bool ssr_images_vec16(const float* x, const float* y, int pitch, int64_t x_plane) {
+  return pitch % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && (x_plane % 4) == 0;
+}
+// The reductions on K + 1 images run one wave per workgroup over a run of rows.  Estimate keys per wave sharing the target's
+// rows: three where they divide by three, else two, else one (k_specred_wave measured 3 and 2 best on the four-metric reduction).
+inline int ssr_keys_per_wave(int n_keys) { return n_keys % 3 == 0 ? 3 : (n_keys % 2 == 0 ? 2 : 1); }
+// Rows per workgroup: ~16 k workgroups per launch over `groups` (item, key group) pairs, at least 8 rows each
+inline int ssr_wave_rows_per_wg(int max_rows, int64_t groups) {
+  int64_t spc = ((int64_t)16384 + groups - 1) / groups;
+  if (spc > max_rows / 8) spc = max_rows / 8;
+  if (spc < 1) spc = 1;
+  return ssr_ceil_div(max_rows, spc);
+}
 // Estimates of a multi-key call go two per complex transform (images only) where the plan has a wave kernel for that
 // (ssr_pair_metrics_multi, ssr_pair_lsd_bands).  est64: float64 estimates - n_fft = 3 q on the rotating four-wave engine
 // (AudioMetrics(48000), ssr_stft_r3_rot.h SSR_IN_EST64X2).
@@ -142,6 +156,8 @@ template <typename T> int ssr_launch_stft_rn_wave(const ssr_plan*, SsrStftParams
 template <typename T> int ssr_launch_stft_r3_64(const ssr_plan*, SsrStftParams<T>&, int grid, hipStream_t);
 // dispatcher (tu_core.hip): fills the plan tables into p and picks the unit
 template <typename T> int ssr_launch_stft(const ssr_plan*, SsrStftParams<T>&, int grid, hipStream_t);
+// tu_metrics.hip: rows[i] = the frames of item i, from the lengths on the device (what the reductions and finalisations read as T_i)
+int ssr_launch_rows_from_len(const ssr_plan* pl, const int32_t* len, int n_items, int32_t* rows, hipStream_t s);
 // tu_lowpass.hip
 template <typename T> int ssr_launch_lowpass(const ssr_plan*, SsrLowpassParams<T>&, int grid, hipStream_t);
 // tu_tlconv.hip: the reference-arithmetic engine (dense float32 DFT products on the matrix cores)

@@ -2,7 +2,7 @@
 // ssr_pair_lsd_bands, ssr_pair_lsd_bands_est64).
 #include "ssr_host.h"
 #include "ssr_lsd_bands.h"
-#include "ssr_pair_images.h"
+#include "ssr_pair_transform.h"
 
 template <int KG, int NB, bool VEC> __global__ __launch_bounds__(64) void k_lsd_bands(SsrLsdBandsParams p) {
   ssr_lsd_bands_body<KG, NB, VEC>(p, blockIdx.x % p.n_chunks, blockIdx.x / p.n_chunks);
@@ -11,11 +11,6 @@ template <int KG, int NB, bool VEC> __global__ __launch_bounds__(64) void k_lsd_
 __global__ __launch_bounds__(256) void k_lsd_bands_finalize(SsrLsdBandsFinalizeParams p, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) ssr_lsd_bands_finalize(p, i);
-}
-
-__global__ void k_lsd_rows_from_len(const int32_t* len, int n_items, int n_fft, int hop, int32_t* rows) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n_items) rows[i] = ssr_num_frames_dev(len[i], n_fft, hop);
 }
 
 // host-side validation of the caller's edges: nothing reaches the device unless every band lies inside [0, n_bins)
@@ -32,19 +27,6 @@ static int check_edges(const int32_t* edges, int64_t n_images, int n_bands, int 
   return SSR_OK;
 }
 
-// rows per one-wave workgroup: ~16 k workgroups per launch, at least 8 rows each (the k_specred_wave rule)
-static void band_chunks(int max_rows, int64_t groups, int* rows_per_chunk, int* n_chunks) {
-  int64_t spc = ((int64_t)16384 + groups - 1) / groups;
-  if (spc > max_rows / 8) spc = max_rows / 8;
-  if (spc < 1) spc = 1;
-  *rows_per_chunk = ssr_ceil_div(max_rows, spc);
-  *n_chunks = ssr_ceil_div(max_rows, *rows_per_chunk);
-}
-
-// estimate keys per wave sharing the target's rows: three where they divide by three, else two, else one (k_specred_wave measured 3
-// and 2 best on the four-metric reduction)
-static int band_kg(int n_keys) { return n_keys % 3 == 0 ? 3 : (n_keys % 2 == 0 ? 2 : 1); }
-
 template <int KG, int NB>
 static void launch_bands_kg(const SsrLsdBandsParams& p, bool vec, dim3 grid, hipStream_t s) {
   if (vec) hipLaunchKernelGGL((k_lsd_bands<KG, NB, true>), grid, dim3(64), 0, s, p);
@@ -53,8 +35,9 @@ static void launch_bands_kg(const SsrLsdBandsParams& p, bool vec, dim3 grid, hip
 
 // the reduction + the finalisation; `edges_dev` already on the device, n_keys * n_items images
 static int launch_bands(SsrLsdBandsParams p, int n_keys, int kg, int max_rows, const int32_t* n_rows, double* out, hipStream_t s) {
-  band_chunks(max_rows, (int64_t)p.n_items * (n_keys / kg), &p.rows_per_chunk, &p.n_chunks);
-  const bool vec = p.pitch % 4 == 0 && (((uintptr_t)p.x | (uintptr_t)p.y) & 15) == 0 && (p.x_plane % 4) == 0;
+  p.rows_per_chunk = ssr_wave_rows_per_wg(max_rows, (int64_t)p.n_items * (n_keys / kg));
+  p.n_chunks = ssr_ceil_div(max_rows, p.rows_per_chunk);
+  const bool vec = ssr_images_vec16(p.x, p.y, p.pitch, p.x_plane);
   const dim3 grid((unsigned)((int64_t)(n_keys / kg) * p.n_items * p.n_chunks));
   const bool two = p.n_bands <= 2;        // the LF / HF split: 2 accumulators per key instead of SSR_MAX_BANDS
   switch (kg * 2 + (two ? 1 : 0)) {
@@ -74,9 +57,8 @@ static int launch_bands(SsrLsdBandsParams p, int n_keys, int kg, int max_rows, c
 }
 
 static size_t part_bytes(int64_t n_images, int max_rows, int n_bands, int64_t groups) {
-  int rpc, nc;
-  band_chunks(max_rows, groups, &rpc, &nc);
-  return ssr_align256((size_t)n_images * nc * n_bands * sizeof(double));
+  const int n_chunks = ssr_ceil_div(max_rows, ssr_wave_rows_per_wg(max_rows, groups));
+  return ssr_align256((size_t)n_images * n_chunks * n_bands * sizeof(double));
 }
 static size_t edges_bytes(int64_t n_images, int n_bands) { return ssr_align256((size_t)n_images * (n_bands + 1) * sizeof(int32_t)); }
 
@@ -109,12 +91,13 @@ extern "C" int ssr_spectrogram_lsd_bands(const float* est_sp, const int64_t* est
 
 // ----------------------------------------------------------------------------------------------------
 // waveform level: K + 1 magnitude images per item (the pair transform of ssr_pair_metrics_multi), then the reduction
-struct BandWs { SsrPairImages im; size_t off_part, off_edges, off_rows, total; int kg; };
+struct BandWs { SsrPairGeom g; SsrPairImages im; size_t off_part, off_edges, off_rows, total; int kg; };
 static BandWs band_ws(const ssr_plan* pl, int n_items, int n_keys, int max_len, int64_t total_rows, int n_bands, bool in64) {
   BandWs w;
-  w.im = ssr_pair_images_layout(pl, n_items, n_keys, max_len, total_rows, in64);
+  w.g = ssr_pair_geom(pl, n_items, max_len, in64);
+  w.im = ssr_pair_images_layout(pl, n_keys, total_rows, in64);
   const int max_T = (int)ssr_num_frames(pl, max_len);
-  w.kg = band_kg(n_keys);
+  w.kg = ssr_keys_per_wave(n_keys);
   size_t o = w.im.end;
   w.off_part = o; o += part_bytes((int64_t)n_keys * n_items, max_T, n_bands, (int64_t)n_items * (n_keys / w.kg));
   w.off_edges = o; o += edges_bytes((int64_t)n_keys * n_items, n_bands);
@@ -134,28 +117,23 @@ static int pair_lsd_bands_impl(const ssr_plan* pl, const float* est, const doubl
                                const int64_t* tgt_off, const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len,
                                int64_t total_rows, const int32_t* edges, int n_bands, double* out, void* workspace, size_t workspace_bytes,
                                void* stream) {
-  if (!pl || (!est && !est64) || !est_off || !tgt || !tgt_off || !len || !frame_off || !edges || !out)
-    return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
-  if (n_bands < 1 || n_bands > SSR_MAX_BANDS) return ssr_fail(SSR_ERR_INVALID_ARG, "n_bands must be in 1..SSR_MAX_BANDS");
-  if (n_items <= 0 || n_keys <= 0) return SSR_OK;
-  if (max_len < 1) return ssr_fail(SSR_ERR_INVALID_ARG, "empty signals");
-  if (max_len >= (1 << 29)) return ssr_fail(SSR_ERR_UNSUPPORTED, "signals of 2^29 samples or more (4 GiB buffer views)");
-  if ((int64_t)n_items * n_keys > 0x3fffffff) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
+  int max_T;
+  if (int rc = ssr_check_pair_batch(pl, (est || est64) && est_off && tgt && tgt_off && len && frame_off && edges && out, n_items, n_keys, max_len,
+                                    true, &max_T, [&] {
+        return n_bands < 1 || n_bands > SSR_MAX_BANDS ? ssr_fail(SSR_ERR_INVALID_ARG, "n_bands must be in 1..SSR_MAX_BANDS") : SSR_OK;
+      }))
+    return rc;
+  if (!max_T) return SSR_OK;
   if (int rc = check_edges(edges, (int64_t)n_items * n_keys, n_bands, pl->n_bins)) return rc;
-  const int max_T = (int)ssr_num_frames(pl, max_len);
-  if ((int64_t)max_T * pl->n_bins >= ((int64_t)1 << 30)) return ssr_fail(SSR_ERR_UNSUPPORTED, "spectrogram of 2^30 elements or more (4 GiB buffer views)");
-  const bool e64 = est64 != nullptr;
-  const BandWs w = band_ws(pl, n_items, n_keys, max_len, total_rows, n_bands, e64);
+  const BandWs w = band_ws(pl, n_items, n_keys, max_len, total_rows, n_bands, est64 != nullptr);
   if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
-  if (int rc_dev = ssr_check_plan_device(pl)) return rc_dev;
   char* ws = (char*)workspace;
   hipStream_t s = (hipStream_t)stream;
   int32_t* rows = (int32_t*)(ws + w.off_rows);
   int32_t* e_dev = (int32_t*)(ws + w.off_edges);
   HIP_TRY(hipMemcpyAsync(e_dev, edges, (size_t)n_items * n_keys * (n_bands + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_lsd_rows_from_len, dim3(ssr_ceil_div(n_items, 256)), dim3(256), 0, s, len, n_items, pl->n_fft, pl->hop, rows);
-  HIP_TRY(hipGetLastError());
-  if (int rc = ssr_pair_images(pl, est, est64, est_off, tgt, tgt_off, len, frame_off, n_items, n_keys, w.im, ws, s)) return rc;
+  if (int rc = ssr_launch_rows_from_len(pl, len, n_items, rows, s)) return rc;
+  if (int rc = ssr_pair_images(pl, {len, frame_off, n_items, w.g}, est, est64, est_off, tgt, tgt_off, n_keys, w.im, ws, s)) return rc;
   SsrLsdBandsParams p{(float*)(ws + w.im.off_est), (float*)(ws + w.im.off_tgt), frame_off, frame_off, rows, e_dev,
                       (int64_t)(w.im.plane / sizeof(float)), pl->n_bins,
                       ssr_mag_pitch(pl->n_bins), n_bands, n_items, 0, 0, (double*)(ws + w.off_part)};

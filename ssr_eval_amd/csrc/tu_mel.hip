@@ -4,7 +4,7 @@
 
 #include "ssr_host.h"
 #include "ssr_mel.h"
-#include "ssr_pair_images.h"
+#include "ssr_pair_transform.h"
 
 __global__ __launch_bounds__(SSR_MEL_SCHED_NT) void k_mel_schedule(SsrMelFb f) {
   __shared__ int lo[SSR_MEL_MAX], wd[SSR_MEL_MAX], start[SSR_MEL_MAX];
@@ -35,11 +35,6 @@ template <bool VEC> __global__ __launch_bounds__(SSR_MEL_NT) void k_mel_project(
 __global__ __launch_bounds__(256) void k_mel_finalize(SsrMelFinalizeParams p, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) ssr_mel_finalize(p, i);
-}
-
-__global__ void k_mel_rows_from_len(const int32_t* len, int n_items, int n_fft, int hop, int32_t* rows) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n_items) rows[i] = ssr_num_frames_dev(len[i], n_fft, hop);
 }
 
 // Host-side validation of the caller's dense filterbank [n_bins][n_mels]: finite, >= 0, every filter one contiguous run of
@@ -94,21 +89,15 @@ static int upload_fb(const float* fb, int n_bins, int n_mels, int n_cep, int nnz
   return SSR_OK;
 }
 
-// estimate keys per wave sharing the target's projected row: three where they divide by three, else two, else one
-static int mel_kg(int n_keys) { return n_keys % 3 == 0 ? 3 : (n_keys % 2 == 0 ? 2 : 1); }
 static int mel_chunks(int max_rows) { return ssr_ceil_div(max_rows, SSR_MEL_RUN); }
 static size_t mel_part_bytes(int64_t n_images, int max_rows) { return ssr_align256((size_t)n_images * mel_chunks(max_rows) * 3 * sizeof(double)); }
-
-static bool mel_vec(const SsrMelParams& p) {
-  return p.pitch % 4 == 0 && (((uintptr_t)p.x | (uintptr_t)p.y) & 15) == 0 && (p.x_plane % 4) == 0;
-}
 
 static SsrLdsSlot g_lds_metrics[2], g_lds_project[2];
 
 // the reduction + the finalisation on n_keys * n_items images; p.f packed on the device
 static int launch_mel(SsrMelParams p, int n_keys, int max_rows, double* out, hipStream_t s) {
   p.n_chunks = mel_chunks(max_rows);
-  const bool vec = mel_vec(p);
+  const bool vec = ssr_images_vec16(p.x, p.y, p.pitch, p.x_plane);
   const size_t lds = mel_lds_bytes(p.F, p.kg);
   const int64_t grid = (int64_t)(n_keys / p.kg) * p.n_items * p.n_chunks;
   if (grid > 0x7fffffff) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
@@ -153,7 +142,7 @@ extern "C" int ssr_spectrogram_mel(const float* sp, const int64_t* frame_off, co
   p.F = n_bins; p.pitch = n_bins; p.n_items = n_images; p.n_chunks = mel_chunks(max_rows); p.kg = 1; p.which = 0; p.mel = out;
   const int64_t grid = (int64_t)n_images * p.n_chunks;
   if (grid > 0x7fffffff) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
-  const bool vec = mel_vec(p);
+  const bool vec = ssr_images_vec16(p.x, p.y, p.pitch, p.x_plane);
   const size_t lds = (ssr_mel_buf_doubles(n_bins) + SSR_MEL_SEGS) * 8;
   const void* fn = vec ? (const void*)k_mel_project<true> : (const void*)k_mel_project<false>;
   if (int rc = ssr_allow_lds(fn, lds, &g_lds_project[vec ? 1 : 0])) return rc;
@@ -194,11 +183,12 @@ extern "C" int ssr_spectrogram_mel_metrics(const float* est_sp, const int64_t* e
 }
 
 // ----------------------------------------------------------------------------------------------------
-// waveform level: K + 1 magnitude images per item (ssr_pair_images.h), then the reduction
-struct MelWs { SsrPairImages im; size_t off_fb, off_part, off_rows, total; };
+// waveform level: K + 1 magnitude images per item (ssr_pair_images), then the reduction
+struct MelWs { SsrPairGeom g; SsrPairImages im; size_t off_fb, off_part, off_rows, total; };
 static MelWs mel_ws(const ssr_plan* pl, int n_items, int n_keys, int max_len, int64_t total_rows, int n_mels, int n_cep, bool in64) {
   MelWs w;
-  w.im = ssr_pair_images_layout(pl, n_items, n_keys, max_len, total_rows, in64);
+  w.g = ssr_pair_geom(pl, n_items, max_len, in64);
+  w.im = ssr_pair_images_layout(pl, n_keys, total_rows, in64);
   size_t o = w.im.end;
   w.off_fb = o; o += fb_bytes(pl->n_bins, n_mels, n_cep);
   w.off_part = o; o += mel_part_bytes((int64_t)n_keys * n_items, (int)ssr_num_frames(pl, max_len));
@@ -219,32 +209,27 @@ static int pair_mel_impl(const ssr_plan* pl, const float* est, const double* est
                          const int64_t* tgt_off, const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len,
                          int64_t total_rows, const float* fb, int n_mels, int n_cep, int which, double* out, void* workspace,
                          size_t workspace_bytes, void* stream) {
-  if (!pl || (!est && !est64) || !est_off || !tgt || !tgt_off || !len || !frame_off || !fb || !out)
-    return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
-  if (int rc = check_which(which)) return rc;
-  if (n_cep < 1) return ssr_fail(SSR_ERR_INVALID_ARG, "n_cep must be in 1..n_mels - 1");
-  int nnz = 0;
-  if (int rc = check_fb(fb, pl->n_bins, n_mels, n_cep, &nnz)) return rc;
-  if (n_items <= 0 || n_keys <= 0) return SSR_OK;
-  if (max_len < 1) return ssr_fail(SSR_ERR_INVALID_ARG, "empty signals");
-  if (max_len >= (1 << 29)) return ssr_fail(SSR_ERR_UNSUPPORTED, "signals of 2^29 samples or more (4 GiB buffer views)");
-  if ((int64_t)n_items * n_keys > 0x3fffffff) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
-  const int max_T = (int)ssr_num_frames(pl, max_len);
-  if ((int64_t)max_T * pl->n_bins >= ((int64_t)1 << 30)) return ssr_fail(SSR_ERR_UNSUPPORTED, "spectrogram of 2^30 elements or more (4 GiB buffer views)");
+  int max_T, nnz = 0;
+  if (int rc = ssr_check_pair_batch(pl, (est || est64) && est_off && tgt && tgt_off && len && frame_off && fb && out, n_items, n_keys, max_len,
+                                    true, &max_T, [&] {
+        if (int rc = check_which(which)) return rc;
+        if (n_cep < 1) return ssr_fail(SSR_ERR_INVALID_ARG, "n_cep must be in 1..n_mels - 1");
+        return check_fb(fb, pl->n_bins, n_mels, n_cep, &nnz);
+      }))
+    return rc;
+  if (!max_T) return SSR_OK;
   const MelWs w = mel_ws(pl, n_items, n_keys, max_len, total_rows, n_mels, n_cep, est64 != nullptr);
   if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
-  if (int rc_dev = ssr_check_plan_device(pl)) return rc_dev;
   char* ws = (char*)workspace;
   hipStream_t s = (hipStream_t)stream;
   SsrMelParams p{};
   if (int rc = upload_fb(fb, pl->n_bins, n_mels, n_cep, nnz, ws + w.off_fb, s, &p.f)) return rc;
   int32_t* rows = (int32_t*)(ws + w.off_rows);
-  hipLaunchKernelGGL(k_mel_rows_from_len, dim3(ssr_ceil_div(n_items, 256)), dim3(256), 0, s, len, n_items, pl->n_fft, pl->hop, rows);
-  HIP_TRY(hipGetLastError());
-  if (int rc = ssr_pair_images(pl, est, est64, est_off, tgt, tgt_off, len, frame_off, n_items, n_keys, w.im, ws, s)) return rc;
+  if (int rc = ssr_launch_rows_from_len(pl, len, n_items, rows, s)) return rc;
+  if (int rc = ssr_pair_images(pl, {len, frame_off, n_items, w.g}, est, est64, est_off, tgt, tgt_off, n_keys, w.im, ws, s)) return rc;
   p.x = (float*)(ws + w.im.off_est); p.y = (float*)(ws + w.im.off_tgt); p.x_row = frame_off; p.y_row = frame_off; p.n_rows = rows;
   p.x_plane = (int64_t)(w.im.plane / sizeof(float));
-  p.F = pl->n_bins; p.pitch = ssr_mag_pitch(pl->n_bins); p.n_items = n_items; p.kg = mel_kg(n_keys); p.which = which;
+  p.F = pl->n_bins; p.pitch = ssr_mag_pitch(pl->n_bins); p.n_items = n_items; p.kg = ssr_keys_per_wave(n_keys); p.which = which;
   p.part = (double*)(ws + w.off_part);
   return launch_mel(p, n_keys, max_T, out, s);
 }

@@ -169,14 +169,17 @@ def test_waveform_level_36_float64_iir_keys_against_oracle(rate):
             assert _rel(got[i][k]["lsd_lf"], lf) < 1e-5 and _rel(got[i][k]["lsd_hf"], hf) < 1e-5, (i, k)
 
 
-@pytest.mark.parametrize("est64", [False, True])
-def test_chunked_keys_equal_one_launch(est64):
+@pytest.mark.parametrize("est64,n_fft,hop", [
+    pytest.param(False, 2229, 480, id="False"), pytest.param(True, 2229, 480, id="True"),
+    pytest.param(False, 4096, 1024, id="False-4096x1024"), pytest.param(True, 4096, 1024, id="True-4096x1024")])
+def test_chunked_keys_equal_one_launch(est64, n_fft, hop):
     """backend.pair_lsd_bands in chunks of keys equals the unchunked call (to the float32 rounding of a magnitude taken with a
-    different transform partner: <= 1e-6 relative)."""
+    different transform partner: <= 1e-6 relative).  2229: the keys go two per complex transform; 4096 (a block engine): every key
+    goes with the target, whose rows land in the scratch plane from key 1 on."""
     from ssr_eval_amd import backend as B
     rng = np.random.default_rng(11)
     n, K, rate = 3, 12, 48000
-    plan = B.get_plan(2229, 480)
+    plan = B.get_plan(n_fft, hop)
     tgts = [(0.1 * rng.standard_normal(20000 + 999 * i)).astype(np.float32) for i in range(n)]
     dt = np.float64 if est64 else np.float32
     ests = [[(t + 0.02 * rng.standard_normal(t.shape[0])).astype(dt) for t in tgts] for _ in range(K)]
@@ -187,7 +190,7 @@ def test_chunked_keys_equal_one_launch(est64):
         part = B.pair_lsd_bands(plan, ests, tgts, edges, keys_per_chunk=kc)
         np.testing.assert_allclose(part, whole, rtol=1e-6)
     from oracle import metrics as om
-    es, ts = om.wav_to_spectrogram(ests[7][1], 2229, 480), om.wav_to_spectrogram(tgts[1], 2229, 480)
+    es, ts = om.wav_to_spectrogram(ests[7][1], n_fft, hop), om.wav_to_spectrogram(tgts[1], n_fft, hop)
     assert _rel(whole[1, 7, 1], band_lsd(es, ts, 50 + 40 * 7, 600)) < 1e-5
 
 
