@@ -620,6 +620,36 @@ int ssr_sosfiltfilt_fast_f64(const double* x, const int64_t* off, const int32_t*
                              const double* sos, const double* zi, const int32_t* n_sections, const int32_t* edge, int n_designs,
                              double* y, int64_t y_stride, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Not in the reference.  Bootstrap of the aggregate: replicates of SSR_Eval_Helper.evaluate's "averaged" - the
+ * mean over speakers of each speaker's mean over its files (ssr_eval/eval.py:200-216 computes the point estimate only) - for
+ * every column of the per-file table at once, and a per-column summary of the replicates.
+ * table: DEVICE [n_rows][n_cols] float64, one row per file, the rows of speaker s at spk_off[s] .. spk_off[s + 1] - 1; spk_off:
+ * HOST [n_spk + 1], from 0 to n_rows, strictly ascending (no empty speaker); n_spk <= SSR_BOOTSTRAP_MAX_SPEAKERS (it travels in
+ * the kernel arguments: no workspace, no copy).  scheme SSR_BOOTSTRAP_UTTERANCE: slot t = speaker t; SSR_BOOTSTRAP_SPEAKER: the
+ * speaker of every slot is drawn with replacement first.  Either way slot t then draws as many files of its speaker as the speaker
+ * has, with replacement, and the SAME files serve every column of the replicate.  Draws are Philox4x32-10 words with the key
+ * (seed & 0xffffffff, seed >> 32): file draw j of slot t of replicate b = word j % 4 of counter (b, j / 4, t, 0), the speaker of
+ * slot t = word t % 4 of counter (b, t / 4, 0, 1); a word u picks index (u * n) >> 32.  A replicate therefore depends on
+ * (seed, b, spk_off, the table) only.  Each replicate of each column is ONE sequential float64 chain (file sums in draw order, slot
+ * means in slot order), so a column gives the same bits alone and inside a wider table.  A column with a non-finite table entry
+ * gets NaN in every replicate.  reps: DEVICE [n_boot][n_cols] float64.  1 <= n_boot <= 16384 (SSR_ERR_UNSUPPORTED above). */
+#define SSR_BOOTSTRAP_UTTERANCE 0
+#define SSR_BOOTSTRAP_SPEAKER 1
+#define SSR_BOOTSTRAP_MAX_Q 8
+#define SSR_BOOTSTRAP_MAX_SPEAKERS 512
+int ssr_bootstrap_means(const double* table, int64_t n_rows, int n_cols, const int32_t* spk_off, int n_spk, int n_boot,
+                        uint64_t seed, int scheme, double* reps, void* stream);
+/* Not in the reference.  Per column of reps (DEVICE [n_boot][n_cols], n_boot <= 16384: one workgroup sorts a column in LDS):
+ * out (DEVICE [n_cols][2 + n_q] float64) = the mean of the replicates, their standard error (two-pass, ddof = 1; NaN for
+ * n_boot = 1) and the n_q <= SSR_BOOTSTRAP_MAX_Q quantiles q (HOST, each in [0, 1]) by NumPy's default linear rule,
+ * pos = q (n_boot - 1); counts (DEVICE [n_cols][2] int32) = the replicates <= 0 and the replicates >= 0.  A column holding a
+ * non-finite replicate gets NaN in every float output and -1 in both counts. */
+int ssr_bootstrap_summary(const double* reps, int n_boot, int n_cols, const double* q, int n_q, double* out, int32_t* counts,
+                          void* stream);
+/* Not in the reference.  *index_tile = the file draws a workgroup generates at a time (speakers with more files take several tiles),
+ * *max_boot = the largest n_boot. */
+int ssr_bootstrap_geometry(int* index_tile, int* max_boot);
+
 /* A12 / SURVEY 8(e).  The path's one collective: the per-speaker [metric sums ..., count] buffer summed over ranks in
  * float64 (what SSR_Eval_Helper.evaluate's mean-of-speaker-means needs from the other shards, ssr_eval/eval.py:200-216) -
  * ncclAllReduce(sum, double) over RCCL / xGMI, in place, on `stream`.  RCCL is resolved with dlopen at the first call

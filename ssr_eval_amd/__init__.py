@@ -8,6 +8,7 @@ from .eval import SSR_Eval_Helper, BasicTestee  # noqa: F401
 from .metrics import AudioMetrics  # noqa: F401
 from .dsp import FDomainHelper  # noqa: F401
 from .lowpass import lowpass, bandpass  # noqa: F401
+from .stats import bootstrap_ci, compare_results  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -22,6 +22,7 @@ WAVE_SNR, WAVE_SI_SDR, WAVE_SEG_SNR = 1, 2, 4                                   
 MEL_LSD, MEL_L1, MEL_MCD, MEL_MAX = 1, 2, 4, 256                                # SSR_MEL_LSD, SSR_MEL_L1, SSR_MEL_MCD, SSR_MEL_MAX
 QUAL_LLR, QUAL_CEP, QUAL_WSS, QUAL_FWSEG = 1, 2, 4, 8                           # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG
 PITCH_F0_RMSE, PITCH_F0_CORR, PITCH_GPE, PITCH_VDE, PITCH_FFE = 1, 2, 4, 8, 16  # SSR_PITCH_*
+BOOTSTRAP_UTTERANCE, BOOTSTRAP_SPEAKER, BOOTSTRAP_MAX_Q = 0, 1, 8                # SSR_BOOTSTRAP_*
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -76,6 +77,9 @@ SIGNATURES = {
     "ssr_f0_track": (_i, [_vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ssr_f0_metrics_workspace_bytes": (_sz, [_vp, _i, _vp, _i, C.c_double, C.c_double, _i]),
     "ssr_f0_metrics": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_double, C.c_double, _i, _vp, _vp, _sz, _vp]),
+    "ssr_bootstrap_means": (_i, [_vp, _i64, _i, _vp, _i, _i, C.c_uint64, _i, _vp, _vp]),
+    "ssr_bootstrap_summary": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "ssr_bootstrap_geometry": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "ssr_to_log": (_i, [_vp, _i64, _vp, _vp]),
     "ssr_from_log": (_i, [_vp, _i64, _vp, _vp]),
     "ssr_energy_sums": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),

@@ -1054,6 +1054,60 @@ def pitch_metrics(tgt_list, est_list, tgt_index, fs, which=31, fmin=50.0, fmax=5
                                (fmin, fmax, which), device, deferred)
 
 
+BOOTSTRAP_SCHEMES = {"utterance": _lib.BOOTSTRAP_UTTERANCE, "speaker": _lib.BOOTSTRAP_SPEAKER}
+
+
+def bootstrap_geometry():
+    """(index_tile, max_boot) of ssr_bootstrap_geometry: the file draws a workgroup generates at a time and the largest n_boot.
+    Host only."""
+    tile, cap = C.c_int(), C.c_int()
+    _lib.check(_lib.load().ssr_bootstrap_geometry(C.byref(tile), C.byref(cap)))
+    return tile.value, cap.value
+
+
+def bootstrap_means(table, spk_off, n_boot, seed=0, scheme="utterance", device=None):
+    """Bootstrap replicates of the mean-of-speaker-means aggregate (ssr_bootstrap_means): table [N, K] float64 (ndarray
+    or tensor; rows grouped by speaker, speaker s at spk_off[s] .. spk_off[s + 1] - 1) -> device tensor [n_boot, K] float64.  The
+    same drawn files serve every column; a column with a non-finite entry is NaN in every replicate."""
+    require_gpu()
+    if scheme not in BOOTSTRAP_SCHEMES:
+        raise ValueError("resample must be 'utterance' or 'speaker'")
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be in [0, 2^64)")
+    dev = torch.device(device) if device is not None else default_device()
+    spk_off = np.ascontiguousarray(spk_off, dtype=np.int32)
+    with torch.cuda.device(dev):
+        t = table if isinstance(table, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64))
+        t = t.to(device=dev, dtype=torch.float64).contiguous()
+        if t.dim() != 2:
+            raise ValueError("table must be [files, columns]")
+        N, K = int(t.shape[0]), int(t.shape[1])
+        reps = torch.empty((max(int(n_boot), 0), K), dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().ssr_bootstrap_means(_vp(t), N, K, spk_off.ctypes.data_as(C.c_void_p), len(spk_off) - 1, int(n_boot), seed,
+                                                   BOOTSTRAP_SCHEMES[scheme], _vp(reps), _stream()))
+    return reps
+
+
+def bootstrap_summary(reps, q):
+    """Per column of the device tensor reps [B, K] float64 (ssr_bootstrap_summary): (mean [K], standard error [K] (ddof 1),
+    quantiles [len(q), K] by NumPy's linear rule, n_le0 [K], n_ge0 [K]) as ndarrays; a column holding a non-finite replicate: NaN
+    and -1."""
+    require_gpu()
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+    if not (isinstance(reps, torch.Tensor) and reps.is_cuda and reps.dtype == torch.float64 and reps.dim() == 2):
+        raise ValueError("reps must be a [B, K] float64 device tensor")
+    reps = reps.contiguous()
+    B, K = int(reps.shape[0]), int(reps.shape[1])
+    with torch.cuda.device(reps.device):
+        out = torch.empty((K, 2 + len(q)), dtype=torch.float64, device=reps.device)
+        counts = torch.empty((K, 2), dtype=torch.int32, device=reps.device)
+        _lib.check(_lib.load().ssr_bootstrap_summary(_vp(reps), B, K, q.ctypes.data_as(C.c_void_p), len(q), _vp(out), _vp(counts),
+                                                     _stream()))
+        out, counts = out.cpu().numpy(), counts.cpu().numpy()
+    return out[:, 0].copy(), out[:, 1].copy(), np.ascontiguousarray(out[:, 2:].T), counts[:, 0].copy(), counts[:, 1].copy()
+
+
 def stft(plan, wavs, kind="mag", torch_style_pad=False):
     """STFT of a list of waveforms.  kind "mag": list of [T, F] tensors; "complex": (re list, im list).
     torch_style_pad: refuse signals not longer than n_fft//2 the way torch's reflect padding does (torchlibrosa);

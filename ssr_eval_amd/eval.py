@@ -22,6 +22,7 @@ from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
 from .metrics import AudioMetrics, which_mask, _MEL_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
+from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
 
 # the reference's four, then the band-split LSD of SSR_Eval_Helper(lsd_split=...) and the intelligibility of
@@ -157,7 +158,7 @@ class SSR_Eval_Helper:
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
-                 quality=None, pitch=None, iir_exact=True):
+                 quality=None, pitch=None, iir_exact=True, bootstrap=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -176,7 +177,12 @@ class SSR_Eval_Helper:
         default 50 and 500).
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
-        within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14)."""
+        within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
+        bootstrap (not in the reference): None = off, the result and its JSON are what they are without the option; a number of
+        replicates B, or a dict of n_boot / level / seed / resample ("utterance" or "speaker") = evaluate() adds
+        result["confidence"] = {"settings": {...}, "averaged": {key: {metric: {"se", "lo", "hi"}}}}, the percentile bootstrap of the
+        "averaged" block (ssr_eval_amd.stats.bootstrap_ci)."""
+        self.bootstrap = None if bootstrap is None else bootstrap_option(bootstrap)
         if not isinstance(iir_exact, bool):
             raise ValueError("iir_exact must be True or False")
         self.iir_exact = iir_exact
@@ -721,6 +727,15 @@ class SSR_Eval_Helper:
         self.last_allreduce_average = D.mean_of_speaker_means(buf)[1] if len(keys) else None
         final_result["each_speaker"] = result_cache
         final_result["averaged"] = averaged
+        if self.bootstrap is not None:
+            # every rank holds the gathered table and the replicates are a function of (table, settings): the same bits everywhere
+            conf = {}
+            if len(work) and table.shape[1]:
+                ci = bootstrap_ci(table, [w[0] for w in work], device=self._device, **self.bootstrap)
+                conf = {k: {m: {"se": se, "lo": lo, "hi": hi} for m, se, lo, hi in zip(mets, *(ci[n][i * M:(i + 1) * M].tolist()
+                                                                                      for n in ("se", "lo", "hi")))}
+                        for i, k in enumerate(keys)}
+            final_result["confidence"] = {"settings": dict(self.bootstrap), "averaged": conf}
         if save_json and rank == 0:
             os.makedirs("results", exist_ok=True)
             write_json(final_result, os.path.join("results", str(now.date()) + "-" + str(now.time()) + "-"
