@@ -309,7 +309,7 @@ int ssr_wave_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const
  *   SSR_MEL_LSD  mel_lsd = mean_t sqrt( mean_m log10( G² / (E + 1e-12)² + 1e-12 )² )        (AudioMetrics.lsd on mel magnitudes)
  *   SSR_MEL_L1   mel_l1  = mean_{t,m} | ln⁺E - ln⁺G |,  ln⁺x = ln(max(x, 1e-5))
  *   SSR_MEL_MCD  mcd     = mean_t (10 / ln 10) sqrt( 2 Σ_{d=1..n_cep} c_d² ),  c = orthonormal DCT-II over m of ln⁺E - ln⁺G
- *                (MFCC-based, no DTW: not an SPTK mel-cepstrum MCD)
+ *                (MFCC-based, frame t against frame t: not an SPTK mel-cepstrum MCD; the warped measure is ssr_*_mel_dtw below)
  * fb: HOST float32 [n_bins][n_mels], row-major (torchaudio's melscale_fbanks layout).  It is validated before anything is
  * enqueued - finite, >= 0, every filter one contiguous run of non-zero weights and none all zero, 1 <= n_mels <= SSR_MEL_MAX,
  * 1 <= n_cep < n_mels - then copied into the workspace on `stream` (from page-locked memory asynchronously: keep it unchanged
@@ -342,6 +342,41 @@ int ssr_pair_mel_metrics_est64(const ssr_plan* plan, const double* est, const in
                                const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
                                const float* fb, int n_mels, int n_cep, int which, double* out, void* workspace, size_t workspace_bytes,
                                void* stream);
+
+/* DTW-aligned mel-cepstral distortion (not in the reference), for testees whose output drifts by a few frames against
+ * the target.  Inputs as above (magnitude images [T][n_bins], fb, ln⁺).  For every image on its own
+ *   c[t][d] = orthonormal DCT-II over m of ln⁺((S fb)[t][m]),  d = 1 .. n_cep            (float64; not the DCT of a difference)
+ * and for an (estimate E, target G) pair of T frames each (the min_len truncation of evaluation()) and a radius R in frames:
+ *   δ(i, j) = (10 / ln 10) sqrt( 2 Σ_d (c_E[i][d] - c_G[j][d])² )   for |i - j| <= R (Sakoe-Chiba band), +inf outside
+ *   D[0][0] = 2 δ(0, 0)
+ *   D[i][j] = min( D[i-1][j-1] + 2 δ(i, j),  D[i-1][j] + δ(i, j),  D[i][j-1] + δ(i, j) )
+ *             the candidates formed in that order, a later one replacing an earlier one only when strictly smaller (a tie keeps the
+ *             diagonal, then (i-1, j))
+ *   mcd_dtw = D[T-1][T-1] / (2 T)          (the normaliser does not depend on the path: the value is continuous in the images)
+ *   dtw_len = cells on the chosen path,  dtw_dev = ( Σ |i - j| over them ) / dtw_len   (mean drift in frames)
+ * R = 0: mean_t δ(t, t), i.e. mcd up to float64 rounding; R >= T behaves as R = T - 1; a wider band never gives a larger value,
+ * bit for bit (every δ is computed the same way whatever R).  0 <= radius <= SSR_DTW_MAX_RADIUS (one band offset per lane),
+ * 1 <= n_cep < n_mels and the filterbank are checked before anything is enqueued (SSR_ERR_INVALID_ARG); the workspace queries
+ * return 0 for such arguments; n_items = 0 enqueues nothing.
+ * out: double [n_items][n_keys][3] = mcd_dtw, dtw_dev, dtw_len.  Deterministic: a pair gives the same bits alone and in any batch. */
+#define SSR_DTW_MAX_RADIUS 31
+/* Image level, the descriptors of ssr_spectrogram_mel_metrics with `radius` for `which`: out double [n_images][3]. */
+size_t ssr_spectrogram_mel_dtw_workspace_bytes(int n_images, int max_rows, int n_bins, int n_mels, int n_cep, int radius);
+int ssr_spectrogram_mel_dtw(const float* est_sp, const int64_t* est_frame_off, const float* tgt_sp, const int64_t* tgt_frame_off,
+                            const int32_t* n_rows, int n_images, int max_rows, int n_bins, const float* fb, int n_mels, int n_cep,
+                            int radius, double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* Waveform level, the descriptors of ssr_pair_mel_metrics with `radius` for `which` (the images are ssr_pair_mel_metrics' own).
+ * ssr_pair_mel_dtw_workspace_bytes serves both entry points. */
+size_t ssr_pair_mel_dtw_workspace_bytes(const ssr_plan* plan, int n_items, int n_keys, int max_len, int64_t total_rows, int n_mels,
+                                        int n_cep, int radius);
+int ssr_pair_mel_dtw(const ssr_plan* plan, const float* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
+                     const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
+                     const float* fb, int n_mels, int n_cep, int radius, double* out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int ssr_pair_mel_dtw_est64(const ssr_plan* plan, const double* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
+                           const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
+                           const float* fb, int n_mels, int n_cep, int radius, double* out, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* Objective quality measures (not in the reference): Loizou's comp_llr.m, comp_cep.m, comp_wss.m and comp_fwseg.m
  * (Speech Enhancement: Theory and Practice, §11.1-11.2), restated.  Both signals widened to float64 with EPS added to every

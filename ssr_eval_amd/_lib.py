@@ -20,6 +20,7 @@ MAX_BANDS = 8                                                                   
 STOI, ESTOI, STOI_BOTH = 1, 2, 3                                                # SSR_STOI, SSR_ESTOI, SSR_STOI_BOTH
 WAVE_SNR, WAVE_SI_SDR, WAVE_SEG_SNR = 1, 2, 4                                   # SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR
 MEL_LSD, MEL_L1, MEL_MCD, MEL_MAX = 1, 2, 4, 256                                # SSR_MEL_LSD, SSR_MEL_L1, SSR_MEL_MCD, SSR_MEL_MAX
+DTW_MAX_RADIUS = 31                                                             # SSR_DTW_MAX_RADIUS
 QUAL_LLR, QUAL_CEP, QUAL_WSS, QUAL_FWSEG = 1, 2, 4, 8                           # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG
 PITCH_F0_RMSE, PITCH_F0_CORR, PITCH_GPE, PITCH_VDE, PITCH_FFE = 1, 2, 4, 8, 16  # SSR_PITCH_*
 BOOTSTRAP_UTTERANCE, BOOTSTRAP_SPEAKER, BOOTSTRAP_MAX_Q = 0, 1, 8                # SSR_BOOTSTRAP_*
@@ -65,6 +66,11 @@ SIGNATURES = {
     "ssr_pair_mel_metrics_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i64, _i, _i]),
     "ssr_pair_mel_metrics": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ssr_pair_mel_metrics_est64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssr_spectrogram_mel_dtw_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "ssr_spectrogram_mel_dtw": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssr_pair_mel_dtw_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i64, _i, _i, _i]),
+    "ssr_pair_mel_dtw": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssr_pair_mel_dtw_est64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ssr_stoi_workspace_bytes": (_sz, [_vp, _i, _vp, _i]),
     "ssr_stoi": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "ssr_stoi_band_edges": (_i, [_vp, _vp]),

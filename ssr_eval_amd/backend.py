@@ -767,6 +767,45 @@ def pair_mel_metrics(plan, est_lists, tgt_list, fb, n_cep, which, deferred=False
                               lambda k0, k1: (fp, nm, int(n_cep), int(which)), deferred)
 
 
+def spectrogram_mel_dtw(est, target, fb, n_cep, radius):
+    """est / target: [N, T, F] magnitude images -> [N, 3] float64 device tensor (mcd_dtw, dtw_dev, dtw_len; ssr_spectrogram_mel_dtw)."""
+    require_gpu()
+    lib = _lib.load()
+    dev = est.device if isinstance(est, torch.Tensor) and est.is_cuda else default_device()
+    nb, nm, fp = _fb_arg(fb)
+    with torch.cuda.device(dev):
+        x = _dev_f32(est, dev).contiguous()
+        y = _dev_f32(target, dev).contiguous()
+        if x.dim() != 3 or x.shape != y.shape or int(x.shape[2]) != nb:
+            raise ValueError("expected two [N, T, %d] images, got %s and %s" % (nb, tuple(x.shape), tuple(y.shape)))
+        N, T, F = (int(v) for v in x.shape)
+        out = torch.empty((N, 3), dtype=torch.float64, device=dev)
+        if N:
+            if T < 1:
+                raise ValueError("empty spectrogram")
+            off, rows = _uniform_images(N, T, dev)
+            ws_bytes = int(lib.ssr_spectrogram_mel_dtw_workspace_bytes(N, T, F, nm, int(n_cep), int(radius)))
+            ws = _workspace(ws_bytes, dev)
+            _lib.check(lib.ssr_spectrogram_mel_dtw(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, fp, nm, int(n_cep), int(radius),
+                                                   _vp(out), _vp(ws), ws_bytes, _stream()))
+        return out
+
+
+def pair_mel_dtw(plan, est_lists, tgt_list, fb, n_cep, radius, deferred=False, keys_per_chunk=None):
+    """DTW-aligned mel-cepstral distortion of K estimates per target, with pair_mel_metrics' arguments and key chunking (radius in
+    frames for `which`) -> [n, K, 3] float64: mcd_dtw, dtw_dev, dtw_len (deferred: a Pending)."""
+    nb, nm, fp = _fb_arg(fb)
+    if nb != plan.n_bins:
+        raise ValueError("the filterbank has %d bins, the transform %d" % (nb, plan.n_bins))
+    lib = plan.lib
+    return _pair_keys_chunked(plan, est_lists, tgt_list, 3, MEL_WS_BYTES, keys_per_chunk,
+                              "mel distances take float32 targets (float64 estimates are kept float64)",
+                              lambda n, kc, max_len, total: lib.ssr_pair_mel_dtw_workspace_bytes(plan.handle, n, kc, max_len, total, nm,
+                                                                                                 int(n_cep), int(radius)),
+                              (lib.ssr_pair_mel_dtw, lib.ssr_pair_mel_dtw_est64),
+                              lambda k0, k1: (fp, nm, int(n_cep), int(radius)), deferred)
+
+
 def octave_taps(p, q):
     """The filter of pystoi.utils.resample_oct for resample_poly(x, p, q) (p / q reduced): Octave's resample() design - a
     Kaiser-windowed ideal low-pass at 1 / (2 max(p, q)) with 60 dB rejection - normalised to unit sum.  float64."""

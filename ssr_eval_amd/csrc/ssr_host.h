@@ -158,6 +158,12 @@ template <typename T> int ssr_launch_stft_r3_64(const ssr_plan*, SsrStftParams<T
 template <typename T> int ssr_launch_stft(const ssr_plan*, SsrStftParams<T>&, int grid, hipStream_t);
 // tu_metrics.hip: rows[i] = the frames of item i, from the lengths on the device (what the reductions and finalisations read as T_i)
 int ssr_launch_rows_from_len(const ssr_plan* pl, const int32_t* len, int n_items, int32_t* rows, hipStream_t s);
+// tu_mel.hip: the filterbank area of a mel workspace - the table's host-side validation (n_cep = 0: projection only; -> *nnz), the
+// area's bytes, and the copy + k_mel_schedule on `s` that packs it at `ws` (-> *f)
+struct SsrMelFb;
+int ssr_mel_check_fb(const float* fb, int n_bins, int n_mels, int n_cep, int* nnz);
+size_t ssr_mel_fb_bytes(int n_bins, int n_mels, int n_cep);
+int ssr_mel_upload_fb(const float* fb, int n_bins, int n_mels, int n_cep, int nnz, char* ws, hipStream_t s, SsrMelFb* f);
 // tu_lowpass.hip
 template <typename T> int ssr_launch_lowpass(const ssr_plan*, SsrLowpassParams<T>&, int grid, hipStream_t);
 // tu_tlconv.hip: the reference-arithmetic engine (dense float32 DFT products on the matrix cores)

@@ -89,6 +89,13 @@ static int upload_fb(const float* fb, int n_bins, int n_mels, int n_cep, int nnz
   return SSR_OK;
 }
 
+// the same for the other mel translation units (ssr_host.h)
+int ssr_mel_check_fb(const float* fb, int n_bins, int n_mels, int n_cep, int* nnz) { return check_fb(fb, n_bins, n_mels, n_cep, nnz); }
+size_t ssr_mel_fb_bytes(int n_bins, int n_mels, int n_cep) { return fb_bytes(n_bins, n_mels, n_cep); }
+int ssr_mel_upload_fb(const float* fb, int n_bins, int n_mels, int n_cep, int nnz, char* ws, hipStream_t s, SsrMelFb* f) {
+  return upload_fb(fb, n_bins, n_mels, n_cep, nnz, ws, s, f);
+}
+
 static int mel_chunks(int max_rows) { return ssr_ceil_div(max_rows, SSR_MEL_RUN); }
 static size_t mel_part_bytes(int64_t n_images, int max_rows) { return ssr_align256((size_t)n_images * mel_chunks(max_rows) * 3 * sizeof(double)); }
 

@@ -21,7 +21,7 @@ import torch
 from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
-from .metrics import AudioMetrics, which_mask, _MEL_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
+from .metrics import AudioMetrics, which_mask, _MEL_DTW_NAMES, _MEL_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
 
@@ -33,6 +33,14 @@ _STOI_OPTIONS = {"stoi": False, "estoi": True, "both": "both"}
 # the keys of SSR_Eval_Helper(waveform=...), (mel=...), (quality=...) and (pitch=...), in that order after every key of _METRIC_KEYS
 # (only present in runs that ask for them)
 _WAVEFORM_KEYS, _MEL_KEYS, _QUALITY_KEYS, _PITCH_KEYS = _WAVE_NAMES, _MEL_NAMES, _QUALITY_NAMES, _PITCH_NAMES
+# the keys of SSR_Eval_Helper(mel_dtw=...), after the mel keys (dtw_len, a count of path cells, is not a per-key result: its mean
+# over files of different lengths says nothing)
+_MEL_DTW_KEYS = _MEL_DTW_NAMES[:2]
+
+
+def result_key_order():
+    """Every built-in metric key in the order a result lists them."""
+    return _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS + _MEL_DTW_KEYS + _QUALITY_KEYS + _PITCH_KEYS
 
 
 def _option_dict(value):
@@ -59,6 +67,11 @@ def _mel_arguments(h, keys):
     return (q.get("which", "all"),), {k: v for k, v in q.items() if k != "which"}
 
 
+def _mel_dtw_arguments(h, keys):
+    q = dict(h.mel_dtw) if isinstance(h.mel_dtw, dict) else {}
+    return (q.pop("radius", 16),), dict(q, lengths=False)
+
+
 def _quality_arguments(h, keys):
     q = _option_dict(h.quality)
     return (q.get("which", "all"), q.get("lpc_order")), {}
@@ -78,6 +91,7 @@ _FAMILIES = (
     ("stoi", "stoi_multi", "stoi_batch", lambda h, keys: ((_STOI_OPTIONS[h.stoi],), {}), False),
     ("waveform", "waveform_multi", "waveform_batch", lambda h, keys: ((_option_dict(h.waveform)["which"],), {}), False),
     ("mel", "mel_distance_multi", "mel_distance_batch", _mel_arguments, False),
+    ("mel_dtw", "mel_dtw_multi", "mel_dtw_batch", _mel_dtw_arguments, False),
     ("quality", "quality_multi", "quality_batch", _quality_arguments, False),
     ("pitch", "pitch_multi", "pitch_batch", _pitch_arguments, False),
 )
@@ -158,7 +172,7 @@ class SSR_Eval_Helper:
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
-                 quality=None, pitch=None, iir_exact=True, bootstrap=None):
+                 quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -168,6 +182,10 @@ class SSR_Eval_Helper:
         mel (not in the reference): None = off; True = every key also gets mel_lsd / mel_l1 / mcd (AudioMetrics.mel_distance_multi /
         mel_distance_batch at evaluation_sr, NVSR's 128-band HTK front end); a dict = front-end options (n_mels, f_min, f_max, norm,
         mel_scale, n_cep) and optionally `which` ("all", one of those names or a tuple of them).
+        mel_dtw (not in the reference): None = off; True = every key also gets mcd_dtw / dtw_dev, the mel-cepstral distortion along
+        the best warp of the estimate's frames onto the target's inside a band of 16 frames and that warp's mean drift in frames
+        (AudioMetrics.mel_dtw_multi / mel_dtw_batch at evaluation_sr); a dict = `radius` (0..31 frames) and / or
+        the mel front-end options (n_mels, f_min, f_max, norm, mel_scale, n_cep).
         quality (not in the reference): None = off; True = every key also gets llr / cep_dist / wss / fwseg_snr
         (AudioMetrics.quality_multi / quality_batch at evaluation_sr; wss and fwseg_snr look at the band below about 3.9 kHz only);
         one of those names or a tuple of them = those; a dict = `which` ("all", a name or a tuple) and / or `lpc_order`.
@@ -231,6 +249,13 @@ class SSR_Eval_Helper:
         if isinstance(mel, dict):                      # every option checked here, not at the first batch
             (which,), opts = _mel_arguments(self, ())
             which_mask(which, _MEL_KEYS)
+            self.audio_metrics._mel_fb(**opts)
+        if not (mel_dtw is None or mel_dtw is True or isinstance(mel_dtw, dict)):
+            raise ValueError("mel_dtw must be None, True or a dict of `radius` and mel options")
+        self.mel_dtw = mel_dtw
+        if mel_dtw is not None:
+            opts = dict(mel_dtw) if isinstance(mel_dtw, dict) else {}          # every option checked here, not at the first batch
+            AudioMetrics.dtw_radius(opts.pop("radius", 16))
             self.audio_metrics._mel_fb(**opts)
         self.unexpected_symbol_test_folder = "_.*#()_+=!@$%^&~"
         self._device = device
@@ -696,7 +721,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS + _QUALITY_KEYS + _PITCH_KEYS
+        order_keys = result_key_order()
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

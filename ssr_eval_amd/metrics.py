@@ -23,6 +23,7 @@ EPS = 1e-12
 _KEYS = ("lsd", "log_sispec", "sispec", "ssim")
 _WAVE_NAMES = ("snr", "si_sdr", "seg_snr")        # SSR_WAVE_SNR, SSR_WAVE_SI_SDR, SSR_WAVE_SEG_SNR: bits 0, 1, 2
 _MEL_NAMES = ("mel_lsd", "mel_l1", "mcd")         # SSR_MEL_LSD, SSR_MEL_L1, SSR_MEL_MCD: bits 0, 1, 2
+_MEL_DTW_NAMES = ("mcd_dtw", "dtw_dev", "dtw_len")      # the columns of ssr_pair_mel_dtw
 _QUALITY_NAMES = ("llr", "cep_dist", "wss", "fwseg_snr")   # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG: bits 0 .. 3
 _PITCH_NAMES = ("f0_rmse", "f0_corr", "gpe", "vde", "ffe")  # SSR_PITCH_F0_RMSE, _F0_CORR, _GPE, _VDE, _FFE: bits 0 .. 4
 
@@ -542,47 +543,39 @@ class AudioMetrics:
         """{'mel_lsd', 'mel_l1', 'mcd'} (or the subset `which` names) of one (estimate, target) pair."""
         return self.mel_distance_batch([est], [target], which, **mel)[0]
 
-    def mel_distance_batch(self, ests, targets, which="all", resident=False, deferred=False, **mel):
-        """mel_distance for lists of pairs, with evaluation_batch's input rules (metrics.py:89-90 truncation, float64 estimates kept
-        float64; float32 targets): one ssr_pair_mel_metrics call per estimate dtype.  deferred: as evaluation_batch."""
-        mask = self._mel_which(which)
-        fb, n_cep = self._mel_fb(**mel)
+    def _mel_batch(self, run, to_dict, ests, targets, resident, deferred):
+        """A mel pair family on lists of pairs: run(est_lists, tgt_list) -> Pending of [n, K, 3], one call per estimate dtype;
+        to_dict(row) -> the pair's dict."""
         pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
         groups = {}
         for i, (e, _) in enumerate(pairs):
             groups.setdefault(bool(B._is_f64(e)), []).append(i)
-        pending = [(idx, B.pair_mel_metrics(self._plan(), [[pairs[i][0] for i in idx]], [pairs[i][1] for i in idx], fb, n_cep, mask,
-                                            deferred=True)) for idx in groups.values()]
+        pending = [(idx, run([[pairs[i][0] for i in idx]], [pairs[i][1] for i in idx])) for idx in groups.values()]
 
         def finish():
             out = [None] * len(pairs)
             for idx, p in pending:
                 vals = p()
                 for r, i in enumerate(idx):
-                    out[i] = self._mel_dict(vals[r, 0], mask)
+                    out[i] = to_dict(vals[r, 0])
             return out
         return finish if deferred else finish()
 
-    def mel_distance_multi(self, ests_by_key, targets, which="all", resident=False, deferred=False, keys_per_chunk=None, **mel):
-        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
-        dicts.  Keys of one estimate dtype share one multi-key launch sequence (each target transformed once per chunk of keys);
-        lengths that differ between keys, or a key with both dtypes, send the pairs through mel_distance_batch."""
-        mask = self._mel_which(which)
-        fb, n_cep = self._mel_fb(**mel)
+    def _mel_multi(self, run, to_dict, batch, ests_by_key, targets, resident, deferred):
+        """The same for K estimates per target: keys of one estimate dtype share one multi-key launch sequence; lengths that differ
+        between keys, or a key with both dtypes, send the pairs through batch(ests, targets) (deferred, resident)."""
         K, n = len(ests_by_key), len(targets)
         pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for i in range(n)] for k in range(K)]
         same_len = all(len({pairs[k][i][0].shape[0] for k in range(K)}) == 1 for i in range(n))
         kinds = [{bool(B._is_f64(pairs[k][i][0])) for i in range(n)} for k in range(K)]
         if n == 0 or not same_len or any(len(kd) != 1 for kd in kinds):
             flat = _item_major(pairs, n, K)
-            return _regroup(self.mel_distance_batch([e for e, _ in flat], [t for _, t in flat], which, True, deferred=True, **mel),
-                            n, K, deferred)
+            return _regroup(batch([e for e, _ in flat], [t for _, t in flat]), n, K, deferred)
         tgts = [pairs[0][i][1] for i in range(n)]
         groups = {}
         for k in range(K):
             groups.setdefault(next(iter(kinds[k])), []).append(k)
-        pending = [(keys, B.pair_mel_metrics(self._plan(), [[pairs[k][i][0] for i in range(n)] for k in keys], tgts, fb, n_cep, mask,
-                                             deferred=True, keys_per_chunk=keys_per_chunk)) for keys in groups.values()]
+        pending = [(keys, run([[pairs[k][i][0] for i in range(n)] for k in keys], tgts)) for keys in groups.values()]
 
         def finish():
             out = [[None] * K for _ in range(n)]
@@ -590,9 +583,28 @@ class AudioMetrics:
                 vals = p()
                 for i in range(n):
                     for j, k in enumerate(keys):
-                        out[i][k] = self._mel_dict(vals[i, j], mask)
+                        out[i][k] = to_dict(vals[i, j])
             return out
         return finish if deferred else finish()
+
+    def mel_distance_batch(self, ests, targets, which="all", resident=False, deferred=False, **mel):
+        """mel_distance for lists of pairs, with evaluation_batch's input rules (metrics.py:89-90 truncation, float64 estimates kept
+        float64; float32 targets): one ssr_pair_mel_metrics call per estimate dtype.  deferred: as evaluation_batch."""
+        mask = self._mel_which(which)
+        fb, n_cep = self._mel_fb(**mel)
+        return self._mel_batch(lambda e, t: B.pair_mel_metrics(self._plan(), e, t, fb, n_cep, mask, deferred=True),
+                               lambda row: self._mel_dict(row, mask), ests, targets, resident, deferred)
+
+    def mel_distance_multi(self, ests_by_key, targets, which="all", resident=False, deferred=False, keys_per_chunk=None, **mel):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  Keys of one estimate dtype share one multi-key launch sequence (each target transformed once per chunk of keys);
+        lengths that differ between keys, or a key with both dtypes, send the pairs through mel_distance_batch."""
+        mask = self._mel_which(which)
+        fb, n_cep = self._mel_fb(**mel)
+        return self._mel_multi(lambda e, t: B.pair_mel_metrics(self._plan(), e, t, fb, n_cep, mask, deferred=True, keys_per_chunk=keys_per_chunk),
+                               lambda row: self._mel_dict(row, mask),
+                               lambda e, t: self.mel_distance_batch(e, t, which, True, deferred=True, **mel),
+                               ests_by_key, targets, resident, deferred)
 
     def mel_distance_spectrogram(self, est_sp, tgt_sp, which="all", **mel):
         """[B, C, T, F] magnitude tensors x2 (F = n_fft // 2 + 1) -> {name: [B, C] float64 tensor} for the names `which` asks for."""
@@ -604,6 +616,51 @@ class AudioMetrics:
         v = B.spectrogram_mel_metrics(est_sp.reshape(Bn * Cn, T, F), tgt_sp.reshape(Bn * Cn, T, F), fb, n_cep, mask)
         v = v.to(est_sp.device).reshape(Bn, Cn, 3)
         return {m: v[..., j] for j, m in enumerate(_MEL_NAMES) if mask & (1 << j)}
+
+    # ---- DTW-aligned mel-cepstral distortion (not in the reference): the mel front end above, every image's own
+    # cepstra, and a band-limited warp of the estimate's frames onto the target's.  radius: the band's half width in frames.
+    @staticmethod
+    def dtw_radius(radius):
+        """-> the radius as an int; ValueError unless it is an integer in 0..31."""
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= B._lib.DTW_MAX_RADIUS:
+            raise ValueError("radius must be an integer in 0..%d (frames)" % B._lib.DTW_MAX_RADIUS)
+        return int(radius)
+
+    @staticmethod
+    def _dtw_dict(row, lengths=True):
+        return {m: float(row[j]) for j, m in enumerate(_MEL_DTW_NAMES) if lengths or m != "dtw_len"}
+
+    def mel_dtw(self, est, target, radius=16, **mel):
+        """{'mcd_dtw', 'dtw_dev', 'dtw_len'} of one (estimate, target) pair: the mel-cepstral distortion along the best warp inside
+        |i - j| <= radius frames, that path's mean drift in frames and its number of cells.  radius = 0: mcd."""
+        return self.mel_dtw_batch([est], [target], radius, **mel)[0]
+
+    def mel_dtw_batch(self, ests, targets, radius=16, resident=False, deferred=False, lengths=True, **mel):
+        """mel_dtw for lists of pairs, with mel_distance_batch's input rules.  lengths=False: the dicts carry no dtw_len."""
+        radius = self.dtw_radius(radius)
+        fb, n_cep = self._mel_fb(**mel)
+        return self._mel_batch(lambda e, t: B.pair_mel_dtw(self._plan(), e, t, fb, n_cep, radius, deferred=True),
+                               lambda row: self._dtw_dict(row, lengths), ests, targets, resident, deferred)
+
+    def mel_dtw_multi(self, ests_by_key, targets, radius=16, resident=False, deferred=False, keys_per_chunk=None, lengths=True, **mel):
+        """K estimates per target, as mel_distance_multi -> n lists of K dicts."""
+        radius = self.dtw_radius(radius)
+        fb, n_cep = self._mel_fb(**mel)
+        return self._mel_multi(lambda e, t: B.pair_mel_dtw(self._plan(), e, t, fb, n_cep, radius, deferred=True, keys_per_chunk=keys_per_chunk),
+                               lambda row: self._dtw_dict(row, lengths),
+                               lambda e, t: self.mel_dtw_batch(e, t, radius, True, deferred=True, lengths=lengths, **mel),
+                               ests_by_key, targets, resident, deferred)
+
+    def mel_dtw_spectrogram(self, est_sp, tgt_sp, radius=16, **mel):
+        """[B, C, T, F] magnitude tensors x2 (F = n_fft // 2 + 1) -> {'mcd_dtw', 'dtw_dev', 'dtw_len'}: [B, C] float64 tensors."""
+        if est_sp.shape != tgt_sp.shape or est_sp.dim() != 4:
+            raise ValueError("expected two [B, C, T, F] tensors of one shape, got %s and %s" % (tuple(est_sp.shape), tuple(tgt_sp.shape)))
+        radius = self.dtw_radius(radius)
+        fb, n_cep = self._mel_fb(**mel)
+        Bn, Cn, T, F = (int(v) for v in est_sp.shape)
+        v = B.spectrogram_mel_dtw(est_sp.reshape(Bn * Cn, T, F), tgt_sp.reshape(Bn * Cn, T, F), fb, n_cep, radius)
+        v = v.to(est_sp.device).reshape(Bn, Cn, 3)
+        return {m: v[..., j] for j, m in enumerate(_MEL_DTW_NAMES)}
 
     # ---- reductions on [B, C, T, F] tensors (est first)
     @staticmethod
