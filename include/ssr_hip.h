@@ -453,6 +453,41 @@ int ssr_f0_metrics(const double* tgt, const int64_t* tgt_off, const int32_t* tgt
                    const int64_t* est_off, const int32_t* tgt_index, int n_est, double fmin, double fmax, int which,
                    double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Anti-wrapping phase distances (not in the reference): the instantaneous-phase, group-delay and instantaneous-
+ * angular-frequency losses of the bandwidth-extension literature with explicit phase modelling (Ai & Ling 2023; AP-BWE, Lu et
+ * al. 2024), restated as metrics.  Both signals widened to float64.  N = n_fft in {256, 512, 1024, 2048}, hop H in [1, N],
+ * periodic Hann window 0.5 - 0.5 cos(2 pi i / N), frames centred with reflect padding of N / 2 samples: T = 1 + n / H frames,
+ * frame t over padded samples [t H, t H + N).  X[t][k], Y[t][k]: the N-point DFTs of the target's and the estimate's windowed
+ * frames, C = Y conj(X); a(z) = |atan2(Im z, Re z)| in [0, pi], and a(z) = 0 where Re z = Im z = 0 whatever their signs (digital
+ * silence scores 0 and is counted).  With f(u) = |u - 2 pi round(u / 2 pi)| the papers' anti-wrapping function,
+ * f(arg Y - arg X) = a(C), and their differences along frequency and time are arguments of products:
+ *   SSR_PHASE_IP    mean over t < T, bin_lo <= k <= bin_hi of a(C[t][k])
+ *   SSR_PHASE_GD    mean over t < T, bin_lo <= k < bin_hi of a(C[t][k + 1] conj(C[t][k]))          (NaN: bin_hi = bin_lo)
+ *   SSR_PHASE_IAF   mean over t < T - 1, bin_lo <= k <= bin_hi of a(C[t + 1][k] conj(C[t][k]))     (NaN: T < 2)
+ * n <= N / 2 (reflect padding undefined) or n = 0: NaN.  Nothing is rescaled: a product that underflows to zero scores 0 (none
+ * does for float32 signals) and the definition does not depend on the level of either signal; the two frames of a pair share one
+ * complex transform, so a spectrum value is accurate to about 1e-16 log2(N) of the larger of the two frames' largest bins, and
+ * multiplying BOTH signals by one power of two changes no bit.  A frame in which either signal is digitally silent has C = 0
+ * exactly.  Values in radians.
+ * Pair e scores estimate e (est + est_off[e], as long as its target) against target tgt_index[e].  tgt / est: float32, or
+ * float64 where tgt_f64 / est_f64; tgt_off / est_off: DEVICE int64 sample offsets.  tgt_len and tgt_index are HOST int32 arrays:
+ * validated before anything is enqueued (which a non-empty subset of 7, n_fft in the set, 1 <= hop <= n_fft,
+ * 0 <= bin_lo <= bin_hi <= n_fft / 2, lengths in [0, 2^29), indices in [0, n_tgt)) and copied into the workspace on `stream`
+ * (from page-locked memory the copy is asynchronous: keep the values until the stream has reached it).  n_est = 0: nothing is
+ * enqueued.  out: double [n_est][popcount(which)], columns in bit order.  Without SSR_PHASE_IAF no warm-up frame is
+ * transformed; the IP and GD bits are the same either way.  Deterministic: fixed-order float sums, no floating-point atomics; a
+ * pair gives the same bits alone, in any batch and at any position.  workspace: ssr_phase_metrics_workspace_bytes (0 for
+ * invalid arguments).  One launch holds a workgroup of n_fft / 8 threads per chunk of 16 frames: SSR_ERR_UNSUPPORTED when that is
+ * 2^32 threads or more (checked before anything is enqueued). */
+#define SSR_PHASE_IP 1
+#define SSR_PHASE_GD 2
+#define SSR_PHASE_IAF 4
+size_t ssr_phase_metrics_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int n_fft, int hop,
+                                         int which);
+int ssr_phase_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt, const void* est,
+                      int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est, int n_fft, int hop, int bin_lo,
+                      int bin_hi, int which, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* A6.  The tensor helpers of ssr_eval/utils.py as stand-alone calls (inside ssr_pair_metrics /
  * ssr_spectrogram_metrics they are fused; these back `from ssr_eval.utils import to_log, pow_p_norm, ...`).
  *   ssr_to_log      out = log10(x + 1e-12)                       utils.py:43-44

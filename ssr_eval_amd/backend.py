@@ -1009,6 +1009,41 @@ def quality_metrics(tgt_list, est_list, tgt_index, fs, which=15, lpc_order=0, de
                                (int(fs), lpc_order, which), device, deferred)
 
 
+# ---- anti-wrapping phase distances: instantaneous phase, group delay, instantaneous angular frequency ---------------------------
+PHASE_N_FFTS = (256, 512, 1024, 2048)
+
+
+def check_phase_frames(n_fft, hop):
+    """(n_fft, hop) as ints (hop None: n_fft // 4), or ValueError: n_fft one of PHASE_N_FFTS, 1 <= hop <= n_fft (the C ABI's own
+    check)."""
+    ints = (int, np.integer)
+    if isinstance(n_fft, bool) or not isinstance(n_fft, ints) or int(n_fft) not in PHASE_N_FFTS:
+        raise ValueError("n_fft must be one of %s" % (PHASE_N_FFTS,))
+    hop = int(n_fft) // 4 if hop is None else hop
+    if isinstance(hop, bool) or not isinstance(hop, ints) or not 1 <= int(hop) <= int(n_fft):
+        raise ValueError("hop must be None (n_fft // 4) or an integer in [1, n_fft]")
+    return int(n_fft), int(hop)
+
+
+def phase_metrics(tgt_list, est_list, tgt_index, n_fft=1024, hop=None, band_bins=None, which=7, device=None, deferred=False):
+    """Anti-wrapping phase distances of estimate e against target tgt_index[e] (ssr_phase_metrics): waveforms (float32
+    or float64, each estimate as long as its target; a list holding both dtypes is widened to float64) -> [n_est, n_out] float64 in
+    radians, columns in bit order of `which` (1 phase_ip, 2 phase_gd, 4 phase_iaf).  n_fft: 256, 512, 1024 or 2048; hop: None =
+    n_fft // 4; band_bins: None = every bin, or (k_lo, k_hi) with 0 <= k_lo <= k_hi <= n_fft // 2, the bins scored.  Device views
+    of one buffer are read where they lie.  deferred: a Pending."""
+    which = int(which)
+    if not 1 <= which <= 7:
+        raise ValueError("which must be a non-empty combination of 1 (phase_ip), 2 (phase_gd) and 4 (phase_iaf)")
+    n_fft, hop = check_phase_frames(n_fft, hop)
+    k_lo, k_hi = (0, n_fft // 2) if band_bins is None else (int(band_bins[0]), int(band_bins[1]))
+    if not 0 <= k_lo <= k_hi <= n_fft // 2:
+        raise ValueError("band_bins must satisfy 0 <= k_lo <= k_hi <= n_fft // 2")
+    lib = _lib.load()
+    return _pair_index_metrics(tgt_list, est_list, tgt_index, bin(which).count("1"), _placed_where_they_lie,
+                               lambda *a: lib.ssr_phase_metrics_workspace_bytes(*a, n_fft, hop, which), lib.ssr_phase_metrics,
+                               (n_fft, hop, k_lo, k_hi, which), device, deferred)
+
+
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
 PITCH_FS = 16000                 # the rate every signal is tracked at
 PITCH_HOP = 160

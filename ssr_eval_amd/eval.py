@@ -21,7 +21,7 @@ import torch
 from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
-from .metrics import AudioMetrics, which_mask, _MEL_DTW_NAMES, _MEL_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
+from .metrics import AudioMetrics, which_mask, _MEL_DTW_NAMES, _MEL_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
 
@@ -36,11 +36,13 @@ _WAVEFORM_KEYS, _MEL_KEYS, _QUALITY_KEYS, _PITCH_KEYS = _WAVE_NAMES, _MEL_NAMES,
 # the keys of SSR_Eval_Helper(mel_dtw=...), after the mel keys (dtw_len, a count of path cells, is not a per-key result: its mean
 # over files of different lengths says nothing)
 _MEL_DTW_KEYS = _MEL_DTW_NAMES[:2]
+# the keys of SSR_Eval_Helper(phase=...), after every other key
+_PHASE_KEYS = _PHASE_NAMES
 
 
 def result_key_order():
     """Every built-in metric key in the order a result lists them."""
-    return _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS + _MEL_DTW_KEYS + _QUALITY_KEYS + _PITCH_KEYS
+    return _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS + _MEL_DTW_KEYS + _QUALITY_KEYS + _PITCH_KEYS + _PHASE_KEYS
 
 
 def _option_dict(value):
@@ -82,6 +84,11 @@ def _pitch_arguments(h, keys):
     return (q.get("which", "all"), q.get("fmin", 50.0), q.get("fmax", 500.0)), {}
 
 
+def _phase_arguments(h, keys):
+    q = _option_dict(h.phase)
+    return (q.get("which", "all"), q.get("n_fft", 1024), q.get("hop"), q.get("band")), {}
+
+
 # The optional metric families in the order they are queued on the stream and their keys appear in a result: (SSR_Eval_Helper
 # option, AudioMetrics method for K keys per file, method for a flat list of pairs, (helper, degradation keys of the call) -> the
 # (positional, keyword) arguments after the signals, whether those arguments hold one value per key - such a family takes the
@@ -94,6 +101,7 @@ _FAMILIES = (
     ("mel_dtw", "mel_dtw_multi", "mel_dtw_batch", _mel_dtw_arguments, False),
     ("quality", "quality_multi", "quality_batch", _quality_arguments, False),
     ("pitch", "pitch_multi", "pitch_batch", _pitch_arguments, False),
+    ("phase", "phase_distance_multi", "phase_distance_batch", _phase_arguments, False),
 )
 
 
@@ -172,7 +180,7 @@ class SSR_Eval_Helper:
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
-                 quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None):
+                 quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -193,6 +201,11 @@ class SSR_Eval_Helper:
         YIN F0 track against the target's (AudioMetrics.pitch_multi / pitch_batch at evaluation_sr, tracked at 16 kHz); one of those
         names or a tuple of them = those; a dict = `which` ("all", a name or a tuple) and / or the search range `fmin`, `fmax` (Hz,
         default 50 and 500).
+        phase (not in the reference): None = off; True = every key also gets phase_ip / phase_gd / phase_iaf, the anti-wrapping
+        instantaneous-phase, group-delay and instantaneous-angular-frequency distances in radians (AudioMetrics.phase_distance_multi /
+        phase_distance_batch at evaluation_sr); one of those names or a tuple of them = those; a dict = `which`
+        ("all", a name or a tuple) and / or `n_fft` (256, 512, 1024 or 2048; default 1024), `hop` (default n_fft // 4) and `band`
+        ((lo_hz, hi_hz), the band scored; default every bin).
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -201,6 +214,10 @@ class SSR_Eval_Helper:
         result["confidence"] = {"settings": {...}, "averaged": {key: {metric: {"se", "lo", "hi"}}}}, the percentile bootstrap of the
         "averaged" block (ssr_eval_amd.stats.bootstrap_ci)."""
         self.bootstrap = None if bootstrap is None else bootstrap_option(bootstrap)
+        if phase is not None and phase is not True:
+            fq = _which_option("phase", phase, _PHASE_KEYS, ("n_fft", "hop", "band"))
+            AudioMetrics._phase_bins(evaluation_sr, B.check_phase_frames(fq.get("n_fft", 1024), fq.get("hop"))[0], fq.get("band"))
+        self.phase = phase
         if not isinstance(iir_exact, bool):
             raise ValueError("iir_exact must be True or False")
         self.iir_exact = iir_exact

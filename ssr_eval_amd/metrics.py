@@ -11,7 +11,9 @@ reference.  All arithmetic runs in libssrhip.so (HIP, gfx950):
 Extras (keyword-only, not in the reference): ``precision`` ("f64" parity mode / "f32"), ``device``,
 ``n_fft`` / ``hop_length`` overrides, and ``evaluation_batch`` for lists of pairs.
 """
+import fractions
 import functools
+import math
 
 import numpy as np
 import torch
@@ -26,6 +28,7 @@ _MEL_NAMES = ("mel_lsd", "mel_l1", "mcd")         # SSR_MEL_LSD, SSR_MEL_L1, SSR
 _MEL_DTW_NAMES = ("mcd_dtw", "dtw_dev", "dtw_len")      # the columns of ssr_pair_mel_dtw
 _QUALITY_NAMES = ("llr", "cep_dist", "wss", "fwseg_snr")   # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG: bits 0 .. 3
 _PITCH_NAMES = ("f0_rmse", "f0_corr", "gpe", "vde", "ffe")  # SSR_PITCH_F0_RMSE, _F0_CORR, _GPE, _VDE, _FFE: bits 0 .. 4
+_PHASE_NAMES = ("phase_ip", "phase_gd", "phase_iaf")       # SSR_PHASE_IP, SSR_PHASE_GD, SSR_PHASE_IAF: bits 0, 1, 2
 
 
 def which_mask(which, names):
@@ -495,6 +498,51 @@ class AudioMetrics:
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  Each target is resampled and tracked once for its K estimates."""
         return self._multi_shared(self._pitch_family(which, fmin, fmax), ests_by_key, targets, resident, deferred)
+
+    # ---- anti-wrapping phase distances (DESIGN §17): instantaneous phase, group delay and instantaneous angular frequency of the
+    # estimate's spectrum against the target's, in radians (0 .. pi), on centred n_fft-point Hann frames of the signals at self.rate
+    _phase_which = staticmethod(functools.partial(which_mask, names=_PHASE_NAMES))
+    _phase_dicts = staticmethod(functools.partial(rows_dicts, names=_PHASE_NAMES))
+
+    @staticmethod
+    def _phase_bins(rate, n_fft, band):
+        """band None -> None (every bin); (lo_hz, hi_hz) -> the bins (ceil(lo n_fft / rate), floor(hi n_fft / rate)) clamped to
+        [0, n_fft // 2]; ValueError where that leaves no bin."""
+        if band is None:
+            return None
+        ok = isinstance(band, (tuple, list)) and len(band) == 2 and all(
+            not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v) for v in band)
+        if not ok:
+            raise ValueError("band must be None or (lo_hz, hi_hz)")
+        lo, hi = (fractions.Fraction(float(v)) * n_fft / fractions.Fraction(float(rate)) for v in band)
+        k_lo, k_hi = max(0, math.ceil(lo)), min(n_fft // 2, math.floor(hi))
+        if k_lo > k_hi:
+            raise ValueError("band %r holds no bin of a %d-point transform at %r Hz" % (tuple(band), n_fft, rate))
+        return k_lo, k_hi
+
+    def _phase_family(self, which, n_fft, hop, band):
+        mask = self._phase_which(which)
+        n_fft, hop = B.check_phase_frames(n_fft, hop)
+        bins = self._phase_bins(self.rate, n_fft, band)
+        return (lambda tgts, ests, index: B.phase_metrics(tgts, ests, index, n_fft, hop, bins, mask, self._device, deferred=True),
+                lambda vals: self._phase_dicts(vals, mask))
+
+    def phase_distance(self, est, target, which="all", n_fft=1024, hop=None, band=None):
+        """{'phase_ip', 'phase_gd', 'phase_iaf'} (or the subset `which` names) of one (estimate, target) pair, in radians.  n_fft:
+        256, 512, 1024 or 2048; hop: None = n_fft // 4; band: None = every bin, or (lo_hz, hi_hz), the band scored."""
+        return self.phase_distance_batch([est], [target], which, n_fft, hop, band)[0]
+
+    def phase_distance_batch(self, ests, targets, which="all", n_fft=1024, hop=None, band=None, resident=False, deferred=False):
+        """phase_distance() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64
+        signals, read in their own dtype: one ssr_phase_metrics call per (target dtype, estimate dtype) group).  deferred: as
+        evaluation_batch."""
+        return self._pairs(self._phase_family(which, n_fft, hop, band), ests, targets, resident, deferred, by_dtype=True)
+
+    def phase_distance_multi(self, ests_by_key, targets, which="all", n_fft=1024, hop=None, band=None, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  The K pairs of a target sit next to each other in one call."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        return _regroup(self.phase_distance_batch(ests, tgts, which, n_fft, hop, band, resident, deferred=True), n, K, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
