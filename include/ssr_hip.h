@@ -488,6 +488,38 @@ int ssr_phase_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, cons
                       int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est, int n_fft, int hop, int bin_lo,
                       int bin_hi, int which, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Multi-resolution STFT distance (not in the reference): the spectral convergence and the log-magnitude distance of
+ * Parallel WaveGAN's training loss (Yamamoto et al. 2020), restated as metrics, at n_res resolutions (N, H, W) = (n_fft[r], hop[r],
+ * win[r]) and their means.  Both signals widened to float64.  N in {256, 512, 1024, 2048}, 1 <= H <= N, 2 <= W <= N; the window is
+ * w[l + i] = 0.5 - 0.5 cos(2 pi i / W) for 0 <= i < W with l = (N - W) / 2 rounded down and zero elsewhere (torch.stft's placement
+ * of a periodic Hann window of win_length W); frames centred with reflect padding of N / 2 samples: T = 1 + n / H frames, none
+ * where n <= N / 2.  X[t][k], Y[t][k]: the N-point DFTs of the target's and the estimate's windowed frames on the bins
+ * bin_lo[r] <= k <= bin_hi[r]; p = max(|.|^2, eps), m = sqrt(p).  Per resolution
+ *   sc  = sqrt(sum (m_x - m_y)^2 / sum m_x^2)   over all scored cells of the signal
+ *   mag = mean |log m_x - log m_y|              over the same cells (evaluated as 0.5 |log(p_x / p_y)|)
+ * and NaN for both where the resolution has no frame.  A frame whose windowed samples are all zero has |.|^2 = 0 exactly, so
+ * m = sqrt(eps) in each of its bins; a frame whose windowed estimate equals its windowed target sample for sample has m_y = m_x
+ * exactly: an estimate equal to its target scores 0 / 0.
+ * Pair e scores estimate e (est + est_off[e], as long as its target) against target tgt_index[e].  tgt / est: float32, or
+ * float64 where tgt_f64 / est_f64; tgt_off / est_off: DEVICE int64 sample offsets.  tgt_len, tgt_index, n_fft, hop, win, bin_lo
+ * and bin_hi are HOST int32 arrays: validated before anything is enqueued (n_res in [1, SSR_MRSTFT_MAX_RES], each n_fft in the
+ * set, 1 <= hop <= n_fft, 2 <= win <= n_fft, 0 <= bin_lo <= bin_hi <= n_fft / 2, eps finite and > 0, lengths in [0, 2^29),
+ * indices in [0, n_tgt)); the first two are copied into the workspace on `stream` (from page-locked memory the copy is
+ * asynchronous: keep the values until the stream has reached it).  n_est = 0: nothing is enqueued.
+ * out: double [n_est][n_res + 1][2]: (sc, mag) of resolution r in row r, their means over the resolutions (added in index order;
+ * NaN where any resolution is NaN) in row n_res.  A resolution's row does not depend on the other resolutions of the call.
+ * Deterministic: fixed-order float sums, no atomics; a pair gives the same bits alone, in any batch and at any position.  Every
+ * launch is on `stream`, without a host wait in between.  workspace: ssr_mrstft_workspace_bytes (0 for invalid arguments).  A
+ * resolution's launch holds a workgroup of n_fft / 8 threads per chunk of 16 frames: SSR_ERR_UNSUPPORTED when that is 2^32 threads
+ * or more (checked before anything is enqueued). */
+#define SSR_MRSTFT_MAX_RES 8
+size_t ssr_mrstft_workspace_bytes(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int n_res,
+                                  const int32_t* n_fft, const int32_t* hop, const int32_t* win);
+int ssr_mrstft_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt, const void* est,
+                       int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est, int n_res, const int32_t* n_fft,
+                       const int32_t* hop, const int32_t* win, const int32_t* bin_lo, const int32_t* bin_hi, double eps, double* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* A6.  The tensor helpers of ssr_eval/utils.py as stand-alone calls (inside ssr_pair_metrics /
  * ssr_spectrogram_metrics they are fused; these back `from ssr_eval.utils import to_log, pow_p_norm, ...`).
  *   ssr_to_log      out = log10(x + 1e-12)                       utils.py:43-44

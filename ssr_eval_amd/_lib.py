@@ -24,6 +24,7 @@ DTW_MAX_RADIUS = 31                                                             
 QUAL_LLR, QUAL_CEP, QUAL_WSS, QUAL_FWSEG = 1, 2, 4, 8                           # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG
 PITCH_F0_RMSE, PITCH_F0_CORR, PITCH_GPE, PITCH_VDE, PITCH_FFE = 1, 2, 4, 8, 16  # SSR_PITCH_*
 PHASE_IP, PHASE_GD, PHASE_IAF = 1, 2, 4                                         # SSR_PHASE_IP, SSR_PHASE_GD, SSR_PHASE_IAF
+MRSTFT_MAX_RES = 8                                                              # SSR_MRSTFT_MAX_RES
 BOOTSTRAP_UTTERANCE, BOOTSTRAP_SPEAKER, BOOTSTRAP_MAX_Q = 0, 1, 8                # SSR_BOOTSTRAP_*
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
@@ -82,6 +83,9 @@ SIGNATURES = {
     "ssr_quality_bands": (_i, [_i, _vp, _vp, _vp, _vp, _sz]),
     "ssr_phase_metrics_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i, _i]),
     "ssr_phase_metrics": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssr_mrstft_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "ssr_mrstft_metrics": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _sz,
+                                _vp]),
     "ssr_f0_track_workspace_bytes": (_sz, [_vp, _i, C.c_double, C.c_double]),
     "ssr_f0_track": (_i, [_vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ssr_f0_metrics_workspace_bytes": (_sz, [_vp, _i, _vp, _i, C.c_double, C.c_double, _i]),

@@ -1044,6 +1044,68 @@ def phase_metrics(tgt_list, est_list, tgt_index, n_fft=1024, hop=None, band_bins
                                (n_fft, hop, k_lo, k_hi, which), device, deferred)
 
 
+# ---- multi-resolution STFT distance: spectral convergence and log-magnitude distance per resolution, and their means -----------
+MRSTFT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))      # Parallel WaveGAN's (n_fft, hop, win), in samples
+MRSTFT_EPS = 1e-7
+
+
+def check_mrstft_resolutions(resolutions):
+    """((n_fft, hop, win), ...) as a tuple of int triples (None: MRSTFT_RESOLUTIONS), or ValueError: 1 to 8 resolutions, n_fft one
+    of PHASE_N_FFTS, 1 <= hop <= n_fft, 2 <= win <= n_fft (the C ABI's own check)."""
+    if resolutions is None:
+        return MRSTFT_RESOLUTIONS
+    ints = (int, np.integer)
+    if not isinstance(resolutions, (tuple, list)) or not 1 <= len(resolutions) <= _lib.MRSTFT_MAX_RES:
+        raise ValueError("resolutions must be None or 1 to %d (n_fft, hop, win) triples" % _lib.MRSTFT_MAX_RES)
+    out = []
+    for res in resolutions:
+        if not isinstance(res, (tuple, list)) or len(res) != 3 or any(isinstance(v, bool) or not isinstance(v, ints) for v in res):
+            raise ValueError("a resolution is a triple of integers (n_fft, hop, win)")
+        n_fft, hop, win = (int(v) for v in res)
+        if n_fft not in PHASE_N_FFTS:
+            raise ValueError("n_fft must be one of %s" % (PHASE_N_FFTS,))
+        if not 1 <= hop <= n_fft:
+            raise ValueError("hop must be in [1, n_fft]")
+        if not 2 <= win <= n_fft:
+            raise ValueError("win must be in [2, n_fft]")
+        out.append((n_fft, hop, win))
+    return tuple(out)
+
+
+def check_mrstft_eps(eps):
+    """eps as a float, or ValueError: finite and > 0."""
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not (0.0 < float(eps) < math.inf):
+        raise ValueError("eps must be a finite number > 0")
+    return float(eps)
+
+
+def mrstft_metrics(tgt_list, est_list, tgt_index, resolutions=None, band_bins=None, eps=MRSTFT_EPS, device=None, deferred=False):
+    """Multi-resolution STFT distance of estimate e against target tgt_index[e] (ssr_mrstft_metrics): waveforms (float32
+    or float64, each estimate as long as its target; a list holding both dtypes is widened to float64) -> [n_est, n_res + 1, 2]
+    float64: (spectral convergence, log-magnitude distance) per resolution, and their means over the resolutions in the last row.
+    resolutions: None = MRSTFT_RESOLUTIONS, or up to 8 (n_fft, hop, win) in samples; band_bins: None = every bin, or one (k_lo, k_hi)
+    or None per resolution, the bins scored.  Device views of one buffer are read where they lie.  deferred: a function that
+    returns the array."""
+    res = check_mrstft_resolutions(resolutions)
+    eps = check_mrstft_eps(eps)
+    bands = [None] * len(res) if band_bins is None else list(band_bins)
+    if len(bands) != len(res):
+        raise ValueError("one band per resolution")
+    bins = [(0, n // 2) if b is None else (int(b[0]), int(b[1])) for (n, _, _), b in zip(res, bands)]
+    if any(not 0 <= lo <= hi <= n // 2 for (n, _, _), (lo, hi) in zip(res, bins)):
+        raise ValueError("band_bins must satisfy 0 <= k_lo <= k_hi <= n_fft // 2")
+    tab = np.ascontiguousarray(np.array([[n, h, w, lo, hi] for (n, h, w), (lo, hi) in zip(res, bins)], np.int32).T)
+    ptr = [tab[j].ctypes.data_as(C.c_void_p) for j in range(5)]
+    lib = _lib.load()
+    R = len(res)
+    rows = _pair_index_metrics(tgt_list, est_list, tgt_index, 2 * (R + 1), _placed_where_they_lie,
+                               lambda *a: lib.ssr_mrstft_workspace_bytes(*a, R, *ptr[:3]), lib.ssr_mrstft_metrics,
+                               (R, *ptr, eps), device, deferred)
+    if deferred:
+        return lambda: rows().reshape(-1, R + 1, 2)
+    return rows.reshape(-1, R + 1, 2)
+
+
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
 PITCH_FS = 16000                 # the rate every signal is tracked at
 PITCH_HOP = 160

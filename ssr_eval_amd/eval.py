@@ -21,7 +21,8 @@ import torch
 from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
-from .metrics import AudioMetrics, which_mask, _MEL_DTW_NAMES, _MEL_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
+from .metrics import AudioMetrics, which_mask, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, \
+    _WAVE_NAMES
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
 
@@ -43,6 +44,16 @@ _PHASE_KEYS = _PHASE_NAMES
 def result_key_order():
     """Every built-in metric key in the order a result lists them."""
     return _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS + _MEL_DTW_KEYS + _QUALITY_KEYS + _PITCH_KEYS + _PHASE_KEYS
+
+
+# the keys of SSR_Eval_Helper(mrstft=...), after every key of result_key_order()
+_MRSTFT_KEYS = _MRSTFT_NAMES
+
+
+def all_key_order():
+    """result_key_order(), then the keys of the families queued after _FAMILIES (_LATER_FAMILIES): the order a result lists its
+    metrics in."""
+    return result_key_order() + _MRSTFT_KEYS
 
 
 def _option_dict(value):
@@ -89,6 +100,11 @@ def _phase_arguments(h, keys):
     return (q.get("which", "all"), q.get("n_fft", 1024), q.get("hop"), q.get("band")), {}
 
 
+def _mrstft_arguments(h, keys):
+    q = h.mrstft if isinstance(h.mrstft, dict) else {}
+    return (q.get("resolutions"), q.get("band"), q.get("eps", B.MRSTFT_EPS)), {}
+
+
 # The optional metric families in the order they are queued on the stream and their keys appear in a result: (SSR_Eval_Helper
 # option, AudioMetrics method for K keys per file, method for a flat list of pairs, (helper, degradation keys of the call) -> the
 # (positional, keyword) arguments after the signals, whether those arguments hold one value per key - such a family takes the
@@ -102,6 +118,11 @@ _FAMILIES = (
     ("quality", "quality_multi", "quality_batch", _quality_arguments, False),
     ("pitch", "pitch_multi", "pitch_batch", _pitch_arguments, False),
     ("phase", "phase_distance_multi", "phase_distance_batch", _phase_arguments, False),
+)
+
+# Families added after "phase": queued behind _FAMILIES', their keys behind result_key_order()'s (all_key_order)
+_LATER_FAMILIES = (
+    ("mrstft", "mrstft_multi", "mrstft_batch", _mrstft_arguments, False),
 )
 
 
@@ -180,7 +201,7 @@ class SSR_Eval_Helper:
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
-                 quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None):
+                 quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -206,6 +227,10 @@ class SSR_Eval_Helper:
         phase_distance_batch at evaluation_sr); one of those names or a tuple of them = those; a dict = `which`
         ("all", a name or a tuple) and / or `n_fft` (256, 512, 1024 or 2048; default 1024), `hop` (default n_fft // 4) and `band`
         ((lo_hz, hi_hz), the band scored; default every bin).
+        mrstft (not in the reference): None = off; True = every key also gets mrstft_sc / mrstft_mag / mrstft, the spectral
+        convergence and the log-magnitude distance of Parallel WaveGAN's multi-resolution STFT loss averaged over its three
+        resolutions, and their sum (AudioMetrics.mrstft_multi / mrstft_batch at evaluation_sr); a dict =
+        `resolutions` (up to 8 (n_fft, hop, win) in samples), `band` ((lo_hz, hi_hz), the band scored) and / or `eps`.
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -218,6 +243,12 @@ class SSR_Eval_Helper:
             fq = _which_option("phase", phase, _PHASE_KEYS, ("n_fft", "hop", "band"))
             AudioMetrics._phase_bins(evaluation_sr, B.check_phase_frames(fq.get("n_fft", 1024), fq.get("hop"))[0], fq.get("band"))
         self.phase = phase
+        if mrstft is not None and mrstft is not True:
+            if not isinstance(mrstft, dict) or not mrstft or set(mrstft) - {"resolutions", "band", "eps"}:
+                raise ValueError("mrstft must be None, True or a dict of 'resolutions', 'band' and / or 'eps'")
+            B.check_mrstft_eps(mrstft.get("eps", B.MRSTFT_EPS))
+            AudioMetrics._mrstft_bins(evaluation_sr, B.check_mrstft_resolutions(mrstft.get("resolutions")), mrstft.get("band"))
+        self.mrstft = mrstft
         if not isinstance(iir_exact, bool):
             raise ValueError("iir_exact must be True or False")
         self.iir_exact = iir_exact
@@ -563,12 +594,12 @@ class SSR_Eval_Helper:
                 values = self.audio_metrics.evaluation_multi(by_key, [all_tgt[i * K] for i in range(len(items))], resident=True, deferred=True)
             else:
                 values = self.audio_metrics.evaluation_batch(all_proc, all_tgt, resident=True, deferred=True)
-        # the optional families, queued behind the four metrics in the same deferred batch, in _FAMILIES' order; the multi path
-        # analyses each target once for its K estimates
+        # the optional families, queued behind the four metrics in the same deferred batch, in _FAMILIES' order, then _LATER_FAMILIES';
+        # the multi path analyses each target once for its K estimates
         queued = []
         if all_proc:
             same_keys = multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items)))
-            for option, multi_name, batch_name, arguments, per_key in _FAMILIES:
+            for option, multi_name, batch_name, arguments, per_key in _FAMILIES + _LATER_FAMILIES:
                 if getattr(self, option) is None:
                     continue
                 if multi and (same_keys or not per_key):
@@ -738,7 +769,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = result_key_order()
+        order_keys = all_key_order()
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

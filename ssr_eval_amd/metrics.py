@@ -29,6 +29,7 @@ _MEL_DTW_NAMES = ("mcd_dtw", "dtw_dev", "dtw_len")      # the columns of ssr_pai
 _QUALITY_NAMES = ("llr", "cep_dist", "wss", "fwseg_snr")   # SSR_QUAL_LLR, SSR_QUAL_CEP, SSR_QUAL_WSS, SSR_QUAL_FWSEG: bits 0 .. 3
 _PITCH_NAMES = ("f0_rmse", "f0_corr", "gpe", "vde", "ffe")  # SSR_PITCH_F0_RMSE, _F0_CORR, _GPE, _VDE, _FFE: bits 0 .. 4
 _PHASE_NAMES = ("phase_ip", "phase_gd", "phase_iaf")       # SSR_PHASE_IP, SSR_PHASE_GD, SSR_PHASE_IAF: bits 0, 1, 2
+_MRSTFT_NAMES = ("mrstft_sc", "mrstft_mag", "mrstft")     # the means over the resolutions of ssr_mrstft_metrics, and their sum
 
 
 def which_mask(which, names):
@@ -543,6 +544,54 @@ class AudioMetrics:
         dicts.  The K pairs of a target sit next to each other in one call."""
         ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
         return _regroup(self.phase_distance_batch(ests, tgts, which, n_fft, hop, band, resident, deferred=True), n, K, deferred)
+
+    # ---- multi-resolution STFT distance (DESIGN §18): Parallel WaveGAN's spectral convergence and log-magnitude distance, averaged
+    # over several (n_fft, hop, win) - in SAMPLES whatever self.rate is; the defaults are the paper's, chosen at 24 kHz
+    @staticmethod
+    def _mrstft_bins(rate, resolutions, band):
+        """band None -> None (every bin); (lo_hz, hi_hz) -> its bins per resolution by _phase_bins' rule; ValueError where a
+        resolution has no bin inside."""
+        return None if band is None else [AudioMetrics._phase_bins(rate, n_fft, band) for n_fft, _, _ in resolutions]
+
+    def _mrstft_family(self, resolutions, band, eps, per_resolution):
+        res = B.check_mrstft_resolutions(resolutions)
+        eps = B.check_mrstft_eps(eps)
+        bins = self._mrstft_bins(self.rate, res, band)
+
+        def dicts(vals):
+            out = []
+            for row in vals:
+                sc, mag = float(row[-1, 0]), float(row[-1, 1])
+                d = {"mrstft_sc": sc, "mrstft_mag": mag, "mrstft": sc + mag}
+                if per_resolution:
+                    d["resolutions"] = [{"n_fft": n, "hop": h, "win": w, "sc": float(r[0]), "mag": float(r[1])}
+                                        for (n, h, w), r in zip(res, row)]
+                out.append(d)
+            return out
+        return (lambda tgts, ests, index: B.mrstft_metrics(tgts, ests, index, res, bins, eps, self._device, deferred=True)), dicts
+
+    def mrstft(self, est, target, resolutions=None, band=None, eps=B.MRSTFT_EPS, per_resolution=False):
+        """{'mrstft_sc', 'mrstft_mag', 'mrstft'} of one (estimate, target) pair: the spectral convergence and the mean absolute
+        log-magnitude difference averaged over the resolutions, and their sum.  resolutions: None = ((1024, 120, 600),
+        (2048, 240, 1200), (512, 50, 240)), or up to 8 (n_fft, hop, win) in samples with n_fft 256, 512, 1024 or 2048; band: None =
+        every bin, or (lo_hz, hi_hz), mapped to bins per resolution as phase_distance maps it (ValueError where a resolution has no
+        bin inside); eps: the floor of the squared magnitudes; per_resolution: also 'resolutions', a list of {'n_fft', 'hop', 'win',
+        'sc', 'mag'}.  A resolution the signal is too short for (n <= n_fft / 2) is NaN, and so are the three values."""
+        return self.mrstft_batch([est], [target], resolutions, band, eps, per_resolution)[0]
+
+    def mrstft_batch(self, ests, targets, resolutions=None, band=None, eps=B.MRSTFT_EPS, per_resolution=False, resident=False,
+                     deferred=False):
+        """mrstft() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals,
+        read in their own dtype: one ssr_mrstft_metrics call per (target dtype, estimate dtype) group).  deferred: as
+        evaluation_batch."""
+        return self._pairs(self._mrstft_family(resolutions, band, eps, per_resolution), ests, targets, resident, deferred, by_dtype=True)
+
+    def mrstft_multi(self, ests_by_key, targets, resolutions=None, band=None, eps=B.MRSTFT_EPS, per_resolution=False, resident=False,
+                     deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  The K pairs of a target sit next to each other in one call."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        return _regroup(self.mrstft_batch(ests, tgts, resolutions, band, eps, per_resolution, resident, deferred=True), n, K, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).

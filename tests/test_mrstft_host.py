@@ -1,0 +1,420 @@
+"""CPU tests of the multi-resolution STFT distance (mrstft_sc, mrstft_mag, mrstft): the float64 oracle
+(tests/mrstft_oracle.py) pinned against torch.stft, a g++ build of the kernel bodies (ssr_mrstft.h) against the oracle, the exact
+cases, bit-identity, the C ABI's argument checks (they return before anything touches a device), AudioMetrics /
+SSR_Eval_Helper(mrstft=...) validation and metric order.
+
+The bound of the emulated-kernel comparison, 1e-9 (absolute + relative), comes from an argument: the transform's rounding error is
+a few 1e-16 log2(N) of the frame's largest bin, at most 1e-13 absolute for Gaussian signals of sigma 0.1; a magnitude is at least
+sqrt(eps) = 3.2e-4, so a logarithm moves by at most 1e-13 / 3.2e-4 < 1e-9, and the means and the norm ratio by far less.  Worst
+differences seen: DESIGN.md section 18."""
+import ctypes as C
+import glob
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import mrstft_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TOL = 1e-9
+DEFAULT = O.DEFAULT_RESOLUTIONS
+
+
+def _noise(rng, n, dtype=np.float32, sigma=0.1):
+    return (sigma * rng.standard_normal(n)).astype(np.float32).astype(dtype)
+
+
+def _near(rng, x, level=0.03, sigma=0.1):
+    """The target plus Gaussian noise of level * sigma, in the target's dtype."""
+    return (x + level * _noise(rng, len(x), x.dtype, sigma)).astype(x.dtype)
+
+
+def _close(got, want):
+    return (np.isnan(got) and np.isnan(want)) or abs(got - want) <= TOL + TOL * abs(want)
+
+
+# ---- the oracle is torch.stft's multi-resolution STFT loss -----------------------------------------------------------------------
+@pytest.mark.parametrize("res", DEFAULT + ((256, 64, 256), (512, 50, 241), (1024, 333, 7)))
+def test_oracle_is_the_torch_stft_form(res):
+    """torch.stft(float64, n_fft, hop, win_length, hann_window(win_length)) (centred, reflect padding), clamp(min=eps).sqrt(),
+    Frobenius ratio and l1_loss of the logarithms - Parallel WaveGAN's SpectralConvergenceLoss / LogSTFTMagnitudeLoss - against
+    the oracle within 1e-12, at the three default resolutions, (256, 64, 256) and two with an odd n_fft - win_length."""
+    import torch
+    n_fft, hop, win = res
+    rng = np.random.default_rng(n_fft + win)
+    for n in (600, 3001, 16000):
+        if n <= n_fft // 2:
+            continue
+        x = _noise(rng, n, np.float64)
+        y = _near(rng, x, 0.5)
+        mags = []
+        for s in (x, y):
+            st = torch.stft(torch.from_numpy(s), n_fft, hop, win, torch.hann_window(win, dtype=torch.float64), return_complex=True)
+            mags.append(torch.sqrt(torch.clamp(st.real ** 2 + st.imag ** 2, min=O.EPS)).transpose(0, 1))
+        assert mags[0].shape == (O.num_frames(n, n_fft, hop), n_fft // 2 + 1)
+        sc = float(torch.norm(mags[0] - mags[1], p="fro") / torch.norm(mags[0], p="fro"))
+        mag = float(torch.nn.functional.l1_loss(torch.log(mags[1]), torch.log(mags[0])))
+        got = O.resolution(x, y, n_fft, hop, win)
+        print(res, n, "sc %.17g %.17g" % (got[0], sc), "mag %.17g %.17g" % (got[1], mag), abs(got[0] - sc), abs(got[1] - mag))
+        assert abs(got[0] - sc) <= 1e-12 and abs(got[1] - mag) <= 1e-12, (res, n, got, sc, mag)
+
+
+def test_oracle_means_and_nan():
+    rng = np.random.default_rng(1)
+    x = _noise(rng, 5000)
+    y = _near(rng, x)
+    d, rows = O.mrstft(x, y)
+    assert len(rows) == 3 and d["mrstft_sc"] == (rows[0][0] + rows[1][0] + rows[2][0]) / 3
+    assert d["mrstft_mag"] == (rows[0][1] + rows[1][1] + rows[2][1]) / 3 and d["mrstft"] == d["mrstft_sc"] + d["mrstft_mag"]
+    assert O.mrstft(x, x)[0] == {"mrstft": 0.0, "mrstft_sc": 0.0, "mrstft_mag": 0.0}
+    short, rows = O.mrstft(x[:1024], y[:1024])                       # n = N / 2 of the 2048-point resolution
+    assert all(np.isnan(v) for v in short.values()) and np.isnan(rows[1]).all() and np.isfinite(rows[0]).all()
+    assert [O.num_frames(n, 1024, 120) for n in (512, 513, 600, 48000)] == [0, 5, 6, 401]
+    z = np.zeros(3000)
+    assert np.all(O.magnitudes(z, 512, 50, 240) == np.sqrt(O.EPS))   # a digitally silent frame: m = sqrt(eps) in every bin
+
+
+# ---- the kernel bodies compiled for the host -------------------------------------------------------------------------------------
+EMU_SRC = os.path.join(ROOT, "tests", "emu", "mrstft_emu.cpp")
+EMU_SO = os.path.join(ROOT, "tests", "emu", "libmrstft_emu.so")
+
+
+@pytest.fixture(scope="module")
+def emu():
+    deps = [EMU_SRC] + glob.glob(os.path.join(ROOT, "ssr_eval_amd", "csrc", "*.h"))
+    if not os.path.exists(EMU_SO) or any(os.path.getmtime(d) > os.path.getmtime(EMU_SO) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", EMU_SO, EMU_SRC])
+    return C.CDLL(EMU_SO)
+
+
+def _res_table(resolutions, bands):
+    bands = [None] * len(resolutions) if bands is None else bands
+    return np.ascontiguousarray(np.array([[n, h, w] + list((0, n // 2) if b is None else b)
+                                          for (n, h, w), b in zip(resolutions, bands)], np.int32).T)
+
+
+def run_emu(lib, tgts, ests, idx, resolutions=DEFAULT, bands=None, eps=O.EPS):
+    """-> [n_est, n_res + 1, 2]"""
+    t64, e64 = tgts[0].dtype == np.float64, ests[0].dtype == np.float64
+    P = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    tl = np.array([len(t) for t in tgts], np.int32)
+    el = np.array([len(e) for e in ests], np.int64)
+    to = np.concatenate(([0], np.cumsum(tl)[:-1])).astype(np.int64)
+    eo = np.concatenate(([0], np.cumsum(el)[:-1])).astype(np.int64)
+    td = np.concatenate(tgts + [np.zeros(1, tgts[0].dtype)])
+    ed = np.concatenate(ests + [np.zeros(1, ests[0].dtype)])
+    idx = np.ascontiguousarray(idx, np.int32)
+    tab = _res_table(resolutions, bands)
+    out = np.full((len(ests), len(resolutions) + 1, 2), -123.0)
+    assert lib.mrstft_emu(P(td), int(t64), P(to), P(tl), len(tgts), P(ed), int(e64), P(eo), P(idx), len(ests), len(resolutions),
+                          P(tab[0]), P(tab[1]), P(tab[2]), P(tab[3]), P(tab[4]), C.c_double(eps), P(out)) == 0
+    return out
+
+
+def check_rows(got, tgts, ests, idx, resolutions=DEFAULT, bands=None, eps=O.EPS):
+    """Every value within TOL of the oracle (NaN where it has NaN) -> the worst absolute difference."""
+    worst = 0.0
+    for e, (y, i) in enumerate(zip(ests, idx)):
+        d, rows = O.mrstft(tgts[i], y, resolutions, bands, eps)
+        want = rows + [(d["mrstft_sc"], d["mrstft_mag"])]
+        for r, (w, g) in enumerate(zip(want, got[e])):
+            for c in range(2):
+                assert _close(g[c], w[c]), (e, r, c, g[c], w[c])
+                if not np.isnan(w[c]):
+                    worst = max(worst, abs(g[c] - w[c]))
+    return worst
+
+
+def _len_for_frames(T, n_fft, hop):
+    """A valid n with T frames (T = 1 + n // hop, n > n_fft / 2), a few samples past the smallest."""
+    n = max((T - 1) * hop, n_fft // 2 + 1)
+    n = min(n + 3, T * hop - 1)
+    assert O.num_frames(n, n_fft, hop) == T, (T, n_fft, hop, n)
+    return n
+
+
+def test_emulated_window_table(emu):
+    for n_fft, win in ((1024, 600), (512, 241), (256, 256), (2048, 2), (512, 511)):
+        w = np.zeros(n_fft)
+        emu.mrstft_window(n_fft, win, w.ctypes.data_as(C.c_void_p))
+        assert np.max(np.abs(w - O.window(n_fft, win))) <= 1e-15            # long double rounded once against float64 arithmetic
+        assert np.count_nonzero(w) == win - 1 and w[(n_fft - win) // 2] == 0.0
+
+
+@pytest.mark.parametrize("n_fft", O.N_FFTS)
+def test_emulated_kernels_match_the_oracle(emu, n_fft):
+    """Per transform size: T = 1, 2 (hop = n_fft), the chunk edges T = 16, 17 and 33 (hop = n_fft / 4), a hop that does not divide
+    n_fft, the shortest valid length n = n_fft / 2 + 1 and a signal too short for its padding; each batch at three windows
+    (win = n_fft, an even and an odd win < n_fft) in one call; estimates near the target (noise at 0.03 sigma) and independent
+    ones; then bands on the last batch."""
+    rng = np.random.default_rng(200 + n_fft)
+    q, odd = n_fft // 4, n_fft // 3 + 1
+    worst = 0.0
+    for hop, frames in ((n_fft, (1, 2, 5)), (q, (16, 17, 33)), (odd, (2, 17))):
+        res = ((n_fft, hop, n_fft), (n_fft, hop, n_fft // 2 + 88), (n_fft, hop, n_fft // 2 + 89 - (n_fft // 2) % 2))
+        assert res[1][2] % 2 == 0 and res[2][2] % 2 == 1
+        lens = [_len_for_frames(T, n_fft, hop) for T in frames] + [n_fft // 2 + 1, n_fft // 2, 0]
+        tg = [_noise(rng, n) for n in lens]
+        ests = [_near(rng, t) if i % 2 == 0 else _noise(rng, len(t)) for i, t in enumerate(tg)] + [_near(rng, tg[0], 1.0)]
+        idx = list(range(len(lens))) + [0]
+        got = run_emu(emu, tg, ests, idx, res)
+        worst = max(worst, check_rows(got, tg, ests, idx, res))
+        assert np.isnan(got[len(lens) - 2:len(lens)]).all() and np.isfinite(got[:len(lens) - 2]).all()      # n = N / 2 and n = 0
+        # a pair alone gives the bits it has in the batch
+        np.testing.assert_array_equal(run_emu(emu, [tg[1]], [ests[1]], [0], res)[0], got[1])
+    for band in ((0, n_fft // 2), (0, 0), (n_fft // 2, n_fft // 2), (n_fft // 8 + 1, n_fft // 4 + 2)):
+        bands = [band, None, band]
+        sub = run_emu(emu, tg, ests, idx, res, bands)
+        worst = max(worst, check_rows(sub, tg, ests, idx, res, bands))
+        np.testing.assert_array_equal(sub[:, 1], got[:, 1])                 # the unbanded resolution's row: the same bits
+    print("n_fft %d: worst |emulated - oracle| = %.3g" % (n_fft, worst))
+
+
+def test_emulated_default_resolutions_and_eps(emu):
+    rng = np.random.default_rng(3)
+    lens = (600, 1025, 4000, 9001)
+    tg = [_noise(rng, n) for n in lens]
+    ests = [_near(rng, t) for t in tg]
+    got = run_emu(emu, tg, ests, range(4))
+    print("worst", check_rows(got, tg, ests, range(4)))
+    assert np.isnan(got[0, 1]).all() and np.isnan(got[0, 3]).all() and np.isfinite(got[0, [0, 2]]).all()      # 600 <= 2048 / 2
+    for eps in (1e-12, 1e-3, 10.0):
+        check_rows(run_emu(emu, tg, ests, range(4), eps=eps), tg, ests, range(4), eps=eps)
+
+
+# ---- exact cases -----------------------------------------------------------------------------------------------------------------
+def test_emulated_identical_signals_score_exactly_zero(emu):
+    rng = np.random.default_rng(4)
+    res = DEFAULT + ((256, 64, 256), (512, 50, 241))
+    for dt in ((np.float32, np.float32), (np.float32, np.float64), (np.float64, np.float32), (np.float64, np.float64)):
+        x = _noise(rng, 7000).astype(dt[0])
+        got = run_emu(emu, [x], [x.astype(dt[1])], [0], res)
+        assert got.shape == (1, 6, 2) and not got.any() and not np.signbit(got).any(), got
+
+
+def test_emulated_silence(emu):
+    """Both silent: 0 / 0.  One side silent, and a silent stretch longer than a frame inside a signal, in both and in the estimate
+    only, at the default eps (the clamp; the vote itself is checked at a small eps below)."""
+    rng = np.random.default_rng(5)
+    n = 6000
+    z, x = np.zeros(n, np.float32), _noise(rng, n)
+    got = run_emu(emu, [z, x], [z, x, z], [0, 0, 1])
+    assert not got[0].any()
+    check_rows(got, [z, x], [z, x, z], [0, 0, 1])
+    assert got[2, 3, 0] > 0.99 and got[1, 3, 1] > 5.0               # all of the target's energy is missing; log ratios of e^5 and more
+    x2, y2, y3 = _noise(rng, n), _noise(rng, n), _noise(rng, n)
+    x2[1000:1000 + 5000] = 0.0
+    y2[1000:1000 + 5000] = 0.0
+    y3[2000:2000 + 2 * 2048 + 17] = 0.0
+    got = run_emu(emu, [x2], [y2, y3], [0, 0])
+    check_rows(got, [x2], [y2, y3], [0, 0])
+
+
+def test_emulated_silent_frames_clamp_to_eps_exactly(emu):
+    """The vote.  A digitally silent signal against a loud one (sigma = 100, N = 512: bins of about 1.4e3, so the packed transform's
+    rounding error, a few 1e-16 of them, is about 3e-13 and its square about 1e-25) at eps = 1e-36, eleven decades below that
+    square: the split alone would return the loud side's rounding error as the silent side's spectrum and clamp nothing, the
+    logarithms would be off by tens; with the vote the silent side is eps exactly, as the oracle's zero spectrum is.  The loud
+    side's own error is relative to its bins, so the 1e-9 bound holds as at the default eps."""
+    rng = np.random.default_rng(15)
+    n = 6000
+    x = 1e3 * _noise(rng, n, np.float64)
+    zz = np.zeros(n, np.float64)
+    res, eps = ((512, 128, 512),), 1e-36
+    assert (3e-16 * np.max(O.magnitudes(x, *res[0], eps=eps))) ** 2 > 1e6 * eps
+    got = run_emu(emu, [x, zz], [zz, x, x.astype(np.float32)], [0, 1, 1], res, eps=eps)
+    for e, (t, y) in enumerate(((x, zz), (zz, x), (zz, x.astype(np.float32)))):
+        want = O.resolution(t, y, *res[0], eps=eps)
+        print("silent side, eps 1e-36:", got[e, 0], want)
+        assert _close(got[e, 0, 0], want[0]) and _close(got[e, 0, 1], want[1]), (e, got[e], want)
+    # a silent stretch inside a loud pair: only its frames clamp
+    x2, y2 = x.copy(), 1e3 * _noise(rng, n, np.float64)
+    y2[1500:1500 + 3 * 512] = 0.0
+    x2[4000:4000 + 2 * 512] = 0.0
+    check_rows(run_emu(emu, [x2], [y2], [0], res, eps=eps), [x2], [y2], [0], res, eps=eps)
+
+
+def test_emulated_short_signal_is_nan_in_its_resolution_and_in_the_means(emu):
+    rng = np.random.default_rng(6)
+    res = ((512, 128, 512), (2048, 512, 2048), (256, 64, 200))
+    x = _noise(rng, 1024)                                           # n = N / 2 of the second resolution
+    y = _near(rng, x)
+    got = run_emu(emu, [x], [y], [0], res)[0]
+    assert np.isnan(got[1]).all() and np.isnan(got[3]).all() and np.isfinite(got[[0, 2]]).all()
+    check_rows(got[None], [x], [y], [0], res)
+
+
+# ---- bits ------------------------------------------------------------------------------------------------------------------------
+def test_emulated_bits_do_not_depend_on_the_batch_or_the_other_resolutions(emu):
+    rng = np.random.default_rng(7)
+    lens = [int(n) for n in rng.integers(1100, 9000, 7)]
+    tg = [_noise(rng, n) for n in lens]
+    ests = [_near(rng, t, 0.3) for t in tg]
+    batch = run_emu(emu, tg, ests, range(7))
+    check_rows(batch, tg, ests, range(7))
+    for i in (0, 3, 6):                                             # alone, and at another position of another batch
+        np.testing.assert_array_equal(run_emu(emu, [tg[i]], [ests[i]], [0])[0], batch[i])
+    order = [4, 6, 0, 5]
+    np.testing.assert_array_equal(run_emu(emu, [tg[i] for i in order], [ests[i] for i in order], range(4)), batch[order])
+    # multi (several estimates of one target through tgt_index) equals single calls
+    more = [_near(rng, tg[2], 0.1) for _ in range(3)]
+    multi = run_emu(emu, [tg[1], tg[2]], more + [ests[1]], [1, 1, 1, 0])
+    for k in range(3):
+        np.testing.assert_array_equal(multi[k], run_emu(emu, [tg[2]], [more[k]], [0])[0])
+    np.testing.assert_array_equal(multi[3], batch[1])
+    # a resolution's row does not depend on which other resolutions are asked for
+    for r, res in enumerate(DEFAULT):
+        np.testing.assert_array_equal(run_emu(emu, tg, ests, range(7), (res,))[:, 0], batch[:, r])
+    swapped = run_emu(emu, tg, ests, range(7), (DEFAULT[2], (256, 64, 256), DEFAULT[0]))
+    np.testing.assert_array_equal(swapped[:, 0], batch[:, 2])
+    np.testing.assert_array_equal(swapped[:, 2], batch[:, 0])
+    # float32 signals widened by the caller: the same bits in every dtype combination
+    for dt in ((np.float32, np.float64), (np.float64, np.float32), (np.float64, np.float64)):
+        np.testing.assert_array_equal(run_emu(emu, [t.astype(dt[0]) for t in tg], [e.astype(dt[1]) for e in ests], range(7)), batch)
+    t64 = [_noise(rng, n, np.float64) + 1e-9 for n in lens[:3]]     # float64 signals that are no float32 values
+    e32 = [_near(rng, t).astype(np.float32) for t in t64]
+    check_rows(run_emu(emu, t64, e32, range(3)), t64, e32, range(3))
+
+
+# ---- C ABI argument checks (no device call happens before any of these errors) ------------------------------------------------
+_DUMMY = C.c_void_p(0x1000)       # never dereferenced: every call below fails its host-side checks first
+
+
+def _i32(a):
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    return a, a.ctypes.data_as(C.c_void_p)
+
+
+def _call(lib, tl, idx, res=((1024, 120, 600),), bins=None, eps=1e-7, n_res=None, n_est=None, ws=_DUMMY, ws_bytes=1 << 30, out=_DUMMY,
+          null=()):
+    tl, tp = _i32(tl)
+    idx, ip = _i32(idx)
+    tab = _res_table(res, bins)
+    ptr = [None if j in null else tab[j].ctypes.data_as(C.c_void_p) for j in range(5)]
+    return lib.ssr_mrstft_metrics(_DUMMY, 0, _DUMMY, tp, len(tl), _DUMMY, 0, _DUMMY, ip, len(idx) if n_est is None else n_est,
+                                  len(res) if n_res is None else n_res, *ptr, eps, out, ws, ws_bytes, None)
+
+
+def test_mrstft_metrics_rejects_bad_arguments_before_launch():
+    from ssr_eval_amd import _lib
+    lib = _lib.load()
+    err = lambda: lib.ssr_last_error().decode()      # noqa: E731
+    E = _lib.ERR_INVALID_ARG
+    for n_res in (0, -1, 9):
+        assert _call(lib, [4000], [0], n_res=n_res) == E and "n_res" in err()
+    assert _call(lib, [4000], [0], res=((512, 128, 512),) * 9) == E and "n_res" in err()
+    for n_fft in (0, 128, 255, 1000, 4096, -1024):
+        assert _call(lib, [4000], [0], res=((n_fft, 64, 64),), bins=[(0, 0)]) == E and "n_fft" in err()
+    for hop in (0, -1, 1025):
+        assert _call(lib, [4000], [0], res=((1024, hop, 600),)) == E and "hop" in err()
+    for win in (1, 0, -5, 1025):
+        assert _call(lib, [4000], [0], res=((1024, 120, win),)) == E and "win" in err()
+    assert _call(lib, [4000], [0], res=((512, 128, 512), (1024, 120, 1025))) == E and "win" in err()      # the second resolution
+    for lo, hi in ((-1, 5), (6, 5), (0, 513), (513, 513)):
+        assert _call(lib, [4000], [0], bins=[(lo, hi)]) == E and "bin" in err()
+    for eps in (0.0, -1e-7, float("inf"), float("nan")):
+        assert _call(lib, [4000], [0], eps=eps) == E and "eps" in err()
+    for j in range(5):
+        assert _call(lib, [4000], [0], null=(j,)) == E and "null" in err()
+    assert _call(lib, [4000, 5000], [2]) == E and "tgt_index" in err()
+    assert _call(lib, [4000, 5000], [0, -1]) == E and "tgt_index" in err()
+    assert _call(lib, [-3], [0]) == E and "lengths" in err()
+    assert _call(lib, [1 << 29], [0]) == E and "lengths" in err()
+    assert _call(lib, [4000], [0], out=None) == E and "null" in err()
+    tl, tp = _i32([4000, 9000])
+    idx, ip = _i32([1, 1, 0])
+    tab = _res_table(DEFAULT, None)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    need = lib.ssr_mrstft_workspace_bytes(tp, 2, ip, 3, 3, P(tab[0]), P(tab[1]), P(tab[2]))
+    assert need > lib.ssr_mrstft_workspace_bytes(tp, 2, ip, 3, 2, P(tab[0]), P(tab[1]), P(tab[2])) > 0
+    assert _call(lib, [4000, 9000], [1, 1, 0], res=DEFAULT, ws_bytes=need - 1) == _lib.ERR_WORKSPACE and "workspace" in err()
+    assert _call(lib, [4000, 9000], [1, 1, 0], res=DEFAULT, ws=None) == _lib.ERR_WORKSPACE
+    bad, bp = _i32([2])
+    assert lib.ssr_mrstft_workspace_bytes(tp, 2, bp, 1, 3, P(tab[0]), P(tab[1]), P(tab[2])) == 0
+    assert lib.ssr_mrstft_workspace_bytes(tp, 2, ip, 3, 0, P(tab[0]), P(tab[1]), P(tab[2])) == 0
+    assert lib.ssr_mrstft_workspace_bytes(tp, 2, ip, 3, 3, P(tab[1]), P(tab[1]), P(tab[2])) == 0          # hops as n_fft
+    assert lib.ssr_mrstft_workspace_bytes(tp, 2, ip, 3, 3, P(tab[0]), P(tab[1]), None) == 0
+    assert _call(lib, [4000], [], n_est=0, ws=None, ws_bytes=0, out=None) == 0     # nothing to score: nothing queued
+
+
+def test_header_ctypes_table_and_library_agree():
+    import re
+    from ssr_eval_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ssr_hip.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(ssr_[a-z_0-9]+)\s*\(", src))
+    lib = _lib.load()
+    for name in ("ssr_mrstft_metrics", "ssr_mrstft_workspace_bytes"):
+        assert name in declared and name in _lib.SIGNATURES and hasattr(lib, name), name
+    assert declared == set(_lib.SIGNATURES)
+    assert "#define SSR_MRSTFT_MAX_RES 8" in src and _lib.MRSTFT_MAX_RES == 8
+
+
+# ---- AudioMetrics / SSR_Eval_Helper options --------------------------------------------------------------------------------------
+def test_audio_metrics_mrstft_options():
+    from ssr_eval_amd import AudioMetrics
+    from ssr_eval_amd import backend as B
+    am = AudioMetrics(48000)
+    assert B.MRSTFT_RESOLUTIONS == DEFAULT and B.MRSTFT_EPS == O.EPS
+    assert B.check_mrstft_resolutions(None) == DEFAULT
+    assert B.check_mrstft_resolutions([[256, np.int64(256), 2]]) == ((256, 256, 2),)
+    for bad in ((), "default", 1024, ((1024, 120),), ((1000, 120, 600),), ((4096, 120, 600),), ((1024, 0, 600),), ((1024, 1025, 600),),
+                ((1024, 120, 1),), ((1024, 120, 1025),), ((1024.0, 120, 600),), ((1024, True, 600),), ((512, 128, 512),) * 9,
+                ((512, 128, 512), None)):
+        with pytest.raises(ValueError):
+            B.check_mrstft_resolutions(bad)
+    for bad in (0, 0.0, -1e-7, float("inf"), float("nan"), None, "1e-7", True):
+        with pytest.raises(ValueError):
+            B.check_mrstft_eps(bad)
+    assert B.check_mrstft_eps(1) == 1.0 and B.check_mrstft_eps(np.float32(0.5)) == 0.5
+    # band -> bins per resolution by _phase_bins' rule: k_lo = ceil(lo N / rate), k_hi = floor(hi N / rate), clamped
+    assert am._mrstft_bins(48000, DEFAULT, None) is None
+    assert am._mrstft_bins(48000, DEFAULT, (4000, 8000)) == [(86, 170), (171, 341), (43, 85)]
+    assert am._mrstft_bins(48000, DEFAULT, (0, 1e9)) == [(0, 512), (0, 1024), (0, 256)]
+    assert am._mrstft_bins(16000, ((256, 64, 256),), (3000, 3000)) == [(48, 48)]
+    for band in ((8000, 4000), (3001, 3040), (24001, 30000), (1, 2, 3), "all", (None, 5)):
+        with pytest.raises(ValueError):
+            am._mrstft_bins(48000, DEFAULT, band)
+    with pytest.raises(ValueError):                                  # a bin of the 2048-point transform, none of the 512-point one
+        am._mrstft_bins(48000, DEFAULT, (3001, 3030))
+    assert am._mrstft_bins(48000, DEFAULT[1:2], (3001, 3030)) == [(129, 129)]
+    x = np.zeros(3000, np.float32)
+    for kw in ({"resolutions": ((300, 10, 20),)}, {"resolutions": ()}, {"band": (5, 1)}, {"eps": 0}, {"eps": float("nan")},
+               {"band": (3001, 3030)}):                              # rejected before any device is touched
+        with pytest.raises(ValueError):
+            am.mrstft(x, x, **kw)
+        with pytest.raises(ValueError):
+            am.mrstft_batch([x], [x], **kw)
+        with pytest.raises(ValueError):
+            am.mrstft_multi([[x]], [x], **kw)
+
+
+def test_helper_mrstft_option_and_metric_order():
+    from ssr_eval_amd import SSR_Eval_Helper, BasicTestee
+    from ssr_eval_amd import eval as E
+    mk = lambda **kw: SSR_Eval_Helper(BasicTestee(), 44100, 44100, test_data_root=None, **kw)      # noqa: E731
+    # (that mrstft=None leaves a result dict identical is checked where evaluate() can run, on the GPU:
+    # tests/test_gpu_mrstft.py::test_evaluate_with_mrstft_and_bootstrap_from_wav_files; here: None is the default and stays None)
+    assert mk().mrstft is None and mk(mrstft=None).mrstft is None
+    for ok in (True, {"resolutions": ((512, 128, 512),)}, {"band": (4000, 16000)}, {"eps": 1e-5},
+               {"resolutions": [(256, 64, 256), (2048, 2048, 2)], "band": (0, 1e6), "eps": 1}):
+        assert mk(mrstft=ok).mrstft == ok
+    for bad in (False, "all", 1, (), ((512, 128, 512),), {}, {"which": "all"}, {"n_fft": 512}, {"resolutions": ((1000, 10, 10),)},
+                {"resolutions": ()}, {"resolutions": ((512, 128, 512),) * 9}, {"band": (8000, 4000)}, {"band": 4000},
+                {"band": (3001, 3010)}, {"eps": 0}, {"eps": "x"}, {"eps": float("inf")}):
+        with pytest.raises(ValueError):
+            mk(mrstft=bad)
+    # the order pinned before this family existed stays; the new keys follow it in all_key_order()
+    assert E._MRSTFT_KEYS == ("mrstft_sc", "mrstft_mag", "mrstft")
+    names = [f[0] for f in E._FAMILIES]
+    assert names == ["lsd_split", "stoi", "waveform", "mel", "mel_dtw", "quality", "pitch", "phase"]
+    assert [f[0] for f in E._LATER_FAMILIES] == ["mrstft"]
+    order = E.result_key_order()
+    assert order == ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi", "estoi", "snr", "si_sdr", "seg_snr", "mel_lsd",
+                     "mel_l1", "mcd", "mcd_dtw", "dtw_dev", "llr", "cep_dist", "wss", "fwseg_snr", "f0_rmse", "f0_corr", "gpe", "vde",
+                     "ffe", "phase_ip", "phase_gd", "phase_iaf")
+    assert E.all_key_order() == order + E._MRSTFT_KEYS and len(set(E.all_key_order())) == len(order) + 3
+    args = E._LATER_FAMILIES[0][3]
+    assert args(mk(mrstft=True), ["k"]) == ((None, None, 1e-7), {})
+    assert args(mk(mrstft={"band": (0, 8000), "eps": 1e-5}), ["k"]) == ((None, (0, 8000), 1e-5), {})
