@@ -248,7 +248,8 @@ int ssr_spectrogram_lsd_bands(const float* est_sp, const int64_t* est_frame_off,
  * target, whose image is not rewritten) - the magnitudes of ssr_pair_metrics_multi - and the band reduction runs on the images.
  * Bands [0, n_bins) give ssr_pair_metrics' LSD to <= 1e-6 relative.  out: double [n_items][n_keys][n_bands].
  * The workspace holds K + 1 magnitude images of the batch (8 (K + 1) * total_rows * n_bins bytes, rows padded to 16 bytes): callers
- * with many keys run them in chunks.  ssr_pair_lsd_bands_workspace_bytes serves both entry points. */
+ * with many keys run them in chunks.  ssr_pair_lsd_bands_workspace_bytes serves both entry points, and both ask for all of it
+ * (SSR_ERR_WORKSPACE for a byte less, whichever layout the call at hand uses). */
 size_t ssr_pair_lsd_bands_workspace_bytes(const ssr_plan* plan, int n_items, int n_keys, int max_len, int64_t total_rows, int n_bands);
 int ssr_pair_lsd_bands(const ssr_plan* plan, const float* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
                        const int32_t* len, const int64_t* frame_off, int n_items, int n_keys, int max_len, int64_t total_rows,
@@ -331,7 +332,7 @@ int ssr_spectrogram_mel_metrics(const float* est_sp, const int64_t* est_frame_of
                                 const int32_t* n_rows, int n_images, int max_rows, int n_bins, const float* fb, int n_mels, int n_cep,
                                 int which, double* out, void* workspace, size_t workspace_bytes, void* stream);
 /* Waveform level, the descriptors of ssr_pair_lsd_bands: the K + 1 magnitude images of ssr_pair_lsd_bands (n_bins = the plan's),
- * then the reduction.  ssr_pair_mel_metrics_workspace_bytes serves both entry points. */
+ * then the reduction.  ssr_pair_mel_metrics_workspace_bytes serves both entry points, and both ask for all of it. */
 size_t ssr_pair_mel_metrics_workspace_bytes(const ssr_plan* plan, int n_items, int n_keys, int max_len, int64_t total_rows, int n_mels,
                                             int n_cep);
 int ssr_pair_mel_metrics(const ssr_plan* plan, const float* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,
@@ -366,7 +367,7 @@ int ssr_spectrogram_mel_dtw(const float* est_sp, const int64_t* est_frame_off, c
                             const int32_t* n_rows, int n_images, int max_rows, int n_bins, const float* fb, int n_mels, int n_cep,
                             int radius, double* out, void* workspace, size_t workspace_bytes, void* stream);
 /* Waveform level, the descriptors of ssr_pair_mel_metrics with `radius` for `which` (the images are ssr_pair_mel_metrics' own).
- * ssr_pair_mel_dtw_workspace_bytes serves both entry points. */
+ * ssr_pair_mel_dtw_workspace_bytes serves both entry points, and both ask for all of it. */
 size_t ssr_pair_mel_dtw_workspace_bytes(const ssr_plan* plan, int n_items, int n_keys, int max_len, int64_t total_rows, int n_mels,
                                         int n_cep, int radius);
 int ssr_pair_mel_dtw(const ssr_plan* plan, const float* est, const int64_t* est_off, const float* tgt, const int64_t* tgt_off,

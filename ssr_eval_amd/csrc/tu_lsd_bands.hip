@@ -126,7 +126,9 @@ static int pair_lsd_bands_impl(const ssr_plan* pl, const float* est, const doubl
   if (!max_T) return SSR_OK;
   if (int rc = check_edges(edges, (int64_t)n_items * n_keys, n_bands, pl->n_bins)) return rc;
   const BandWs w = band_ws(pl, n_items, n_keys, max_len, total_rows, n_bands, est64 != nullptr);
-  if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
+  // the contract is the size the query reports - one size for both entry points - not this layout's own (smaller or equal) need
+  if (!workspace || workspace_bytes < ssr_pair_lsd_bands_workspace_bytes(pl, n_items, n_keys, max_len, total_rows, n_bands))
+    return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
   char* ws = (char*)workspace;
   hipStream_t s = (hipStream_t)stream;
   int32_t* rows = (int32_t*)(ws + w.off_rows);

@@ -226,7 +226,9 @@ static int pair_mel_impl(const ssr_plan* pl, const float* est, const double* est
     return rc;
   if (!max_T) return SSR_OK;
   const MelWs w = mel_ws(pl, n_items, n_keys, max_len, total_rows, n_mels, n_cep, est64 != nullptr);
-  if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
+  // the contract is the size the query reports - one size for both entry points - not this layout's own (smaller or equal) need
+  if (!workspace || workspace_bytes < ssr_pair_mel_metrics_workspace_bytes(pl, n_items, n_keys, max_len, total_rows, n_mels, n_cep))
+    return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
   char* ws = (char*)workspace;
   hipStream_t s = (hipStream_t)stream;
   SsrMelParams p{};

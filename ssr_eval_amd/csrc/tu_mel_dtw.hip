@@ -121,7 +121,9 @@ static int pair_dtw_impl(const ssr_plan* pl, const float* est, const double* est
   if (!max_T) return SSR_OK;
   if (total_rows < 1) return ssr_fail(SSR_ERR_INVALID_ARG, "total_rows must be the batch's frames");
   const DtwWs w = dtw_ws(pl, n_items, n_keys, max_len, total_rows, n_mels, n_cep, est64 != nullptr);
-  if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
+  // the contract is the size the query reports - one size for both entry points - not this layout's own (smaller or equal) need
+  if (!workspace || workspace_bytes < ssr_pair_mel_dtw_workspace_bytes(pl, n_items, n_keys, max_len, total_rows, n_mels, n_cep, radius))
+    return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
   char* ws = (char*)workspace;
   hipStream_t s = (hipStream_t)stream;
   SsrMelCepParams c{};
