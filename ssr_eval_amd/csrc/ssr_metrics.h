@@ -72,6 +72,8 @@ template <int CPT> SSR_DEV int ssr_ssim_slot_of(int tid, int d) { return (CPT % 
 // operations of the single wave execute in order), which makes room for a seven-row ring of the y pixels (rows of RW floats:
 // the thread's own four columns as one 16-byte slot at 4 tid, the strip's extra columns at 256 + tid) at twelve waves per CU:
 // 7,392 + 2,648 + 704 B per wave against 11,296 B with four column arrays and no ring.
+// The eight-column variant (CPT = 8: wide images, ssim_geom in tu_metrics.hip) takes 19,952 B per wave: eight waves per CU, the two
+// per SIMD its 250 VGPRs allow.
 template <int CPT, bool CONTIG = false> struct SsrSsimLds {
   static constexpr int PW = SSR_SSIM_NT * CPT + 8 + ((CPT % 2 == 0) ? (SSR_SSIM_NT * CPT + 8) / CPT + 1 : 0);
   static constexpr int NQ = CONTIG ? 1 : 4;
@@ -427,26 +429,31 @@ SSR_BODY void ssr_ssim_body(const SsrSsimParams& p, BLK& blk, int tile, int item
             }                                                                                                                \
           }                                                                                                                  \
           /* fold the quantity into the SSIM expression at once (ssr_ssim_value's stages): two live values per output.       \
-             The thread's four float32 values of a row are added in float32 (values in [-1, 1]: 1e-7 per row, unbiased,    \
-             against the 1e-5 bar on the mean) and join the float64 sum once. */                                             \
+             The four float32 values of an aligned quad of a row are added in float32 (values in [-1, 1]: 1e-7 per row,    \
+             unbiased, against the 1e-5 bar on the mean) and join the float64 sum once.  The eight-column variant adds its  \
+             two quads separately - those of four-column lanes 2 tid and 2 tid + 1 - so every float32 rounding is the     \
+             four-column kernel's and an item's sum differs from it by the order of the float64 additions alone. */        \
           const int j0 = tid * CPT;                                                                                          \
-          float row_s = 0.0f;                                                                                                \
-          SSR_UNROLL for (int i = 0; i < CPT; ++i) {                                                                         \
-            if (q == 0) R.pxy[i] = wq[i];                                                                                    \
-            if (q == 1) { const double sx = R.pxy[i]; ssr_ssim_stage1(sx, wq[i], R.pxy[i], R.pb[i]); }                       \
-            if (q == 2) R.den[i] = ssr_ssim_stage2f(R.pb[i], wq[i]);                                                         \
-            if (q == 3) {                                                                                                    \
-              const float sv = ssr_ssim_stage3f(R.pxy[i], wq[i], R.den[i]);                                                  \
-              row_s += (j0 + i < ncol_out) ? sv : 0.0f;                                                                      \
+          SSR_UNROLL for (int h = 0; h < CPT / 4; ++h) {                                                                     \
+            float row_s = 0.0f;                                                                                              \
+            SSR_UNROLL for (int i = 4 * h; i < 4 * h + 4; ++i) {                                                             \
+              if (q == 0) R.pxy[i] = wq[i];                                                                                  \
+              if (q == 1) { const double sx = R.pxy[i]; ssr_ssim_stage1(sx, wq[i], R.pxy[i], R.pb[i]); }                     \
+              if (q == 2) R.den[i] = ssr_ssim_stage2f(R.pb[i], wq[i]);                                                       \
+              if (q == 3) {                                                                                                  \
+                const float sv = ssr_ssim_stage3f(R.pxy[i], wq[i], R.den[i]);                                                \
+                row_s += (j0 + i < ncol_out) ? sv : 0.0f;                                                                    \
+              }                                                                                                              \
             }                                                                                                                \
+            if (q == 3) R.s += (double)row_s;                                                                                \
           }                                                                                                                  \
-          if (q == 3) R.s += (double)row_s;                                                                                  \
         });                                                                                                                  \
       }                                                                                                                      \
     }
     // ring slot = step mod 7, prefetch set = step mod 2: all indices static.  Steps 0 .. 5 fill the window (n_steps >= 7; no
     // column-sum hand-off yet); then whole trips of fourteen steps in a loop without a branch inside it - the steady state: every
-    // step waits with vmcnt(7) / (5) / (4), the youngest request (four loads) always stays in flight, 148 VGPRs; then the tile's
+    // step waits with vmcnt(7) / (5) / (4), the youngest request (four loads) always stays in flight, 148 VGPRs (eight columns: six
+    // loads per request, vmcnt(11) / (9) / (8) / (6), 250 VGPRs - tests/test_ssim_wide_isa.py); then the tile's
     // last, short trip, which leaves at its first missing step (forward branches to ONE exit: no join on the way, so this copy
     // keeps its rows in flight as well).  A single loop of fourteen steps with such exits is half the code, but measured 1 %
     // slower: the compiler routes the exits through the loop latch and the first step of every trip waits vmcnt(0).

@@ -4,8 +4,9 @@
 #include "ssr_metrics.h"
 #include "ssr_pair_transform.h"
 
+// (the eight-column CONTIG variant is compiled for two waves per SIMD - 256 VGPRs; every other variant as before)
 template <int CPT, bool CONTIG>
-__global__ __launch_bounds__(SSR_SSIM_NT, 1) void k_ssim(SsrSsimParams p) {
+__global__ __launch_bounds__(SSR_SSIM_NT, (CPT == 8 ? 2 : 1)) void k_ssim(SsrSsimParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   SsrBlk blk{(int)threadIdx.x};
   const int tiles = p.n_row_tiles * p.n_strips;
@@ -45,6 +46,17 @@ static SsimGeom ssim_geom(int max_rows, int n_bins, int n_items, bool aligned_ro
       const int strips4 = ssr_ceil_div(outs, ssr_ssim_strip_out(4)), strips_c = ssr_ceil_div(outs, ssr_ssim_strip_out(g.cpt));
       if (strips4 * 5 * 68 < strips_c * (g.cpt + 1) * 100) g.cpt = 4;
     }
+  }
+  if (aligned_rows && g.cpt == 4) {
+    // Eight consecutive columns per lane (k_ssim<8, true>: strips of 512 outputs, two waves per SIMD instead of three).  The kernel
+    // is issue-bound, so a strip row is priced by the instructions of the steady fourteen-step trip of the compiled loops:
+    // SSR_SSIM_TRIP4 for 256 outputs against SSR_SSIM_TRIP8 for 512 (disassembly of the shipped code objects,
+    // profiles/ssim_wide_notes.md).  F = 1025: 2 x 6371 < 4 x 3731 and F = 513: 1 x 6371 < 2 x 3731 take eight columns;
+    // F = 1115: 3 x 6371 > 5 x 3731 stays on four.
+    constexpr int SSR_SSIM_TRIP4 = 3731, SSR_SSIM_TRIP8 = 6371;
+    const int outs = n_bins - (SSR_SSIM_WIN - 1);
+    if (outs > 0 && ssr_ceil_div(outs, ssr_ssim_strip_out(8)) * SSR_SSIM_TRIP8 < ssr_ceil_div(outs, ssr_ssim_strip_out(4)) * SSR_SSIM_TRIP4)
+      g.cpt = 8;
   }
   g.n_strips = n_bins > 6 ? ssr_ceil_div(n_bins - 6, ssr_ssim_strip_out(g.cpt)) : 1;
   return g;
@@ -100,9 +112,13 @@ static int launch_ssim(const float* x, const float* y, const int64_t* frame_off,
                        int F, int pitch, const SsimGeom& g, double* part, hipStream_t s, int vi_n = 0, int64_t x_plane = 0) {
   SsrSsimParams p{x, y, frame_off, n_rows, F, g.rows_per_tile, g.n_row_tiles, g.n_strips, part, pitch, vi_n, x_plane};
   const int grid = n_items * g.n_row_tiles * g.n_strips;
-  // four consecutive columns per thread through aligned 16-byte loads: rows and both bases 16-byte aligned
-  if (g.cpt == 4 && pitch > 0 && pitch % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0)
-    return launch_ssim_inst<4, true>(p, grid, s);
+  // four or eight consecutive columns per thread through aligned 16-byte loads: rows and both bases 16-byte aligned
+  const bool contig = pitch > 0 && pitch % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+  if (g.cpt == 8) {                // chosen for aligned rows only (ssim_geom), and it has no strided form
+    if (!contig) return ssr_fail(SSR_ERR_UNSUPPORTED, "eight-column SSIM geometry on unaligned rows");
+    return launch_ssim_inst<8, true>(p, grid, s);
+  }
+  if (g.cpt == 4 && contig) return launch_ssim_inst<4, true>(p, grid, s);
   switch (g.cpt) {
     case 1: return launch_ssim_inst<1>(p, grid, s);
     case 2: return launch_ssim_inst<2>(p, grid, s);
