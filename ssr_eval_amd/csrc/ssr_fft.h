@@ -17,6 +17,7 @@
 // powers with one complex multiply each (error <= 2 ulp of the working type).
 #pragma once
 #include "ssr_block.h"
+#include <vector>
 
 template <typename T> SSR_DEV void ssr_bfly2(cx<T>* v) {
   cx<T> a = v[0], b = v[1];
@@ -210,4 +211,31 @@ SSR_BODY void ssr_fft_mid_passes(BLK& blk, REGS& regs, T* re, T* im, const TW& t
     SSR_PHASE(blk, regs, ssr_fft_load<T, LOGN, PASS, PPT>(tid, re, im, R.v);
               ssr_fft_compute<T, LOGN, PASS, PPT>(tid, R.v, tw));
   }
+}
+
+// The transform finished to natural order: passes 1 .. NPASS - 1 after the caller's phase loaded, computed and stored pass 0,
+// the last pass stored like the others - re[ssr_pad(k)], im[ssr_pad(k)] = Z[k] once the closing barrier has passed.
+// Regs must expose `cx<double> v[8]`.
+template <int LOGN, typename BLK, typename REGS, typename TW>
+SSR_BODY void ssr_fft_finish_natural(BLK& blk, REGS& regs, double* re, double* im, const TW& tw) {
+  ssr_fft_mid_passes<double, LOGN, 1, 8>(blk, regs, re, im, tw);
+  SSR_PHASE(blk, regs, ssr_fft_store<double, LOGN, SsrFftPlan<LOGN>::NPASS - 1>(tid, re, im, R.v));
+}
+
+// Two real signals packed into one complex frame, in first-pass register order: frame t (hop H, centred, reflect-padded) of x
+// (n samples) times the window into the real parts, of y into the imaginary parts.  w[r]: the window at ssr_fft_first_index(tid, r).
+template <int LOGN, typename TT, typename TE>
+SSR_DEV void ssr_fft_load_packed_frame(int tid, const double* w, const TT* x, const TE* y, int t, int H, int n, cx<double>* v) {
+  SSR_UNROLL for (int r = 0; r < 8; ++r) {
+    const int i = ssr_reflect(t * H + ssr_fft_first_index<LOGN>(tid, r) - (1 << LOGN) / 2, n);
+    v[r] = {w[r] * (double)x[i], w[r] * (double)y[i]};
+  }
+}
+
+// host table: the transform's twiddles tw[i] = exp(-2 pi i i / N) (long double, rounded once).  Named after its first user,
+// the phase distances; ssr_quality.h and ssr_mrstft.h build the same table
+static inline void ssr_phase_twiddles_host(int N, std::vector<cx<double>>& tw) {
+  const long double two_pi = 6.283185307179586476925286766559005768L;
+  tw.resize(N);
+  for (int i = 0; i < N; ++i) tw[i] = {(double)cosl(two_pi * i / N), (double)-sinl(two_pi * i / N)};
 }

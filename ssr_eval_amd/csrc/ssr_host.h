@@ -8,11 +8,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/ssr_hip.h"
 #include "ssr_block.h"
+#include "ssr_fft.h"
 #include "ssr_tables.h"
 
 int ssr_fail(int code, const std::string& msg);   // records the thread-local message behind ssr_last_error()
@@ -20,6 +23,12 @@ int ssr_fail(int code, const std::string& msg);   // records the thread-local me
   do {                                                                                             \
     hipError_t e_ = (expr);                                                                        \
     if (e_ != hipSuccess) return ssr_fail(SSR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+// a kernel launch and its error check: SSR_LAUNCH((k_name<A, B>), grid, block, stream, args...) - no dynamic LDS
+#define SSR_LAUNCH(kernel, grid, block, stream, ...)                                               \
+  do {                                                                                             \
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                               \
+    HIP_TRY(hipGetLastError());                                                                    \
   } while (0)
 
 template <typename T> struct DevTables {
@@ -114,7 +123,8 @@ inline bool ssr_multi_fast_path(const ssr_plan* pl, bool est64) {
   return ssr_stft_uses_wave_engine(pl, false) || ssr_stft_rn_wave_radix(pl) != 0;
 }
 
-// ---- the per-pair families (tu_stoi / tu_wave_metrics / tu_quality / tu_pitch): estimate e is scored against target tgt_index[e] ----
+// ---- the per-pair families (tu_stoi / tu_wave_metrics / tu_quality / tu_pitch / tu_phase / tu_mrstft): estimate e is scored
+// against target tgt_index[e].  The device side of what they share is ssr_pairs.h ----
 // host-side validation of the two descriptor arrays (host memory): lengths in [0, len_limit), indices in [0, n_tgt)
 inline int ssr_check_pair_index(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int64_t len_limit,
                                 const char* len_msg, const char* count_msg = "n_tgt and n_est must be >= 0") {
@@ -134,12 +144,46 @@ inline int ssr_upload_pair_index(const int32_t* tgt_len, int n_tgt, const int32_
   HIP_TRY(hipMemcpyAsync(idx_dev, tgt_index, (size_t)n_est * sizeof(int32_t), hipMemcpyHostToDevice, s));
   return SSR_OK;
 }
-// f(TT{}, TE{}) with the element types of the target and estimate buffers: (float | double) x (float | double)
-template <typename F> inline void ssr_dispatch_pair_dtypes(bool tgt_f64, bool est_f64, F&& f) {
-  if (!tgt_f64 && !est_f64) f(float{}, float{});
-  else if (!tgt_f64) f(float{}, double{});
-  else if (!est_f64) f(double{}, float{});
-  else f(double{}, double{});
+// the signal buffers of an entry point that reads float32 or float64 signals where they lie (checked after the descriptors:
+// an empty batch has returned by then); the signals themselves may be absent where no target has a sample
+inline int ssr_check_pair_buffers(const void* tgt, const int64_t* tgt_off, const void* est, const int64_t* est_off, const void* out,
+                                  const int32_t* tgt_len, int n_tgt) {
+  int64_t samples = 0;
+  for (int t = 0; t < n_tgt; ++t) samples += tgt_len[t];
+  if (!tgt_off || !est_off || !out || (samples > 0 && (!tgt || !est))) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  return SSR_OK;
+}
+// f(TT{}, TE{}) with the element types of the target and estimate buffers: (float | double) x (float | double); -> f's value
+template <typename F> inline auto ssr_dispatch_pair_dtypes(bool tgt_f64, bool est_f64, F&& f) {
+  if (!tgt_f64 && !est_f64) return f(float{}, float{});
+  if (!tgt_f64) return f(float{}, double{});
+  if (!est_f64) return f(double{}, float{});
+  return f(double{}, double{});
+}
+// a workspace carved area after area, each rounded to 256 bytes: take() -> the area's offset; o: the bytes so far
+struct SsrWsLayout {
+  size_t o = 0;
+  size_t take(size_t bytes) { const size_t at = o; o += ssr_align256(bytes); return at; }
+};
+// host tables by key: built on first use under a lock, never written again - the reference holds for the life of the process
+// (the asynchronous copies into a workspace read them after the entry point has returned)
+template <typename K, typename V> struct SsrHostTables {
+  std::mutex mu;
+  std::map<K, V> cache;
+  template <typename B> const V& get(const K& key, B&& build) {
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find(key);
+    if (it == cache.end()) {
+      it = cache.emplace(key, V{}).first;
+      build(it->second);
+    }
+    return it->second;
+  }
+};
+// the twiddles of an n_fft-point transform (ssr_phase_twiddles_host): one cache for every family that transforms frames
+inline const std::vector<cx<double>>& ssr_twiddles_cached(int n_fft) {
+  static SsrHostTables<int, std::vector<cx<double>>> tables;
+  return tables.get(n_fft, [&](std::vector<cx<double>>& tw) { ssr_phase_twiddles_host(n_fft, tw); });
 }
 
 // ---- launchers defined by the kernel translation units --------------------------------------------------------

@@ -76,8 +76,8 @@ struct SsrMrstftRegs {
 template <typename TT, typename TE, int LOGN, typename BLK>
 SSR_BODY void ssr_mrstft_dist_body(const SsrMrstftSig& p, const SsrMrstftRes& q, double eps, BLK& blk, int64_t g, SsrMrstftLds<LOGN>& S) {
   using PL = SsrFftPlan<LOGN>;
-  constexpr int N = PL::N, NT = PL::NT, LAST = PL::NPASS - 1, NW = (NT + 63) / 64;
-  const int e = ssr_phase_find(q.chunk_off, p.n_est, g);
+  constexpr int N = PL::N, NT = PL::NT, NW = (NT + 63) / 64;
+  const int e = ssr_prefix_find(q.chunk_off, p.n_est, g);
   const int ch = (int)(g - q.chunk_off[e]);
   const int ti = p.tgt_index[e];
   const int n = p.tgt_len[ti], H = q.H;
@@ -96,10 +96,7 @@ SSR_BODY void ssr_mrstft_dist_body(const SsrMrstftSig& p, const SsrMrstftRes& q,
   for (int t = t0; t < t1; ++t) {
     ssr_launder(blk);     // (per-pass LDS addresses are recomputed where used, not hoisted across the frame loop)
     SSR_PHASE(blk, regs, {
-      SSR_UNROLL for (int r = 0; r < 8; ++r) {
-        const int i = ssr_reflect(t * H + ssr_fft_first_index<LOGN>(tid, r) - N / 2, n);
-        R.v[r] = {R.w[r] * (double)x[i], R.w[r] * (double)y[i]};
-      }
+      ssr_fft_load_packed_frame<LOGN>(tid, R.w, x, y, t, H, n, R.v);
       // what is exact about the two windowed frames and what the packed transform would round away: a silent frame has a zero
       // spectrum (next to a loud frame the split returns the loud one's rounding error for it), equal frames have equal spectra
       bool lx = false, ly = false, df = false;
@@ -112,14 +109,7 @@ SSR_BODY void ssr_mrstft_dist_body(const SsrMrstftSig& p, const SsrMrstftRes& q,
       ssr_fft_compute<double, LOGN, 0>(tid, R.v, tw);
       ssr_fft_store<double, LOGN, 0>(tid, S.re, S.im, R.v);
     });
-    ssr_fft_mid_passes<double, LOGN, 1, 8>(blk, regs, S.re, S.im, tw);
-    SSR_PHASE(blk, regs, {
-      SSR_UNROLL for (int r = 0; r < 8; ++r) {
-        const int k = ssr_fft_out_index<LOGN, LAST>(tid, r);
-        S.re[ssr_pad(k)] = R.v[r].x;
-        S.im[ssr_pad(k)] = R.v[r].y;
-      }
-    });
+    ssr_fft_finish_natural<LOGN>(blk, regs, S.re, S.im, tw);
     SSR_PHASE(blk, regs, {
       // X[k] = (Z[k] + conj(Z[N - k])) / 2, Y[k] = (Z[k] - conj(Z[N - k])) / (2 i); at k = 0 and k = N / 2 the two are the real
       // and the imaginary part of Z[k] themselves

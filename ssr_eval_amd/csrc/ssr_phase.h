@@ -19,9 +19,8 @@
 // alone, in any batch and at any position; the three sums never mix, so a subset of `which` gives the bits of the full call.
 // There are no atomics.  All bodies compile on the host too (SSR_HOST_EMU, tests/emu/phase_emu.cpp).
 #pragma once
-#include "ssr_block.h"
+#include "ssr_pairs.h"
 #include "ssr_fft.h"
-#include <vector>
 
 #define SSR_PHASE_IP 1
 #define SSR_PHASE_GD 2
@@ -35,8 +34,6 @@
 // T = 1 + n // H centred frames; none where the reflect padding of N / 2 samples is undefined (n <= N / 2)
 SSR_HD int ssr_phase_frames(int n, int N, int H) { return n > N / 2 ? 1 + n / H : 0; }
 SSR_HD int ssr_phase_chunks(int n, int N, int H) { return (ssr_phase_frames(n, N, H) + SSR_PHASE_FR - 1) / SSR_PHASE_FR; }
-SSR_HD int ssr_phase_popcount(int which) { return (which & 1) + ((which >> 1) & 1) + ((which >> 2) & 1); }
-SSR_HD int ssr_phase_col(int which, int bit) { return ssr_phase_popcount(which & (bit - 1)); }
 // log2 of n_fft, or -1 where n_fft is not 256, 512, 1024 or 2048
 SSR_HD int ssr_phase_log2_nfft(int n_fft) {
   for (int g = SSR_PHASE_LOGN_MIN; g <= SSR_PHASE_LOGN_MAX; ++g)
@@ -58,16 +55,6 @@ struct SsrPhaseParams {
   double* part;                 // [chunk_off[n_est]][3] chunk sums: IP, GD, IAF
   double* out;                  // [n_est][popcount(which)]
 };
-
-// largest s in [0, n) with off[s] <= g (off ascending, off[0] = 0)
-SSR_HD int ssr_phase_find(const int64_t* off, int n, int64_t g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // the anti-wrapping distance of the phase of z from 0: |arg z| in [0, pi]; 0 at z = 0 whatever the signs of its zeros
 SSR_HD double ssr_phase_a(cx<double> z) { return (z.x == 0.0 && z.y == 0.0) ? 0.0 : fabs(atan2(z.y, z.x)); }
@@ -117,8 +104,8 @@ struct SsrPhaseRegs {
 template <typename TT, typename TE, int LOGN, typename BLK>
 SSR_BODY void ssr_phase_dist_body(const SsrPhaseParams& p, BLK& blk, int64_t g, SsrPhaseLds<LOGN>& S) {
   using PL = SsrFftPlan<LOGN>;
-  constexpr int N = PL::N, NT = PL::NT, LAST = PL::NPASS - 1, NW = (NT + 63) / 64;
-  const int e = ssr_phase_find(p.chunk_off, p.n_est, g);
+  constexpr int N = PL::N, NT = PL::NT, NW = (NT + 63) / 64;
+  const int e = ssr_prefix_find(p.chunk_off, p.n_est, g);
   const int ch = (int)(g - p.chunk_off[e]);
   const int ti = p.tgt_index[e];
   const int n = p.tgt_len[ti], H = p.H;
@@ -140,10 +127,7 @@ SSR_BODY void ssr_phase_dist_body(const SsrPhaseParams& p, BLK& blk, int64_t g, 
     const bool score = t >= t0, iaf_now = iaf && score && t > tb;
     ssr_launder(blk);     // (per-pass LDS addresses are recomputed where used, not hoisted across the frame loop)
     SSR_PHASE(blk, regs, {
-      SSR_UNROLL for (int r = 0; r < 8; ++r) {
-        const int i = ssr_reflect(t * H + ssr_fft_first_index<LOGN>(tid, r) - N / 2, n);
-        R.v[r] = {R.w[r] * (double)x[i], R.w[r] * (double)y[i]};
-      }
+      ssr_fft_load_packed_frame<LOGN>(tid, R.w, x, y, t, H, n, R.v);
       // a frame of digital silence has a zero spectrum; packed next to a loud frame the split would return the loud one's
       // rounding error for it instead, so such a frame is found here and its C set to zero below
       bool lx = false, ly = false;
@@ -153,14 +137,7 @@ SSR_BODY void ssr_phase_dist_body(const SsrPhaseParams& p, BLK& blk, int64_t g, 
       ssr_fft_compute<double, LOGN, 0>(tid, R.v, tw);
       ssr_fft_store<double, LOGN, 0>(tid, S.re, S.im, R.v);
     });
-    ssr_fft_mid_passes<double, LOGN, 1, 8>(blk, regs, S.re, S.im, tw);
-    SSR_PHASE(blk, regs, {
-      SSR_UNROLL for (int r = 0; r < 8; ++r) {
-        const int k = ssr_fft_out_index<LOGN, LAST>(tid, r);
-        S.re[ssr_pad(k)] = R.v[r].x;
-        S.im[ssr_pad(k)] = R.v[r].y;
-      }
-    });
+    ssr_fft_finish_natural<LOGN>(blk, regs, S.re, S.im, tw);
     SSR_PHASE(blk, regs, {
       // X[k] = (Z[k] + conj(Z[N - k])) / 2, Y[k] = (Z[k] - conj(Z[N - k])) / (2 i); at k = 0 and k = N / 2 the two are the real
       // and the imaginary part of Z[k] themselves and C is their real product
@@ -222,16 +199,9 @@ template <typename BLK> SSR_BODY void ssr_phase_finalize_body(const SsrPhasePara
         s[0] += p.part[3 * g]; s[1] += p.part[3 * g + 1]; s[2] += p.part[3 * g + 2];
       }
       const int64_t cells[3] = {T * nb, T * (nb - 1), (T - 1) * nb};
-      double* o = p.out + (int64_t)e * ssr_phase_popcount(p.which);
+      double* o = p.out + (int64_t)e * ssr_which_count(p.which);
       for (int m = 0; m < 3; ++m)
         if (p.which & (1 << m)) *o++ = (T > 0 && cells[m] > 0) ? s[m] / (double)cells[m] : (double)NAN;
     }
   });
-}
-
-// ---- host table: the transform's twiddles (long double, rounded once)
-static inline void ssr_phase_twiddles_host(int N, std::vector<cx<double>>& tw) {
-  const long double two_pi = 6.283185307179586476925286766559005768L;
-  tw.resize(N);
-  for (int i = 0; i < N; ++i) tw[i] = {(double)cosl(two_pi * i / N), (double)-sinl(two_pi * i / N)};
 }

@@ -17,7 +17,7 @@
 // Every sum has a fixed order and there are no atomics: a signal's track, and a pair's values, are the same bits alone, in any
 // batch and through the multi path.  All bodies compile on the host too (SSR_HOST_EMU, tests/emu/pitch_emu.cpp).
 #pragma once
-#include "ssr_block.h"
+#include "ssr_pairs.h"
 
 #define SSR_PITCH_F0_RMSE 1
 #define SSR_PITCH_F0_CORR 2
@@ -45,11 +45,6 @@ SSR_HD int ssr_pitch_runs(int tau_hi) { return (tau_hi + SSR_PITCH_R - 1) / SSR_
 // frames of a 16 kHz signal of n samples: frame t is centred on sample t H
 SSR_HD int64_t ssr_pitch_frames(int64_t n) { return n > 0 ? n / SSR_PITCH_HOP + 1 : 0; }
 SSR_HD int64_t ssr_pitch_tiles(int64_t n) { return (ssr_pitch_frames(n) + SSR_PITCH_F - 1) / SSR_PITCH_F; }
-SSR_HD int ssr_pitch_popcount(int which) {
-  int c = 0;
-  for (int b = 0; b < 5; ++b) c += (which >> b) & 1;
-  return c;
-}
 
 #ifdef SSR_HOST_EMU
 // inside a phase: dst = the first lane of this wave where pred holds, -1 if none (host: lanes run in ascending order)
@@ -90,15 +85,6 @@ SSR_HD int64_t ssr_pitch_len(const SsrPitchParams& p, int i) { return i < p.n_a 
 SSR_HD const double* ssr_pitch_sig(const SsrPitchParams& p, int i) {
   return i < p.n_a ? p.sig_a + p.off_a[i] : p.sig_b + p.off_b[i - p.n_a];
 }
-// largest s in [0, n) with pre[s] <= g (pre ascending, pre[0] = 0): the signal that owns tile g
-SSR_HD int ssr_pitch_find(const int64_t* pre, int n, int64_t g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (pre[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // ---- geometry: one workgroup of SSR_PITCH_NT threads.  LDS: 2 * NT int64.
 template <typename BLK> SSR_BODY void ssr_pitch_geometry_body(const SsrPitchParams& p, BLK& blk, int64_t* sums) {
@@ -135,7 +121,7 @@ template <typename BLK>
 SSR_BODY void ssr_pitch_track_body(const SsrPitchParams& p, BLK& blk, int64_t g, double* xs, double* d, double* wsum,
                                    double* wpart, double* wmin, int* wtau, int* wcand, int* wfirst) {
   const int NT = SSR_PITCH_NT, H = SSR_PITCH_HOP, W = SSR_PITCH_WIN, F = SSR_PITCH_F, NR = SSR_PITCH_R, RUN = SSR_PITCH_RUN;
-  const int i = ssr_pitch_find(p.tile_pre, p.n_a + p.n_b, g);
+  const int i = ssr_prefix_find(p.tile_pre, p.n_a + p.n_b, g);
   const int64_t n = ssr_pitch_len(p, i), T = ssr_pitch_frames(n), t0 = (g - p.tile_pre[i]) * F;
   const int nf = (int)(T - t0 < F ? T - t0 : F), nb = p.nb, tau_lo = p.tau_lo, tau_hi = p.tau_hi;
   const double* x = ssr_pitch_sig(p, i);
@@ -361,7 +347,7 @@ SSR_BODY void ssr_pitch_pair_body(const SsrPitchParams& p, BLK& blk, int e, doub
       v[2] = nbd > 0.0 ? ng / nbd : nan;
       v[3] = T > 0 ? nv / Td : nan;
       v[4] = T > 0 ? (nv + ng) / Td : nan;
-      double* o = p.out + (int64_t)e * ssr_pitch_popcount(p.which);
+      double* o = p.out + (int64_t)e * ssr_which_count(p.which);
       int c = 0;
       for (int b = 0; b < 5; ++b)
         if (p.which & (1 << b)) o[c++] = v[b];

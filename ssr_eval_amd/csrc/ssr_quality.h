@@ -3,8 +3,8 @@
 // and the frequency-weighted segmental SNR (fwSNRseg), on float32 or float64 targets and estimates read in their own dtype.
 // Every sample gets EPS added, frames are those of §10 (L = 30 ms, hop L / 4, Loizou's Hann window), all arithmetic is float64.
 //
-//   geometry   one workgroup: runs of consecutive pairs that name one target; frame prefix sums over runs and over pairs; the
-//              window
+//   geometry   one workgroup (ssr_pairs.h): runs of consecutive pairs that name one target; frame prefix sums over runs and
+//              over pairs; the window
 //   lpc        one wave per (run, frame): the P + 1 lags of the target's frame by fixed-order wave reductions, Levinson-Durbin and
 //              the cepstrum on one lane; then the same for each estimate of the run, and its LLR and cepstral distance
 //   bands      one workgroup of N / 8 threads per (run, frame): the N-point transform of the real frame (ssr_fft.h in LDS), its
@@ -18,7 +18,7 @@
 // only atomics are the integer histogram counts of the select.  All bodies compile on the host too (SSR_HOST_EMU,
 // tests/emu/quality_emu.cpp).
 #pragma once
-#include "ssr_block.h"
+#include "ssr_pairs.h"
 #include "ssr_fft.h"
 #include <vector>
 
@@ -27,6 +27,7 @@
 #define SSR_QUAL_WSS 4
 #define SSR_QUAL_FWSEG 8
 #define SSR_QUAL_NT 256                    // threads of the geometry and finalize workgroups
+static_assert(SSR_QUAL_NT == SSR_PAIRS_NT, "the geometry workgroup is ssr_run_geometry_body's");
 #define SSR_QUAL_BANDS 25
 #define SSR_QUAL_PMAX 32                   // largest LPC order
 #define SSR_QUAL_FS_MIN 8000
@@ -55,8 +56,6 @@ SSR_HD int ssr_qual_log2_nfft(int fs) {
 SSR_HD int ssr_qual_default_order(int fs) { return fs < 10000 ? 10 : 16; }
 // frames averaged by the trimmed mean: MATLAB's round(0.95 M)
 SSR_HD int64_t ssr_qual_trim_count(int64_t M) { return (int64_t)floor(0.95 * (double)M + 0.5); }
-SSR_HD int ssr_qual_popcount(int which) { return (which & 1) + ((which >> 1) & 1) + ((which >> 2) & 1) + ((which >> 3) & 1); }
-SSR_HD int ssr_qual_col(int which, int bit) { return ssr_qual_popcount(which & (bit - 1)); }
 
 struct SsrQualParams {
   const void* tgt;              // targets (clean), float32 or float64
@@ -79,51 +78,10 @@ struct SsrQualParams {
   double* out;                  // [n_est][popcount(which)]
 };
 
-// largest s in [0, n) with off[s] <= g (off ascending, off[0] = 0)
-SSR_HD int ssr_qual_find(const int64_t* off, int n, int64_t g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// ---- geometry: one workgroup of SSR_QUAL_NT threads.  LDS: 3 * NT int64.
+// ---- geometry: ssr_run_geometry_body on the frames of each target
 template <typename BLK> SSR_BODY void ssr_qual_geometry_body(const SsrQualParams& p, BLK& blk, int64_t* sums) {
-  const int NT = SSR_QUAL_NT, c = (p.n_est + NT - 1) / NT;
-  SSR_REGS(int, regs, blk);
-  SSR_PHASE(blk, regs, {
-    int64_t runs = 0, rf = 0, pf = 0;
-    for (int e = tid * c; e < p.n_est && e < (tid + 1) * c; ++e) {
-      const int64_t M = ssr_qual_frames(p.tgt_len[p.tgt_index[e]], p.fs);
-      if (e == 0 || p.tgt_index[e] != p.tgt_index[e - 1]) { ++runs; rf += M; }
-      pf += M;
-    }
-    sums[tid] = runs; sums[NT + tid] = rf; sums[2 * NT + tid] = pf;
-    for (int i = tid; i < p.L; i += NT) p.win[i] = 0.5 * (1.0 - cos(2.0 * M_PI * (double)(i + 1) / (double)(p.L + 1)));
-  });
-  SSR_PHASE(blk, regs, {
-    if (tid < 3) {
-      int64_t a = 0;
-      for (int t = 0; t < NT; ++t) { const int64_t v = sums[tid * NT + t]; sums[tid * NT + t] = a; a += v; }
-    }
-  });
-  SSR_PHASE(blk, regs, {
-    int64_t r = sums[tid], rf = sums[NT + tid], pf = sums[2 * NT + tid];
-    for (int e = tid * c; e < p.n_est && e < (tid + 1) * c; ++e) {
-      const int64_t M = ssr_qual_frames(p.tgt_len[p.tgt_index[e]], p.fs);
-      if (e == 0 || p.tgt_index[e] != p.tgt_index[e - 1]) {
-        p.run_start[r] = e; p.run_frame[r] = rf;
-        ++r; rf += M;
-      }
-      p.pair_frame[e] = pf;
-      pf += M;
-    }
-    if (tid == NT - 1) {
-      p.run_start[p.n_runs] = p.n_est; p.run_frame[p.n_runs] = rf; p.pair_frame[p.n_est] = pf;
-    }
-  });
+  ssr_run_geometry_body(p.tgt_len, p.tgt_index, p.n_est, [&](int32_t n) { return ssr_qual_frames(n, p.fs); },
+                        p.run_start, p.run_frame, p.pair_frame, p.win, p.L, blk, sums);
 }
 
 // ---- LPC analysis (one lane; a, alpha, tmp: P + 1 doubles each)
@@ -213,7 +171,7 @@ SSR_BODY void ssr_qual_lags(const SsrQualParams& p, BLK& blk, REGS& regs, const 
 // ---- lpc: grid block g = (run, frame j), one wave of 64 lanes
 template <typename TT, typename TE, typename BLK>
 SSR_BODY void ssr_qual_lpc_body(const SsrQualParams& p, BLK& blk, int64_t g, SsrQualLpcLds& S) {
-  const int r = ssr_qual_find(p.run_frame, p.n_runs, g);
+  const int r = ssr_prefix_find(p.run_frame, p.n_runs, g);
   const int64_t j = g - p.run_frame[r];
   const int e0 = p.run_start[r], e1 = p.run_start[r + 1];
   const int P = p.P;
@@ -314,7 +272,7 @@ struct SsrQualBandRegs {
 template <typename T, int LOGN, typename BLK, typename REGS>
 SSR_BODY void ssr_qual_band_sums(const SsrQualParams& p, BLK& blk, REGS& regs, SsrQualBandLds<LOGN>& S, const T* s, bool pw, bool mag) {
   using PL = SsrFftPlan<LOGN>;
-  constexpr int NT = PL::NT, LAST = PL::NPASS - 1, NW = (NT + 63) / 64;
+  constexpr int NT = PL::NT, NW = (NT + 63) / 64;
   const double* w = p.win;
   const cx<double>* tw = p.tw;
   const int L = p.L;
@@ -327,14 +285,7 @@ SSR_BODY void ssr_qual_band_sums(const SsrQualParams& p, BLK& blk, REGS& regs, S
     ssr_fft_compute<double, LOGN, 0>(tid, R.v, tw);
     ssr_fft_store<double, LOGN, 0>(tid, S.re, S.im, R.v);
   });
-  ssr_fft_mid_passes<double, LOGN, 1, 8>(blk, regs, S.re, S.im, tw);
-  SSR_PHASE(blk, regs, {
-    SSR_UNROLL for (int r = 0; r < 8; ++r) {
-      const int k = ssr_fft_out_index<LOGN, LAST>(tid, r);
-      S.re[ssr_pad(k)] = R.v[r].x;
-      S.im[ssr_pad(k)] = R.v[r].y;
-    }
-  });
+  ssr_fft_finish_natural<LOGN>(blk, regs, S.re, S.im, tw);
   SSR_PHASE(blk, regs, {
     double ma = 0.0;
     SSR_UNROLL for (int q = 0; q < 4; ++q) {
@@ -368,7 +319,7 @@ SSR_BODY void ssr_qual_band_sums(const SsrQualParams& p, BLK& blk, REGS& regs, S
 // ---- bands: grid block g = (run, frame j), N / 8 threads
 template <typename TT, typename TE, int LOGN, typename BLK>
 SSR_BODY void ssr_qual_bands_body(const SsrQualParams& p, BLK& blk, int64_t g, SsrQualBandLds<LOGN>& S) {
-  const int r = ssr_qual_find(p.run_frame, p.n_runs, g);
+  const int r = ssr_prefix_find(p.run_frame, p.n_runs, g);
   const int64_t j = g - p.run_frame[r];
   const int e0 = p.run_start[r], e1 = p.run_start[r + 1];
   const bool wss = (p.which & SSR_QUAL_WSS) != 0, fws = (p.which & SSR_QUAL_FWSEG) != 0;
@@ -433,12 +384,12 @@ struct SsrQualFinLds {
 template <typename BLK> SSR_BODY void ssr_qual_finalize_body(const SsrQualParams& p, BLK& blk, int e, SsrQualFinLds& S) {
   const int NT = SSR_QUAL_NT;
   const int64_t M = ssr_qual_frames(p.tgt_len[p.tgt_index[e]], p.fs);
-  const int n_out = ssr_qual_popcount(p.which);
+  const int n_out = ssr_which_count(p.which);
   const int64_t c = (M + NT - 1) / NT;
   SSR_REGS(int, regs, blk);
   for (int m = 0; m < 4; ++m) {
     if (!(p.which & (1 << m))) continue;
-    double* o = p.out + (int64_t)e * n_out + ssr_qual_col(p.which, 1 << m);
+    double* o = p.out + (int64_t)e * n_out + ssr_which_col(p.which, 1 << m);
     if (M == 0) {
       SSR_PHASE(blk, regs, { if (tid == 0) *o = (double)NAN; });
       continue;
@@ -547,7 +498,5 @@ static inline void ssr_qual_tables_host(int fs, SsrQualTables& t) {
     t.lo[b] = lo; t.hi[b] = hi; t.off[b] = (int)t.packed.size();
     for (int j = lo; j < hi; ++j) t.packed.push_back(t.dense[(size_t)b * N2 + j]);
   }
-  const long double two_pi = 6.283185307179586476925286766559005768L;
-  t.tw.resize(t.N);
-  for (int i = 0; i < t.N; ++i) t.tw[i] = {(double)cosl(two_pi * i / t.N), (double)-sinl(two_pi * i / t.N)};
+  ssr_phase_twiddles_host(t.N, t.tw);
 }

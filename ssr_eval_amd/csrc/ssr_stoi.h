@@ -14,7 +14,7 @@
 // Every sum has a fixed order (no atomics): results are identical from run to run and independent of the batch they are in.
 // All bodies compile on the host too (SSR_HOST_EMU, tests/emu/stoi_emu.cpp).
 #pragma once
-#include "ssr_block.h"
+#include "ssr_pairs.h"
 
 #define SSR_STOI_FRAME 256           // N_FRAME
 #define SSR_STOI_HOP 128
@@ -77,16 +77,6 @@ static inline void ssr_stoi_band_edges_host(int* lo, int* hi) {
   }
 }
 
-// largest s in [0, n) with off[s] <= g (off ascending, off[0] = 0)
-SSR_HD int ssr_stoi_find(const int64_t* off, int n, int64_t g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 SSR_HD int ssr_stoi_target_of(const SsrStoiParams& p, int s) { return s < p.n_tgt ? s : p.tgt_index[s - p.n_tgt]; }
 
 // ---- geometry: one workgroup of SSR_STOI_NT threads.  LDS: 2 * NT int64.
@@ -126,7 +116,7 @@ template <typename BLK> SSR_BODY void ssr_stoi_geometry_body(const SsrStoiParams
 
 // ---- energy of target frame g (g < fr_off[n_tgt])
 SSR_HD void ssr_stoi_energy(const SsrStoiParams& p, int64_t g) {
-  const int t = ssr_stoi_find(p.fr_off, p.n_tgt, g);
+  const int t = ssr_prefix_find(p.fr_off, p.n_tgt, g);
   const int64_t i = g - p.fr_off[t];
   const double* x = p.tgt + p.tgt_off[t] + i * SSR_STOI_HOP;
   double s = 0.0;
@@ -190,7 +180,7 @@ SSR_HD unsigned ssr_stoi_bitrev9(unsigned n) {
 template <typename BLK> SSR_BODY void ssr_stoi_bands_body(const SsrStoiParams& p, BLK& blk, int64_t g, double* re, double* im,
                                                          double* twr, double* twi, double* pw) {
   const int S = p.n_tgt + p.n_est;
-  const int s = ssr_stoi_find(p.fr_off, S, g);
+  const int s = ssr_prefix_find(p.fr_off, S, g);
   const int t = (int)(g - p.fr_off[s]);
   const int tt = ssr_stoi_target_of(p, s);
   if (t >= p.n_kept[tt] - 1) return;                    // (uniform over the workgroup)
@@ -301,7 +291,7 @@ SSR_HD double ssr_estoi_segment(const double* X, const double* Y, double* rs, in
 // LDS: X, Y [SEG_ROWS][15], rs [60][SEG], red [2][SEG] doubles.
 template <typename BLK> SSR_BODY void ssr_stoi_segments_body(const SsrStoiParams& p, BLK& blk, int64_t g, double* X, double* Y,
                                                             double* rs, double* red) {
-  const int e = ssr_stoi_find(p.st_off, p.n_est, g);
+  const int e = ssr_prefix_find(p.st_off, p.n_est, g);
   const int k = (int)(g - p.st_off[e]);
   const int tt = p.tgt_index[e];
   const int T = p.n_kept[tt] - 1, J = T - (SSR_STOI_N - 1);

@@ -2,8 +2,8 @@
 // Speech Enhancement, §11.1, comp_snr.m), on the signals as they lie - float32 or float64 targets and estimates, read in their
 // own dtype and accumulated in float64.
 //
-//   geometry   one workgroup: runs of consecutive pairs that name the same target, tile prefix sums over runs and over pairs,
-//              the frame window
+//   geometry   one workgroup (ssr_pairs.h): runs of consecutive pairs that name the same target, tile prefix sums over runs and
+//              over pairs, the frame window
 //   pass 1     one workgroup per (run, tile): the target's tile sums once, then for each estimate of the run Σy, the centred
 //              co-moment and Σ(x - y)^2 about the tile means, and seg_j of the frames that start in the tile (a frame's L - R halo
 //              is read past the tile); one partial record per (pair, tile)
@@ -16,12 +16,13 @@
 // pair gives the same bits alone, in any batch and in any run.  All bodies compile on the host too (SSR_HOST_EMU,
 // tests/emu/wave_emu.cpp).
 #pragma once
-#include "ssr_block.h"
+#include "ssr_pairs.h"
 
 #define SSR_WAVE_SNR 1
 #define SSR_WAVE_SI_SDR 2
 #define SSR_WAVE_SEG_SNR 4
 #define SSR_WAVE_NT 256                    // threads of every workgroup
+static_assert(SSR_WAVE_NT == SSR_PAIRS_NT, "the geometry workgroup is ssr_run_geometry_body's");
 #define SSR_WAVE_TILE_MIN 4096             // a tile is the smallest whole number of hops with at least this many samples
 #define SSR_WAVE_EPS 2.220446049250313e-16 // np.finfo(np.float64).eps
 #define SSR_WAVE_SEG_LO -10.0
@@ -46,9 +47,6 @@ SSR_HD int64_t ssr_wave_frames(int64_t n, int fs) {
   const int L = ssr_wave_frame_len(fs), R = ssr_wave_hop(fs);
   return (R > 0 && n >= L) ? (n - L) / R : 0;
 }
-SSR_HD int ssr_wave_popcount(int which) { return (which & 1) + ((which >> 1) & 1) + ((which >> 2) & 1); }
-// output column of metric bit b (columns in bit order)
-SSR_HD int ssr_wave_col(int which, int bit) { return ssr_wave_popcount(which & (bit - 1)); }
 
 struct SsrWaveParams {
   const void* tgt;              // targets (clean), float32 or float64
@@ -70,56 +68,17 @@ struct SsrWaveParams {
   double* out;                  // [n_est][popcount(which)]
 };
 
-// largest s in [0, n) with off[s] <= g (off ascending, off[0] = 0)
-SSR_HD int ssr_wave_find(const int64_t* off, int n, int64_t g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// ---- geometry: one workgroup of SSR_WAVE_NT threads.  LDS: 3 * NT int64.
+// ---- geometry: ssr_run_geometry_body on the tiles of each target
 template <typename BLK> SSR_BODY void ssr_wave_geometry_body(const SsrWaveParams& p, BLK& blk, int64_t* sums) {
-  const int NT = SSR_WAVE_NT, c = (p.n_est + NT - 1) / NT;
-  SSR_REGS(int, regs, blk);
-  SSR_PHASE(blk, regs, {
-    int64_t runs = 0, rt = 0, pt = 0;
-    for (int e = tid * c; e < p.n_est && e < (tid + 1) * c; ++e) {
-      const int64_t nt = ssr_wave_tiles(p.tgt_len[p.tgt_index[e]], p.fs);
-      if (e == 0 || p.tgt_index[e] != p.tgt_index[e - 1]) { ++runs; rt += nt; }
-      pt += nt;
-    }
-    sums[tid] = runs; sums[NT + tid] = rt; sums[2 * NT + tid] = pt;
-    for (int i = tid; i < p.L; i += NT) p.win[i] = 0.5 * (1.0 - cos(2.0 * M_PI * (double)(i + 1) / (double)(p.L + 1)));
-  });
-  SSR_PHASE(blk, regs, {
-    if (tid < 3) {
-      int64_t a = 0;
-      for (int t = 0; t < NT; ++t) { const int64_t v = sums[tid * NT + t]; sums[tid * NT + t] = a; a += v; }
-    }
-  });
-  SSR_PHASE(blk, regs, {
-    int64_t r = sums[tid], rt = sums[NT + tid], pt = sums[2 * NT + tid];
-    for (int e = tid * c; e < p.n_est && e < (tid + 1) * c; ++e) {
-      const int64_t nt = ssr_wave_tiles(p.tgt_len[p.tgt_index[e]], p.fs);
-      if (e == 0 || p.tgt_index[e] != p.tgt_index[e - 1]) {
-        p.run_start[r] = e; p.run_tile[r] = rt;
-        ++r; rt += nt;
-      }
-      p.pair_tile[e] = pt;
-      pt += nt;
-    }
-    if (tid == NT - 1) { p.run_start[p.n_runs] = p.n_est; p.run_tile[p.n_runs] = rt; p.pair_tile[p.n_est] = pt; }
-  });
+  ssr_run_geometry_body(p.tgt_len, p.tgt_index, p.n_est, [&](int32_t n) { return ssr_wave_tiles(n, p.fs); },
+                        p.run_start, p.run_tile, p.pair_tile, p.win, p.L, blk, sums);
 }
 
 // (run, tile k) of pass-grid block g, its target and the tile's samples [a, a + m)
 struct SsrWaveTile { int r, e0, e1, t; int64_t k, a, m, n; };
 SSR_HD SsrWaveTile ssr_wave_tile_of(const SsrWaveParams& p, int64_t g) {
   SsrWaveTile w;
-  w.r = ssr_wave_find(p.run_tile, p.n_runs, g);
+  w.r = ssr_prefix_find(p.run_tile, p.n_runs, g);
   w.k = g - p.run_tile[w.r];
   w.e0 = p.run_start[w.r]; w.e1 = p.run_start[w.r + 1];
   w.t = p.tgt_index[w.e0];
@@ -229,7 +188,7 @@ SSR_BODY void ssr_wave_pass1_body(const SsrWaveParams& p, BLK& blk, int64_t g, d
 // ---- finalize 1: pair e.  Chan, Golub & LeVeque's pairwise update, tile after tile.
 SSR_HD void ssr_wave_finalize1(const SsrWaveParams& p, int e) {
   const int64_t n = p.tgt_len[p.tgt_index[e]];
-  const int n_out = ssr_wave_popcount(p.which);
+  const int n_out = ssr_which_count(p.which);
   double* out = p.out + (int64_t)e * n_out;
   double na = 0.0, mx = 0.0, my = 0.0, m2x = 0.0, cxy = 0.0, sxx = 0.0, sdd = 0.0, sseg = 0.0;
   const int64_t nt = p.pair_tile[e + 1] - p.pair_tile[e];
@@ -247,8 +206,8 @@ SSR_HD void ssr_wave_finalize1(const SsrWaveParams& p, int e) {
   }
   const int64_t M = ssr_wave_frames(n, p.fs);
   if (p.which & SSR_WAVE_SNR)
-    out[ssr_wave_col(p.which, SSR_WAVE_SNR)] = n > 0 ? 10.0 * log10((sxx + SSR_WAVE_EPS) / (sdd + SSR_WAVE_EPS)) : (double)NAN;
-  if (p.which & SSR_WAVE_SEG_SNR) out[ssr_wave_col(p.which, SSR_WAVE_SEG_SNR)] = M > 0 ? sseg / (double)M : (double)NAN;
+    out[ssr_which_col(p.which, SSR_WAVE_SNR)] = n > 0 ? 10.0 * log10((sxx + SSR_WAVE_EPS) / (sdd + SSR_WAVE_EPS)) : (double)NAN;
+  if (p.which & SSR_WAVE_SEG_SNR) out[ssr_which_col(p.which, SSR_WAVE_SEG_SNR)] = M > 0 ? sseg / (double)M : (double)NAN;
   if (p.which & SSR_WAVE_SI_SDR) {
     p.fin[3 * (int64_t)e + 0] = mx;
     p.fin[3 * (int64_t)e + 1] = my;
@@ -292,6 +251,6 @@ SSR_HD void ssr_wave_finalize2(const SsrWaveParams& p, int e) {
   const int64_t n = p.tgt_len[p.tgt_index[e]];
   double ss = 0.0, rr = 0.0;
   for (int64_t g = p.pair_tile[e]; g < p.pair_tile[e + 1]; ++g) { ss += p.part2[g * SSR_WAVE_P2]; rr += p.part2[g * SSR_WAVE_P2 + 1]; }
-  p.out[(int64_t)e * ssr_wave_popcount(p.which) + ssr_wave_col(p.which, SSR_WAVE_SI_SDR)] =
+  p.out[(int64_t)e * ssr_which_count(p.which) + ssr_which_col(p.which, SSR_WAVE_SI_SDR)] =
       n > 0 ? 10.0 * log10((ss + SSR_WAVE_EPS) / (rr + SSR_WAVE_EPS)) : (double)NAN;
 }

@@ -1,8 +1,6 @@
 // libssrhip.so translation unit: the multi-resolution STFT distance (spectral convergence and log-magnitude distance per
 // resolution and their means) on float32 / float64 signals (ssr_mrstft.h) and its entry points (ssr_mrstft_metrics,
 // ssr_mrstft_workspace_bytes).
-#include <map>
-#include <mutex>
 #include <utility>
 
 #include "ssr_host.h"
@@ -27,28 +25,10 @@ __global__ __launch_bounds__(SSR_PHASE_FIN_NT) void k_mrstft_finalize(SsrMrstftS
   ssr_mrstft_finalize_body(p, a, blk, (int)blockIdx.x);
 }
 
-// tables per transform size and per (size, window length): built once on the host, never written again (the workspace copies
-// read them)
-static std::mutex g_tables_mu;
-static const std::vector<cx<double>>& mrstft_twiddles(int n_fft) {
-  static std::map<int, std::vector<cx<double>>> cache;
-  std::lock_guard<std::mutex> lock(g_tables_mu);
-  auto it = cache.find(n_fft);
-  if (it == cache.end()) {
-    it = cache.emplace(n_fft, std::vector<cx<double>>{}).first;
-    ssr_phase_twiddles_host(n_fft, it->second);
-  }
-  return it->second;
-}
+// the window per (transform size, window length): built once on the host, never written again (the workspace copies read it)
 static const std::vector<double>& mrstft_window(int n_fft, int win) {
-  static std::map<std::pair<int, int>, std::vector<double>> cache;
-  std::lock_guard<std::mutex> lock(g_tables_mu);
-  auto it = cache.find({n_fft, win});
-  if (it == cache.end()) {
-    it = cache.emplace(std::make_pair(n_fft, win), std::vector<double>{}).first;
-    ssr_mrstft_window_host(n_fft, win, it->second);
-  }
-  return it->second;
+  static SsrHostTables<std::pair<int, int>, std::vector<double>> tables;
+  return tables.get({n_fft, win}, [&](std::vector<double>& w) { ssr_mrstft_window_host(n_fft, win, w); });
 }
 
 // workspace layout: a deterministic function of the target lengths, the pair -> target map and the resolutions' n_fft and hop
@@ -60,17 +40,17 @@ struct MrstftWs {
 static MrstftWs mrstft_ws(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int n_res, const int32_t* n_fft,
                           const int32_t* hop) {
   MrstftWs w{};
-  size_t o = 0;
-  w.off_len = o; o += ssr_align256((size_t)n_tgt * sizeof(int32_t));
-  w.off_idx = o; o += ssr_align256((size_t)n_est * sizeof(int32_t));
+  SsrWsLayout l;
+  w.off_len = l.take((size_t)n_tgt * sizeof(int32_t));
+  w.off_idx = l.take((size_t)n_est * sizeof(int32_t));
   for (int r = 0; r < n_res; ++r) {
     for (int e = 0; e < n_est; ++e) w.chunks[r] += ssr_phase_chunks(tgt_len[tgt_index[e]], n_fft[r], hop[r]);
-    w.off_co[r] = o; o += ssr_align256((size_t)(n_est + 1) * sizeof(int64_t));
-    w.off_tw[r] = o; o += ssr_align256((size_t)n_fft[r] * sizeof(cx<double>));
-    w.off_win[r] = o; o += ssr_align256((size_t)n_fft[r] * sizeof(double));
-    w.off_part[r] = o; o += ssr_align256((size_t)w.chunks[r] * 3 * sizeof(double));
+    w.off_co[r] = l.take((size_t)(n_est + 1) * sizeof(int64_t));
+    w.off_tw[r] = l.take((size_t)n_fft[r] * sizeof(cx<double>));
+    w.off_win[r] = l.take((size_t)n_fft[r] * sizeof(double));
+    w.off_part[r] = l.take((size_t)w.chunks[r] * 3 * sizeof(double));
   }
-  w.total = o;
+  w.total = l.o;
   return w;
 }
 
@@ -93,15 +73,6 @@ extern "C" size_t ssr_mrstft_workspace_bytes(const int32_t* tgt_len, int n_tgt, 
   return mrstft_ws(tgt_len, n_tgt, tgt_index, n_est, n_res, n_fft, hop).total;
 }
 
-template <typename TT, typename TE>
-static void launch_dist(const SsrMrstftSig& p, const SsrMrstftRes& q, double eps, int64_t grid, int logn, hipStream_t s) {
-  const dim3 g((unsigned)grid), b((unsigned)((1 << logn) / 8));
-  if (logn == 8) hipLaunchKernelGGL((k_mrstft_dist<TT, TE, 8>), g, b, 0, s, p, q, eps);
-  else if (logn == 9) hipLaunchKernelGGL((k_mrstft_dist<TT, TE, 9>), g, b, 0, s, p, q, eps);
-  else if (logn == 10) hipLaunchKernelGGL((k_mrstft_dist<TT, TE, 10>), g, b, 0, s, p, q, eps);
-  else hipLaunchKernelGGL((k_mrstft_dist<TT, TE, 11>), g, b, 0, s, p, q, eps);
-}
-
 extern "C" int ssr_mrstft_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt,
                                   const void* est, int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est, int n_res,
                                   const int32_t* n_fft, const int32_t* hop, const int32_t* win, const int32_t* bin_lo,
@@ -114,9 +85,7 @@ extern "C" int ssr_mrstft_metrics(const void* tgt, int tgt_f64, const int64_t* t
       return ssr_fail(SSR_ERR_INVALID_ARG, "bins must satisfy 0 <= bin_lo <= bin_hi <= n_fft / 2");
   if (!(eps > 0.0) || !(eps <= 1.7976931348623157e308)) return ssr_fail(SSR_ERR_INVALID_ARG, "eps must be finite and > 0");
   if (n_est == 0) return SSR_OK;
-  int64_t samples = 0;
-  for (int t = 0; t < n_tgt; ++t) samples += tgt_len[t];
-  if (!tgt_off || !est_off || !out || (samples > 0 && (!tgt || !est))) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  if (int rc = ssr_check_pair_buffers(tgt, tgt_off, est, est_off, out, tgt_len, n_tgt)) return rc;
   const MrstftWs w = mrstft_ws(tgt_len, n_tgt, tgt_index, n_est, n_res, n_fft, hop);
   // (one workgroup per chunk: every launch stays below 2^32 threads, which every HIP runtime takes)
   for (int r = 0; r < n_res; ++r)
@@ -128,13 +97,12 @@ extern "C" int ssr_mrstft_metrics(const void* tgt, int tgt_f64, const int64_t* t
   int32_t* idx_dev = (int32_t*)(ws + w.off_idx);
   if (int rc = ssr_upload_pair_index(tgt_len, n_tgt, tgt_index, n_est, len_dev, idx_dev, s)) return rc;
   SsrMrstftSig p{};
-  p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = len_dev; p.tgt_index = idx_dev;
-  p.n_tgt = n_tgt; p.n_est = n_est;
+  ssr_set_pair_sig(p, tgt, tgt_off, est, est_off, len_dev, idx_dev, n_tgt, n_est);
   SsrMrstftAll a{};
   a.n_res = n_res; a.out = out;
   for (int r = 0; r < n_res; ++r) {
     // (the tables are cached for the life of the process: the caller need not keep them)
-    const std::vector<cx<double>>& tw = mrstft_twiddles(n_fft[r]);
+    const std::vector<cx<double>>& tw = ssr_twiddles_cached(n_fft[r]);
     const std::vector<double>& wn = mrstft_window(n_fft[r], win[r]);
     HIP_TRY(hipMemcpyAsync(ws + w.off_tw[r], tw.data(), tw.size() * sizeof(cx<double>), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(ws + w.off_win[r], wn.data(), wn.size() * sizeof(double), hipMemcpyHostToDevice, s));
@@ -145,17 +113,18 @@ extern "C" int ssr_mrstft_metrics(const void* tgt, int tgt_f64, const int64_t* t
   }
   for (int r = 0; r < n_res; ++r) {
     const SsrMrstftRes& q = a.res[r];
-    hipLaunchKernelGGL(k_mrstft_geometry, dim3(1), dim3(SSR_PHASE_NT), 0, s, p, q);
-    HIP_TRY(hipGetLastError());
+    SSR_LAUNCH(k_mrstft_geometry, dim3(1), dim3(SSR_PHASE_NT), s, p, q);
     if (w.chunks[r] > 0) {
-      const int logn = ssr_phase_log2_nfft(q.N);
-      ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
-        launch_dist<decltype(tt), decltype(te)>(p, q, eps, w.chunks[r], logn, s);
+      const int rc = ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
+        return ssr_dispatch_logn<SSR_PHASE_LOGN_MIN, SSR_PHASE_LOGN_MAX>(ssr_phase_log2_nfft(q.N), [&](auto logn) -> int {
+          constexpr int LOGN = decltype(logn)::value;
+          SSR_LAUNCH((k_mrstft_dist<decltype(tt), decltype(te), LOGN>), dim3((unsigned)w.chunks[r]), dim3((1u << LOGN) / 8), s, p, q, eps);
+          return SSR_OK;
+        });
       });
-      HIP_TRY(hipGetLastError());
+      if (rc) return rc;
     }
   }
-  hipLaunchKernelGGL(k_mrstft_finalize, dim3((unsigned)ssr_ceil_div(n_est, SSR_PHASE_FIN_NT)), dim3(SSR_PHASE_FIN_NT), 0, s, p, a);
-  HIP_TRY(hipGetLastError());
+  SSR_LAUNCH(k_mrstft_finalize, dim3((unsigned)ssr_ceil_div(n_est, SSR_PHASE_FIN_NT)), dim3(SSR_PHASE_FIN_NT), s, p, a);
   return SSR_OK;
 }

@@ -1,8 +1,5 @@
 // libssrhip.so translation unit: the anti-wrapping phase distances IP, GD and IAF on float32 / float64 signals (ssr_phase.h) and
 // its entry points (ssr_phase_metrics, ssr_phase_metrics_workspace_bytes).
-#include <map>
-#include <mutex>
-
 #include "ssr_host.h"
 #include "ssr_phase.h"
 
@@ -23,31 +20,18 @@ __global__ __launch_bounds__(SSR_PHASE_FIN_NT) void k_phase_finalize(SsrPhasePar
   ssr_phase_finalize_body(p, blk, (int)blockIdx.x);
 }
 
-// twiddles per transform size: built once on the host, never written again (the workspace copies read them)
-static const std::vector<cx<double>>& phase_twiddles(int n_fft) {
-  static std::mutex mu;
-  static std::map<int, std::vector<cx<double>>> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(n_fft);
-  if (it == cache.end()) {
-    it = cache.emplace(n_fft, std::vector<cx<double>>{}).first;
-    ssr_phase_twiddles_host(n_fft, it->second);
-  }
-  return it->second;
-}
-
 // workspace layout: a deterministic function of the target lengths, the pair -> target map, n_fft and hop
 struct PhaseWs { size_t off_len, off_idx, off_co, off_tw, off_part, total; int64_t chunks; };
 static PhaseWs phase_ws(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int n_fft, int hop) {
   PhaseWs w{};
   for (int e = 0; e < n_est; ++e) w.chunks += ssr_phase_chunks(tgt_len[tgt_index[e]], n_fft, hop);
-  size_t o = 0;
-  w.off_len = o; o += ssr_align256((size_t)n_tgt * sizeof(int32_t));
-  w.off_idx = o; o += ssr_align256((size_t)n_est * sizeof(int32_t));
-  w.off_co = o; o += ssr_align256((size_t)(n_est + 1) * sizeof(int64_t));
-  w.off_tw = o; o += ssr_align256((size_t)n_fft * sizeof(cx<double>));
-  w.off_part = o; o += ssr_align256((size_t)w.chunks * 3 * sizeof(double));
-  w.total = o;
+  SsrWsLayout l;
+  w.off_len = l.take((size_t)n_tgt * sizeof(int32_t));
+  w.off_idx = l.take((size_t)n_est * sizeof(int32_t));
+  w.off_co = l.take((size_t)(n_est + 1) * sizeof(int64_t));
+  w.off_tw = l.take((size_t)n_fft * sizeof(cx<double>));
+  w.off_part = l.take((size_t)w.chunks * 3 * sizeof(double));
+  w.total = l.o;
   return w;
 }
 
@@ -66,14 +50,6 @@ extern "C" size_t ssr_phase_metrics_workspace_bytes(const int32_t* tgt_len, int 
   return phase_ws(tgt_len, n_tgt, tgt_index, n_est, n_fft, hop).total;
 }
 
-template <typename TT, typename TE> static void launch_dist(const SsrPhaseParams& p, int64_t grid, int logn, hipStream_t s) {
-  const dim3 g((unsigned)grid), b((unsigned)((1 << logn) / 8));
-  if (logn == 8) hipLaunchKernelGGL((k_phase_dist<TT, TE, 8>), g, b, 0, s, p);
-  else if (logn == 9) hipLaunchKernelGGL((k_phase_dist<TT, TE, 9>), g, b, 0, s, p);
-  else if (logn == 10) hipLaunchKernelGGL((k_phase_dist<TT, TE, 10>), g, b, 0, s, p);
-  else hipLaunchKernelGGL((k_phase_dist<TT, TE, 11>), g, b, 0, s, p);
-}
-
 extern "C" int ssr_phase_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt,
                                  const void* est, int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est, int n_fft,
                                  int hop, int bin_lo, int bin_hi, int which, double* out, void* workspace, size_t workspace_bytes,
@@ -81,14 +57,12 @@ extern "C" int ssr_phase_metrics(const void* tgt, int tgt_f64, const int64_t* tg
   if (int rc = check_phase_args(tgt_len, n_tgt, tgt_index, n_est, n_fft, hop, which)) return rc;
   if (bin_lo < 0 || bin_lo > bin_hi || bin_hi > n_fft / 2) return ssr_fail(SSR_ERR_INVALID_ARG, "bins must satisfy 0 <= bin_lo <= bin_hi <= n_fft / 2");
   if (n_est == 0) return SSR_OK;
-  int64_t samples = 0;
-  for (int t = 0; t < n_tgt; ++t) samples += tgt_len[t];
-  if (!tgt_off || !est_off || !out || (samples > 0 && (!tgt || !est))) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  if (int rc = ssr_check_pair_buffers(tgt, tgt_off, est, est_off, out, tgt_len, n_tgt)) return rc;
   const PhaseWs w = phase_ws(tgt_len, n_tgt, tgt_index, n_est, n_fft, hop);
   // (one workgroup per chunk: the launch stays below 2^32 threads, which every HIP runtime takes)
   if (w.chunks * (n_fft / 8) > 0xffffffffLL) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
   if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
-  const std::vector<cx<double>>& tw = phase_twiddles(n_fft);
+  const std::vector<cx<double>>& tw = ssr_twiddles_cached(n_fft);
   char* ws = (char*)workspace;
   hipStream_t s = (hipStream_t)stream;
   int32_t* len_dev = (int32_t*)(ws + w.off_len);
@@ -97,20 +71,21 @@ extern "C" int ssr_phase_metrics(const void* tgt, int tgt_f64, const int64_t* tg
   // (the table is cached for the life of the process: the caller need not keep it)
   HIP_TRY(hipMemcpyAsync(ws + w.off_tw, tw.data(), tw.size() * sizeof(cx<double>), hipMemcpyHostToDevice, s));
   SsrPhaseParams p{};
-  p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = len_dev; p.tgt_index = idx_dev;
-  p.n_tgt = n_tgt; p.n_est = n_est; p.which = which; p.N = n_fft; p.H = hop; p.k_lo = bin_lo; p.k_hi = bin_hi;
+  ssr_set_pair_sig(p, tgt, tgt_off, est, est_off, len_dev, idx_dev, n_tgt, n_est);
+  p.which = which; p.N = n_fft; p.H = hop; p.k_lo = bin_lo; p.k_hi = bin_hi;
   p.tw = (const cx<double>*)(ws + w.off_tw); p.chunk_off = (int64_t*)(ws + w.off_co); p.part = (double*)(ws + w.off_part);
   p.out = out;
-  hipLaunchKernelGGL(k_phase_geometry, dim3(1), dim3(SSR_PHASE_NT), 0, s, p);
-  HIP_TRY(hipGetLastError());
+  SSR_LAUNCH(k_phase_geometry, dim3(1), dim3(SSR_PHASE_NT), s, p);
   if (w.chunks > 0) {
-    const int logn = ssr_phase_log2_nfft(n_fft);
-    ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
-      launch_dist<decltype(tt), decltype(te)>(p, w.chunks, logn, s);
+    const int rc = ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
+      return ssr_dispatch_logn<SSR_PHASE_LOGN_MIN, SSR_PHASE_LOGN_MAX>(ssr_phase_log2_nfft(n_fft), [&](auto logn) -> int {
+        constexpr int LOGN = decltype(logn)::value;
+        SSR_LAUNCH((k_phase_dist<decltype(tt), decltype(te), LOGN>), dim3((unsigned)w.chunks), dim3((1u << LOGN) / 8), s, p);
+        return SSR_OK;
+      });
     });
-    HIP_TRY(hipGetLastError());
+    if (rc) return rc;
   }
-  hipLaunchKernelGGL(k_phase_finalize, dim3((unsigned)ssr_ceil_div(n_est, SSR_PHASE_FIN_NT)), dim3(SSR_PHASE_FIN_NT), 0, s, p);
-  HIP_TRY(hipGetLastError());
+  SSR_LAUNCH(k_phase_finalize, dim3((unsigned)ssr_ceil_div(n_est, SSR_PHASE_FIN_NT)), dim3(SSR_PHASE_FIN_NT), s, p);
   return SSR_OK;
 }

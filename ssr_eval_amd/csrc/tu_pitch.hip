@@ -62,16 +62,16 @@ static PitchWs pitch_ws(const int32_t* len, int n_a, const int32_t* idx, int n_b
     w.frames += ssr_pitch_frames(m);
   }
   const size_t nf = tracks ? (size_t)w.frames : 0;
-  size_t o = 0;
-  w.off_len = o; o += ssr_align256((size_t)n_a * sizeof(int32_t));
-  w.off_idx = o; o += ssr_align256((size_t)n_b * sizeof(int32_t));
-  w.off_tp = o; o += ssr_align256((size_t)(n_a + n_b + 1) * sizeof(int64_t));
-  w.off_fp = o; o += ssr_align256((size_t)(n_a + n_b + 1) * sizeof(int64_t));
-  w.off_f0 = o; o += ssr_align256(nf * sizeof(double));
-  w.off_ap = o; o += ssr_align256(nf * sizeof(double));
-  w.off_en = o; o += ssr_align256(nf * sizeof(double));
-  w.off_vo = o; o += ssr_align256(nf);
-  w.total = o;
+  SsrWsLayout l;
+  w.off_len = l.take((size_t)n_a * sizeof(int32_t));
+  w.off_idx = l.take((size_t)n_b * sizeof(int32_t));
+  w.off_tp = l.take((size_t)(n_a + n_b + 1) * sizeof(int64_t));
+  w.off_fp = l.take((size_t)(n_a + n_b + 1) * sizeof(int64_t));
+  w.off_f0 = l.take(nf * sizeof(double));
+  w.off_ap = l.take(nf * sizeof(double));
+  w.off_en = l.take(nf * sizeof(double));
+  w.off_vo = l.take(nf);
+  w.total = l.o;
   return w;
 }
 
@@ -81,14 +81,9 @@ static void pitch_options(SsrPitchParams& p, double fmin, double fmax) {
 
 // geometry, tracker and voicing for the n_a + n_b signals of p
 static int launch_tracks(SsrPitchParams& p, int64_t tiles, hipStream_t s) {
-  hipLaunchKernelGGL(k_pitch_geometry, dim3(1), dim3(SSR_PITCH_NT), 0, s, p);
-  HIP_TRY(hipGetLastError());
-  if (tiles > 0) {
-    hipLaunchKernelGGL(k_pitch_track, dim3((unsigned)tiles), dim3(SSR_PITCH_NT), 0, s, p);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_pitch_voicing, dim3((unsigned)(p.n_a + p.n_b)), dim3(SSR_PITCH_NT), 0, s, p);
-  HIP_TRY(hipGetLastError());
+  SSR_LAUNCH(k_pitch_geometry, dim3(1), dim3(SSR_PITCH_NT), s, p);
+  if (tiles > 0) SSR_LAUNCH(k_pitch_track, dim3((unsigned)tiles), dim3(SSR_PITCH_NT), s, p);
+  SSR_LAUNCH(k_pitch_voicing, dim3((unsigned)(p.n_a + p.n_b)), dim3(SSR_PITCH_NT), s, p);
   return SSR_OK;
 }
 
@@ -150,7 +145,6 @@ extern "C" int ssr_f0_metrics(const double* tgt, const int64_t* tgt_off, const i
   p.voiced = (uint8_t*)(ws + w.off_vo);
   p.which = which; p.out = out;
   if (int rc = launch_tracks(p, w.tiles, s)) return rc;
-  hipLaunchKernelGGL(k_pitch_pairs, dim3((unsigned)n_est), dim3(SSR_PITCH_NT), 0, s, p);
-  HIP_TRY(hipGetLastError());
+  SSR_LAUNCH(k_pitch_pairs, dim3((unsigned)n_est), dim3(SSR_PITCH_NT), s, p);
   return SSR_OK;
 }

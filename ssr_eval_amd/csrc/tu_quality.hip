@@ -1,8 +1,5 @@
 // libssrhip.so translation unit: LLR, LPC cepstral distance, WSS and fwSNRseg on float32 / float64 signals (ssr_quality.h) and
 // its entry points (ssr_quality_metrics, ssr_quality_metrics_workspace_bytes, ssr_quality_bands).
-#include <map>
-#include <mutex>
-
 #include "ssr_host.h"
 #include "ssr_quality.h"
 
@@ -32,15 +29,8 @@ __global__ __launch_bounds__(SSR_QUAL_NT) void k_qual_finalize(SsrQualParams p) 
 
 // band filters and twiddles per sample rate: built once on the host, never written again (the workspace copies read them)
 static const SsrQualTables& qual_tables(int fs) {
-  static std::mutex mu;
-  static std::map<int, SsrQualTables> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(fs);
-  if (it == cache.end()) {
-    it = cache.emplace(fs, SsrQualTables{}).first;
-    ssr_qual_tables_host(fs, it->second);
-  }
-  return it->second;
+  static SsrHostTables<int, SsrQualTables> tables;
+  return tables.get(fs, [&](SsrQualTables& t) { ssr_qual_tables_host(fs, t); });
 }
 
 // workspace layout: a deterministic function of the target lengths, the pair -> target map, fs and which
@@ -55,17 +45,17 @@ static QualWs qual_ws(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_inde
   }
   const bool bands = (which & (SSR_QUAL_WSS | SSR_QUAL_FWSEG)) != 0;
   const SsrQualTables& t = qual_tables(fs);
-  size_t o = 0;
-  w.off_len = o; o += ssr_align256((size_t)n_tgt * sizeof(int32_t));
-  w.off_idx = o; o += ssr_align256((size_t)n_est * sizeof(int32_t));
-  w.off_rs = o; o += ssr_align256((size_t)(w.n_runs + 1) * sizeof(int32_t));
-  w.off_rf = o; o += ssr_align256((size_t)(w.n_runs + 1) * sizeof(int64_t));
-  w.off_pf = o; o += ssr_align256((size_t)(n_est + 1) * sizeof(int64_t));
-  w.off_win = o; o += ssr_align256((size_t)ssr_qual_frame_len(fs) * sizeof(double));
-  w.off_tw = o; o += bands ? ssr_align256((size_t)t.N * sizeof(cx<double>)) : 0;
-  w.off_fw = o; o += bands ? ssr_align256((t.packed.size() + 1) * sizeof(double)) : 0;
-  w.off_val = o; o += ssr_align256((size_t)w.pair_frames * 4 * sizeof(double));
-  w.total = o;
+  SsrWsLayout l;
+  w.off_len = l.take((size_t)n_tgt * sizeof(int32_t));
+  w.off_idx = l.take((size_t)n_est * sizeof(int32_t));
+  w.off_rs = l.take((size_t)(w.n_runs + 1) * sizeof(int32_t));
+  w.off_rf = l.take((size_t)(w.n_runs + 1) * sizeof(int64_t));
+  w.off_pf = l.take((size_t)(n_est + 1) * sizeof(int64_t));
+  w.off_win = l.take((size_t)ssr_qual_frame_len(fs) * sizeof(double));
+  w.off_tw = l.take(bands ? (size_t)t.N * sizeof(cx<double>) : 0);
+  w.off_fw = l.take(bands ? (t.packed.size() + 1) * sizeof(double) : 0);
+  w.off_val = l.take((size_t)w.pair_frames * 4 * sizeof(double));
+  w.total = l.o;
   return w;
 }
 
@@ -99,22 +89,12 @@ extern "C" int ssr_quality_bands(int fs, int32_t* n_fft, double* cent, double* b
   return SSR_OK;
 }
 
-template <typename TT, typename TE> static void launch_bands(const SsrQualParams& p, int64_t grid, int logn, hipStream_t s) {
-  const dim3 g((unsigned)grid), b((unsigned)((1 << logn) / 8));
-  if (logn == 9) hipLaunchKernelGGL((k_qual_bands<TT, TE, 9>), g, b, 0, s, p);
-  else if (logn == 10) hipLaunchKernelGGL((k_qual_bands<TT, TE, 10>), g, b, 0, s, p);
-  else if (logn == 11) hipLaunchKernelGGL((k_qual_bands<TT, TE, 11>), g, b, 0, s, p);
-  else hipLaunchKernelGGL((k_qual_bands<TT, TE, 12>), g, b, 0, s, p);
-}
-
 extern "C" int ssr_quality_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const int32_t* tgt_len, int n_tgt,
                                    const void* est, int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est, int fs,
                                    int lpc_order, int which, double* out, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_qual_args(tgt_len, n_tgt, tgt_index, n_est, fs, lpc_order, which)) return rc;
   if (n_est == 0) return SSR_OK;
-  int64_t samples = 0;
-  for (int t = 0; t < n_tgt; ++t) samples += tgt_len[t];
-  if (!tgt_off || !est_off || !out || (samples > 0 && (!tgt || !est))) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  if (int rc = ssr_check_pair_buffers(tgt, tgt_off, est, est_off, out, tgt_len, n_tgt)) return rc;
   const QualWs w = qual_ws(tgt_len, n_tgt, tgt_index, n_est, fs, which);
   if (w.run_frames > 0x7fffffff) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
   if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
@@ -130,8 +110,8 @@ extern "C" int ssr_quality_metrics(const void* tgt, int tgt_f64, const int64_t* 
     HIP_TRY(hipMemcpyAsync(ws + w.off_fw, t.packed.data(), t.packed.size() * sizeof(double), hipMemcpyHostToDevice, s));
   }
   SsrQualParams p{};
-  p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = len_dev; p.tgt_index = idx_dev;
-  p.n_tgt = n_tgt; p.n_est = n_est; p.n_runs = w.n_runs; p.which = which; p.fs = fs;
+  ssr_set_pair_sig(p, tgt, tgt_off, est, est_off, len_dev, idx_dev, n_tgt, n_est);
+  p.n_runs = w.n_runs; p.which = which; p.fs = fs;
   p.L = ssr_qual_frame_len(fs); p.R = ssr_qual_hop(fs); p.P = lpc_order ? lpc_order : ssr_qual_default_order(fs); p.N = t.N;
   p.run_start = (int32_t*)(ws + w.off_rs); p.run_frame = (int64_t*)(ws + w.off_rf);
   p.pair_frame = (int64_t*)(ws + w.off_pf); p.win = (double*)(ws + w.off_win);
@@ -139,22 +119,21 @@ extern "C" int ssr_quality_metrics(const void* tgt, int tgt_f64, const int64_t* 
   p.fw = bands ? (const double*)(ws + w.off_fw) : nullptr;
   for (int b = 0; b < SSR_QUAL_BANDS; ++b) { p.band_lo[b] = t.lo[b]; p.band_hi[b] = t.hi[b]; p.band_off[b] = t.off[b]; }
   p.val = (double*)(ws + w.off_val); p.n_val = w.pair_frames; p.out = out;
-  hipLaunchKernelGGL(k_qual_geometry, dim3(1), dim3(SSR_QUAL_NT), 0, s, p);
-  HIP_TRY(hipGetLastError());
-  if (lpc && w.run_frames > 0) {
-    ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
-      hipLaunchKernelGGL((k_qual_lpc<decltype(tt), decltype(te)>), dim3((unsigned)w.run_frames), dim3(64), 0, s, p);
-    });
-    HIP_TRY(hipGetLastError());
-  }
-  if (bands && w.run_frames > 0) {
-    const int logn = ssr_qual_log2_nfft(fs);
-    ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
-      launch_bands<decltype(tt), decltype(te)>(p, w.run_frames, logn, s);
-    });
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_qual_finalize, dim3((unsigned)n_est), dim3(SSR_QUAL_NT), 0, s, p);
-  HIP_TRY(hipGetLastError());
+  SSR_LAUNCH(k_qual_geometry, dim3(1), dim3(SSR_QUAL_NT), s, p);
+  const dim3 frames((unsigned)w.run_frames);
+  const int rc = ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) -> int {
+    using TT = decltype(tt);
+    using TE = decltype(te);
+    if (lpc && w.run_frames > 0) SSR_LAUNCH((k_qual_lpc<TT, TE>), frames, dim3(64), s, p);
+    if (bands && w.run_frames > 0)
+      return ssr_dispatch_logn<9, 12>(ssr_qual_log2_nfft(fs), [&](auto logn) -> int {
+        constexpr int LOGN = decltype(logn)::value;
+        SSR_LAUNCH((k_qual_bands<TT, TE, LOGN>), frames, dim3((1u << LOGN) / 8), s, p);
+        return SSR_OK;
+      });
+    return SSR_OK;
+  });
+  if (rc) return rc;
+  SSR_LAUNCH(k_qual_finalize, dim3((unsigned)n_est), dim3(SSR_QUAL_NT), s, p);
   return SSR_OK;
 }

@@ -60,18 +60,18 @@ static StoiWs stoi_ws(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_inde
     w.tiles += ssr_stoi_seg_tiles(f);
   }
   const int S = n_tgt + n_est;
-  size_t o = 0;
-  w.off_len = o; o += ssr_align256((size_t)S * sizeof(int32_t));
-  w.off_idx = o; o += ssr_align256((size_t)n_est * sizeof(int32_t));
-  w.off_fr = o; o += ssr_align256((size_t)(S + 1) * sizeof(int64_t));
-  w.off_st = o; o += ssr_align256((size_t)(n_est + 1) * sizeof(int64_t));
-  w.off_win = o; o += ssr_align256(SSR_STOI_FRAME * sizeof(double));
-  w.off_energy = o; o += ssr_align256((size_t)w.tgt_frames * sizeof(double));
-  w.off_kept = o; o += ssr_align256((size_t)w.tgt_frames * sizeof(int32_t));
-  w.off_nkept = o; o += ssr_align256((size_t)n_tgt * sizeof(int32_t));
-  w.off_tob = o; o += ssr_align256((size_t)w.all_frames * SSR_STOI_BANDS * sizeof(double));
-  w.off_part = o; o += ssr_align256((size_t)w.tiles * 2 * sizeof(double));
-  w.total = o;
+  SsrWsLayout l;
+  w.off_len = l.take((size_t)S * sizeof(int32_t));
+  w.off_idx = l.take((size_t)n_est * sizeof(int32_t));
+  w.off_fr = l.take((size_t)(S + 1) * sizeof(int64_t));
+  w.off_st = l.take((size_t)(n_est + 1) * sizeof(int64_t));
+  w.off_win = l.take(SSR_STOI_FRAME * sizeof(double));
+  w.off_energy = l.take((size_t)w.tgt_frames * sizeof(double));
+  w.off_kept = l.take((size_t)w.tgt_frames * sizeof(int32_t));
+  w.off_nkept = l.take((size_t)n_tgt * sizeof(int32_t));
+  w.off_tob = l.take((size_t)w.all_frames * SSR_STOI_BANDS * sizeof(double));
+  w.off_part = l.take((size_t)w.tiles * 2 * sizeof(double));
+  w.total = l.o;
   return w;
 }
 
@@ -112,25 +112,11 @@ extern "C" int ssr_stoi(const double* tgt, const int64_t* tgt_off, const int32_t
   p.energy = (double*)(ws + w.off_energy); p.kept = (int32_t*)(ws + w.off_kept); p.n_kept = (int32_t*)(ws + w.off_nkept);
   p.tob = (double*)(ws + w.off_tob); p.part = (double*)(ws + w.off_part); p.out = out;
   ssr_stoi_band_edges_host(p.band_lo, p.band_hi);
-  hipLaunchKernelGGL(k_stoi_geometry, dim3(1), dim3(SSR_STOI_NT), 0, s, p);
-  HIP_TRY(hipGetLastError());
-  if (w.tgt_frames > 0) {
-    hipLaunchKernelGGL(k_stoi_energy, dim3((unsigned)ssr_ceil_div(w.tgt_frames, 256)), dim3(256), 0, s, p, w.tgt_frames);
-    HIP_TRY(hipGetLastError());
-  }
-  if (n_tgt > 0) {
-    hipLaunchKernelGGL(k_stoi_vad, dim3((unsigned)n_tgt), dim3(SSR_STOI_NT), 0, s, p);
-    HIP_TRY(hipGetLastError());
-  }
-  if (w.all_frames > 0) {
-    hipLaunchKernelGGL(k_stoi_bands, dim3((unsigned)w.all_frames), dim3(SSR_STOI_NT), 0, s, p);
-    HIP_TRY(hipGetLastError());
-  }
-  if (w.tiles > 0) {
-    hipLaunchKernelGGL(k_stoi_segments, dim3((unsigned)w.tiles), dim3(SSR_STOI_SEG), 0, s, p);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_stoi_finalize, dim3((unsigned)ssr_ceil_div(n_est, 256)), dim3(256), 0, s, p);
-  HIP_TRY(hipGetLastError());
+  SSR_LAUNCH(k_stoi_geometry, dim3(1), dim3(SSR_STOI_NT), s, p);
+  if (w.tgt_frames > 0) SSR_LAUNCH(k_stoi_energy, dim3((unsigned)ssr_ceil_div(w.tgt_frames, 256)), dim3(256), s, p, w.tgt_frames);
+  if (n_tgt > 0) SSR_LAUNCH(k_stoi_vad, dim3((unsigned)n_tgt), dim3(SSR_STOI_NT), s, p);
+  if (w.all_frames > 0) SSR_LAUNCH(k_stoi_bands, dim3((unsigned)w.all_frames), dim3(SSR_STOI_NT), s, p);
+  if (w.tiles > 0) SSR_LAUNCH(k_stoi_segments, dim3((unsigned)w.tiles), dim3(SSR_STOI_SEG), s, p);
+  SSR_LAUNCH(k_stoi_finalize, dim3((unsigned)ssr_ceil_div(n_est, 256)), dim3(256), s, p);
   return SSR_OK;
 }

@@ -41,17 +41,18 @@ static WaveWs wave_ws(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_inde
     if (e == 0 || tgt_index[e] != tgt_index[e - 1]) { ++w.n_runs; w.run_tiles += nt; }
     w.pair_tiles += nt;
   }
-  size_t o = 0;
-  w.off_len = o; o += ssr_align256((size_t)n_tgt * sizeof(int32_t));
-  w.off_idx = o; o += ssr_align256((size_t)n_est * sizeof(int32_t));
-  w.off_rs = o; o += ssr_align256((size_t)(w.n_runs + 1) * sizeof(int32_t));
-  w.off_rt = o; o += ssr_align256((size_t)(w.n_runs + 1) * sizeof(int64_t));
-  w.off_pt = o; o += ssr_align256((size_t)(n_est + 1) * sizeof(int64_t));
-  w.off_win = o; o += ssr_align256((size_t)ssr_wave_frame_len(fs) * sizeof(double));
-  w.off_p1 = o; o += ssr_align256((size_t)w.pair_tiles * SSR_WAVE_P1 * sizeof(double));
-  w.off_p2 = o; o += (which & SSR_WAVE_SI_SDR) ? ssr_align256((size_t)w.pair_tiles * SSR_WAVE_P2 * sizeof(double)) : 0;
-  w.off_fin = o; o += (which & SSR_WAVE_SI_SDR) ? ssr_align256((size_t)n_est * 3 * sizeof(double)) : 0;
-  w.total = o;
+  const bool si = (which & SSR_WAVE_SI_SDR) != 0;
+  SsrWsLayout l;
+  w.off_len = l.take((size_t)n_tgt * sizeof(int32_t));
+  w.off_idx = l.take((size_t)n_est * sizeof(int32_t));
+  w.off_rs = l.take((size_t)(w.n_runs + 1) * sizeof(int32_t));
+  w.off_rt = l.take((size_t)(w.n_runs + 1) * sizeof(int64_t));
+  w.off_pt = l.take((size_t)(n_est + 1) * sizeof(int64_t));
+  w.off_win = l.take((size_t)ssr_wave_frame_len(fs) * sizeof(double));
+  w.off_p1 = l.take((size_t)w.pair_tiles * SSR_WAVE_P1 * sizeof(double));
+  w.off_p2 = l.take(si ? (size_t)w.pair_tiles * SSR_WAVE_P2 * sizeof(double) : 0);
+  w.off_fin = l.take(si ? (size_t)n_est * 3 * sizeof(double) : 0);
+  w.total = l.o;
   return w;
 }
 
@@ -73,9 +74,7 @@ extern "C" int ssr_wave_metrics(const void* tgt, int tgt_f64, const int64_t* tgt
                                 int which, double* out, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_wave_args(tgt_len, n_tgt, tgt_index, n_est, fs, which)) return rc;
   if (n_est == 0) return SSR_OK;
-  int64_t samples = 0;
-  for (int t = 0; t < n_tgt; ++t) samples += tgt_len[t];
-  if (!tgt_off || !est_off || !out || (samples > 0 && (!tgt || !est))) return ssr_fail(SSR_ERR_INVALID_ARG, "null argument");
+  if (int rc = ssr_check_pair_buffers(tgt, tgt_off, est, est_off, out, tgt_len, n_tgt)) return rc;
   const WaveWs w = wave_ws(tgt_len, n_tgt, tgt_index, n_est, fs, which);
   if (w.run_tiles > 0x7fffffff) return ssr_fail(SSR_ERR_UNSUPPORTED, "batch too large for one launch");
   if (!workspace || workspace_bytes < w.total) return ssr_fail(SSR_ERR_WORKSPACE, "workspace too small");
@@ -85,34 +84,25 @@ extern "C" int ssr_wave_metrics(const void* tgt, int tgt_f64, const int64_t* tgt
   int32_t* idx_dev = (int32_t*)(ws + w.off_idx);
   if (int rc = ssr_upload_pair_index(tgt_len, n_tgt, tgt_index, n_est, len_dev, idx_dev, s)) return rc;
   SsrWaveParams p{};
-  p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = len_dev; p.tgt_index = idx_dev;
-  p.n_tgt = n_tgt; p.n_est = n_est; p.n_runs = w.n_runs; p.which = which; p.fs = fs;
+  ssr_set_pair_sig(p, tgt, tgt_off, est, est_off, len_dev, idx_dev, n_tgt, n_est);
+  p.n_runs = w.n_runs; p.which = which; p.fs = fs;
   p.L = ssr_wave_frame_len(fs); p.R = ssr_wave_hop(fs); p.fpt = ssr_wave_frames_per_tile(fs); p.tile = ssr_wave_tile_len(fs);
   p.run_start = (int32_t*)(ws + w.off_rs); p.run_tile = (int64_t*)(ws + w.off_rt); p.pair_tile = (int64_t*)(ws + w.off_pt);
   p.win = (double*)(ws + w.off_win); p.part1 = (double*)(ws + w.off_p1);
   p.part2 = (which & SSR_WAVE_SI_SDR) ? (double*)(ws + w.off_p2) : nullptr;
   p.fin = (which & SSR_WAVE_SI_SDR) ? (double*)(ws + w.off_fin) : nullptr;
   p.out = out;
-  hipLaunchKernelGGL(k_wave_geometry, dim3(1), dim3(SSR_WAVE_NT), 0, s, p);
-  HIP_TRY(hipGetLastError());
-  const dim3 tiles((unsigned)w.run_tiles), nt(SSR_WAVE_NT);
-  if (w.run_tiles > 0) {
-    ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
-      hipLaunchKernelGGL((k_wave_pass1<decltype(tt), decltype(te)>), tiles, nt, 0, s, p);
-    });
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_wave_finalize1, dim3((unsigned)ssr_ceil_div(n_est, 256)), dim3(256), 0, s, p);
-  HIP_TRY(hipGetLastError());
-  if (which & SSR_WAVE_SI_SDR) {
-    if (w.run_tiles > 0) {
-      ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) {
-        hipLaunchKernelGGL((k_wave_pass2<decltype(tt), decltype(te)>), tiles, nt, 0, s, p);
-      });
-      HIP_TRY(hipGetLastError());
+  SSR_LAUNCH(k_wave_geometry, dim3(1), dim3(SSR_WAVE_NT), s, p);
+  const dim3 tiles((unsigned)w.run_tiles), nt(SSR_WAVE_NT), pairs((unsigned)ssr_ceil_div(n_est, 256));
+  return ssr_dispatch_pair_dtypes(tgt_f64, est_f64, [&](auto tt, auto te) -> int {
+    using TT = decltype(tt);
+    using TE = decltype(te);
+    if (w.run_tiles > 0) SSR_LAUNCH((k_wave_pass1<TT, TE>), tiles, nt, s, p);
+    SSR_LAUNCH(k_wave_finalize1, pairs, dim3(256), s, p);
+    if (which & SSR_WAVE_SI_SDR) {
+      if (w.run_tiles > 0) SSR_LAUNCH((k_wave_pass2<TT, TE>), tiles, nt, s, p);
+      SSR_LAUNCH(k_wave_finalize2, pairs, dim3(256), s, p);
     }
-    hipLaunchKernelGGL(k_wave_finalize2, dim3((unsigned)ssr_ceil_div(n_est, 256)), dim3(256), 0, s, p);
-    HIP_TRY(hipGetLastError());
-  }
-  return SSR_OK;
+    return SSR_OK;
+  });
 }

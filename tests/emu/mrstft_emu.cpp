@@ -15,11 +15,8 @@ template <typename TT, typename TE, int LOGN> static void dist(const SsrMrstftSi
 }
 
 template <typename TT, typename TE> static void passes(const SsrMrstftSig& p, const SsrMrstftRes& q, double eps, int64_t grid) {
-  const int logn = ssr_phase_log2_nfft(q.N);
-  if (logn == 8) dist<TT, TE, 8>(p, q, eps, grid);
-  else if (logn == 9) dist<TT, TE, 9>(p, q, eps, grid);
-  else if (logn == 10) dist<TT, TE, 10>(p, q, eps, grid);
-  else dist<TT, TE, 11>(p, q, eps, grid);
+  ssr_dispatch_logn<SSR_PHASE_LOGN_MIN, SSR_PHASE_LOGN_MAX>(
+      ssr_phase_log2_nfft(q.N), [&](auto logn) { dist<TT, TE, decltype(logn)::value>(p, q, eps, grid); });
 }
 
 // tgt / est: float32 or float64 signals at tgt + tgt_off[t] / est + est_off[e]; out: [n_est][n_res + 1][2]
@@ -29,8 +26,7 @@ extern "C" int mrstft_emu(const void* tgt, int tgt_f64, const int64_t* tgt_off, 
                           double* out) {
   if (n_res < 1 || n_res > SSR_MRSTFT_MAX_RES) return -2;
   SsrMrstftSig p{};
-  p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = tgt_len; p.tgt_index = tgt_index;
-  p.n_tgt = n_tgt; p.n_est = n_est;
+  ssr_set_pair_sig(p, tgt, tgt_off, est, est_off, tgt_len, tgt_index, n_tgt, n_est);
   SsrMrstftAll a{};
   a.n_res = n_res; a.out = out;
   std::vector<std::vector<cx<double>>> tw(n_res);

@@ -14,11 +14,8 @@ template <typename TT, typename TE, int LOGN> static void dist(SsrPhaseParams& p
 }
 
 template <typename TT, typename TE> static void passes(SsrPhaseParams& p, int64_t grid) {
-  const int logn = ssr_phase_log2_nfft(p.N);
-  if (logn == 8) dist<TT, TE, 8>(p, grid);
-  else if (logn == 9) dist<TT, TE, 9>(p, grid);
-  else if (logn == 10) dist<TT, TE, 10>(p, grid);
-  else dist<TT, TE, 11>(p, grid);
+  ssr_dispatch_logn<SSR_PHASE_LOGN_MIN, SSR_PHASE_LOGN_MAX>(ssr_phase_log2_nfft(p.N),
+                                                            [&](auto logn) { dist<TT, TE, decltype(logn)::value>(p, grid); });
 }
 
 // tgt / est: float32 or float64 signals at tgt + tgt_off[t] / est + est_off[e]; out: [n_est][popcount(which)]
@@ -33,8 +30,8 @@ extern "C" int phase_emu(const void* tgt, int tgt_f64, const int64_t* tgt_off, c
   std::vector<int64_t> co(n_est + 1, -1), sums(SSR_PHASE_NT);
   std::vector<double> part(3 * chunks + 1, -777.0);
   SsrPhaseParams p{};
-  p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = tgt_len; p.tgt_index = tgt_index;
-  p.n_tgt = n_tgt; p.n_est = n_est; p.which = which; p.N = n_fft; p.H = hop; p.k_lo = bin_lo; p.k_hi = bin_hi;
+  ssr_set_pair_sig(p, tgt, tgt_off, est, est_off, tgt_len, tgt_index, n_tgt, n_est);
+  p.which = which; p.N = n_fft; p.H = hop; p.k_lo = bin_lo; p.k_hi = bin_hi;
   p.tw = tw.data(); p.chunk_off = co.data(); p.part = part.data(); p.out = out;
   SsrBlk blk{SSR_PHASE_NT};
   ssr_phase_geometry_body(p, blk, sums.data());

@@ -19,13 +19,8 @@ template <typename TT, typename TE> static void passes(SsrQualParams& p, int64_t
     SsrBlk blk{64};
     for (int64_t g = 0; g < run_frames; ++g) ssr_qual_lpc_body<TT, TE>(p, blk, g, *lds);
   }
-  if (p.which & (SSR_QUAL_WSS | SSR_QUAL_FWSEG)) {
-    const int logn = ssr_qual_log2_nfft(p.fs);
-    if (logn == 9) bands<TT, TE, 9>(p, run_frames);
-    else if (logn == 10) bands<TT, TE, 10>(p, run_frames);
-    else if (logn == 11) bands<TT, TE, 11>(p, run_frames);
-    else bands<TT, TE, 12>(p, run_frames);
-  }
+  if (p.which & (SSR_QUAL_WSS | SSR_QUAL_FWSEG))
+    ssr_dispatch_logn<9, 12>(ssr_qual_log2_nfft(p.fs), [&](auto logn) { bands<TT, TE, decltype(logn)::value>(p, run_frames); });
 }
 
 // tgt / est: float32 or float64 signals at tgt + tgt_off[t] / est + est_off[e]; out: [n_est][popcount(which)]
@@ -45,8 +40,8 @@ extern "C" int quality_emu(const void* tgt, int tgt_f64, const int64_t* tgt_off,
   std::vector<int64_t> rf(n_runs + 1), pf(n_est + 1), sums(3 * SSR_QUAL_NT);
   std::vector<double> win(ssr_qual_frame_len(fs) + 1), val(4 * pair_frames + 1, -777.0);
   SsrQualParams p{};
-  p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = tgt_len; p.tgt_index = tgt_index;
-  p.n_tgt = n_tgt; p.n_est = n_est; p.n_runs = n_runs; p.which = which; p.fs = fs;
+  ssr_set_pair_sig(p, tgt, tgt_off, est, est_off, tgt_len, tgt_index, n_tgt, n_est);
+  p.n_runs = n_runs; p.which = which; p.fs = fs;
   p.L = ssr_qual_frame_len(fs); p.R = ssr_qual_hop(fs); p.P = lpc_order ? lpc_order : ssr_qual_default_order(fs); p.N = t.N;
   p.run_start = rs.data(); p.run_frame = rf.data(); p.pair_frame = pf.data(); p.win = win.data();
   p.tw = t.tw.data(); p.fw = t.packed.data();

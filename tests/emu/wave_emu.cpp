@@ -31,8 +31,8 @@ extern "C" int wave_emu(const void* tgt, int tgt_f64, const int64_t* tgt_off, co
   std::vector<double> win(ssr_wave_frame_len(fs) + 1), p1(pair_tiles * SSR_WAVE_P1 + 1), p2(pair_tiles * SSR_WAVE_P2 + 1),
       fin(3 * n_est + 1);
   SsrWaveParams p{};
-  p.tgt = tgt; p.tgt_off = tgt_off; p.est = est; p.est_off = est_off; p.tgt_len = tgt_len; p.tgt_index = tgt_index;
-  p.n_tgt = n_tgt; p.n_est = n_est; p.n_runs = n_runs; p.which = which; p.fs = fs;
+  ssr_set_pair_sig(p, tgt, tgt_off, est, est_off, tgt_len, tgt_index, n_tgt, n_est);
+  p.n_runs = n_runs; p.which = which; p.fs = fs;
   p.L = ssr_wave_frame_len(fs); p.R = ssr_wave_hop(fs); p.fpt = ssr_wave_frames_per_tile(fs); p.tile = ssr_wave_tile_len(fs);
   p.run_start = rs.data(); p.run_tile = rt.data(); p.pair_tile = pt.data(); p.win = win.data();
   p.part1 = p1.data(); p.part2 = p2.data(); p.fin = fin.data(); p.out = out;
