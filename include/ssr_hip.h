@@ -305,6 +305,10 @@ int ssr_wave_metrics(const void* tgt, int tgt_f64, const int64_t* tgt_off, const
                      const void* est, int est_f64, const int64_t* est_off, const int32_t* tgt_index, int n_est,
                      int fs, int which, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Filter-invariant SDR (BSS Eval's SDR with a causal FIR filter of the target as the allowed distortion): the two
+ * entry points of that family and SSR_BSS_MAX_TAPS are declared in ssr_hip_bss.h, with the conventions of the waveform metrics. */
+#include "ssr_hip_bss.h"
+
 /* Mel-spectrogram distances (not in the reference) on magnitude images S [T][n_bins] (power 1):
  *   M[t][m] = Σ_f S[t][f] fb[f][m]           (float64 sums; E / G: the estimate's / target's mel image)
  *   SSR_MEL_LSD  mel_lsd = mean_t sqrt( mean_m log10( G² / (E + 1e-12)² + 1e-12 )² )        (AudioMetrics.lsd on mel magnitudes)

@@ -25,6 +25,7 @@ QUAL_LLR, QUAL_CEP, QUAL_WSS, QUAL_FWSEG = 1, 2, 4, 8                           
 PITCH_F0_RMSE, PITCH_F0_CORR, PITCH_GPE, PITCH_VDE, PITCH_FFE = 1, 2, 4, 8, 16  # SSR_PITCH_*
 PHASE_IP, PHASE_GD, PHASE_IAF = 1, 2, 4                                         # SSR_PHASE_IP, SSR_PHASE_GD, SSR_PHASE_IAF
 MRSTFT_MAX_RES = 8                                                              # SSR_MRSTFT_MAX_RES
+BSS_MAX_TAPS = 512                                                              # SSR_BSS_MAX_TAPS
 BOOTSTRAP_UTTERANCE, BOOTSTRAP_SPEAKER, BOOTSTRAP_MAX_Q = 0, 1, 8                # SSR_BOOTSTRAP_*
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
@@ -130,6 +131,12 @@ SIGNATURES = {
     "ssr_allreduce_sums": (_i, [_vp, _i, _vp, _vp]),
 }
 
+# name -> (restype, argtypes): exactly the symbols include/ssr_hip_bss.h declares (the part of the C ABI ssr_hip.h includes)
+BSS_SIGNATURES = {
+    "ssr_bss_sdr_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i]),
+    "ssr_bss_sdr": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -147,7 +154,7 @@ def load():
             "libssrhip.so not found at %s - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  ssr_eval_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **BSS_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

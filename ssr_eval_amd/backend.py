@@ -1106,6 +1106,41 @@ def mrstft_metrics(tgt_list, est_list, tgt_index, resolutions=None, band_bins=No
     return rows.reshape(-1, R + 1, 2)
 
 
+# ---- filter-invariant SDR: BSS Eval's SDR with a causal FIR filter of the target as the allowed distortion ---------------------
+BSS_TAPS = _lib.BSS_MAX_TAPS     # mir_eval's flen
+
+
+def check_bss_taps(taps):
+    """taps as an int, or ValueError: an integer in [1, 512] (the C ABI's own check)."""
+    if isinstance(taps, bool) or not isinstance(taps, (int, np.integer)) or not 1 <= int(taps) <= _lib.BSS_MAX_TAPS:
+        raise ValueError("taps must be an integer in [1, %d]" % _lib.BSS_MAX_TAPS)
+    return int(taps)
+
+
+def bss_sdr(tgt_list, est_list, tgt_index, taps=BSS_TAPS, return_filter=False, device=None, deferred=False):
+    """Filter-invariant SDR of estimate e against target tgt_index[e] (ssr_bss_sdr): waveforms (float32 or float64, each
+    estimate as long as its target; a list holding both dtypes is widened to float64) -> [n_est, 2] float64, columns sdr (dB) and
+    sdr_lag (the tap of the largest filter coefficient, in samples); return_filter: (that, the filters [n_est, taps]).  Device views
+    of one buffer are read where they lie; pairs next to each other that name one target compute its autocorrelation once.
+    deferred: a Pending (return_filter: a pair of them)."""
+    taps = check_bss_taps(taps)
+    lib = _lib.load()
+    filt = None
+    if return_filter:
+        dev = torch.device(device) if device is not None else default_device()
+        filt = torch.empty((len(est_list), taps), dtype=torch.float64, device=dev)
+    fp = _vp(filt)
+
+    def entry(*a):      # the filters go between `out` and the workspace
+        return lib.ssr_bss_sdr(*a[:-3], fp, *a[-3:])
+    rows = _pair_index_metrics(tgt_list, est_list, tgt_index, 2, _placed_where_they_lie,
+                               lambda *a: lib.ssr_bss_sdr_workspace_bytes(*a, taps), entry, (taps,), device, deferred)
+    if not return_filter:
+        return rows
+    with torch.cuda.device(filt.device):
+        return (rows, Pending(filt)) if deferred else (rows, filt.cpu().numpy())
+
+
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
 PITCH_FS = 16000                 # the rate every signal is tracked at
 PITCH_HOP = 160

@@ -31,7 +31,7 @@ def units():
 
 def _headers_mtime():
     deps = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + \
-        [os.path.join(os.path.dirname(_HERE), "include", "ssr_hip.h"), os.path.abspath(__file__)]
+        glob.glob(os.path.join(os.path.dirname(_HERE), "include", "*.h")) + [os.path.abspath(__file__)]
     return max(os.path.getmtime(d) for d in deps)
 
 

@@ -21,7 +21,7 @@ import torch
 from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
-from .metrics import AudioMetrics, which_mask, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, \
+from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, \
     _WAVE_NAMES
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
@@ -54,6 +54,16 @@ def all_key_order():
     """result_key_order(), then the keys of the families queued after _FAMILIES (_LATER_FAMILIES): the order a result lists its
     metrics in."""
     return result_key_order() + _MRSTFT_KEYS
+
+
+# the keys of SSR_Eval_Helper(bss_sdr=...), after every key of all_key_order()
+_BSS_KEYS = _BSS_NAMES
+
+
+def every_key_order():
+    """all_key_order(), then the keys of the families queued after _LATER_FAMILIES (_NEWER_FAMILIES): the order a result lists its
+    metrics in.  (result_key_order() and all_key_order() stay what they were when they were pinned.)"""
+    return all_key_order() + _BSS_KEYS
 
 
 def _option_dict(value):
@@ -105,6 +115,21 @@ def _mrstft_arguments(h, keys):
     return (q.get("resolutions"), q.get("band"), q.get("eps", B.MRSTFT_EPS)), {}
 
 
+def _bss_option(value):
+    """ValueError unless `value` is None, True or {"taps": an integer in [1, 512]}; -> the tap count (None: the family is off)."""
+    if value is None:
+        return None
+    if value is True:
+        return B.BSS_TAPS
+    if not isinstance(value, dict) or set(value) != {"taps"}:
+        raise ValueError("bss_sdr must be None, True or a dict of 'taps'")
+    return B.check_bss_taps(value["taps"])
+
+
+def _bss_arguments(h, keys):
+    return (_bss_option(h.bss_sdr),), {}
+
+
 # The optional metric families in the order they are queued on the stream and their keys appear in a result: (SSR_Eval_Helper
 # option, AudioMetrics method for K keys per file, method for a flat list of pairs, (helper, degradation keys of the call) -> the
 # (positional, keyword) arguments after the signals, whether those arguments hold one value per key - such a family takes the
@@ -123,6 +148,11 @@ _FAMILIES = (
 # Families added after "phase": queued behind _FAMILIES', their keys behind result_key_order()'s (all_key_order)
 _LATER_FAMILIES = (
     ("mrstft", "mrstft_multi", "mrstft_batch", _mrstft_arguments, False),
+)
+
+# Families added after "mrstft": queued behind _LATER_FAMILIES', their keys behind all_key_order()'s (every_key_order)
+_NEWER_FAMILIES = (
+    ("bss_sdr", "bss_sdr_multi", "bss_sdr_batch", _bss_arguments, False),
 )
 
 
@@ -201,7 +231,7 @@ class SSR_Eval_Helper:
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
-                 quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None):
+                 quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -231,6 +261,10 @@ class SSR_Eval_Helper:
         convergence and the log-magnitude distance of Parallel WaveGAN's multi-resolution STFT loss averaged over its three
         resolutions, and their sum (AudioMetrics.mrstft_multi / mrstft_batch at evaluation_sr); a dict =
         `resolutions` (up to 8 (n_fft, hop, win) in samples), `band` ((lo_hz, hi_hz), the band scored) and / or `eps`.
+        bss_sdr (not in the reference): None = off; True = every key also gets sdr / sdr_lag, BSS Eval's SDR in dB with a causal
+        512-tap FIR filter of the target as the allowed distortion - a delay or a colouring of the output costs nothing - and the
+        tap of that filter's largest coefficient, the output's latency in samples (AudioMetrics.bss_sdr_multi / bss_sdr_batch at
+        evaluation_sr); a dict = `taps` (1 .. 512).
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -249,6 +283,8 @@ class SSR_Eval_Helper:
             B.check_mrstft_eps(mrstft.get("eps", B.MRSTFT_EPS))
             AudioMetrics._mrstft_bins(evaluation_sr, B.check_mrstft_resolutions(mrstft.get("resolutions")), mrstft.get("band"))
         self.mrstft = mrstft
+        _bss_option(bss_sdr)
+        self.bss_sdr = bss_sdr
         if not isinstance(iir_exact, bool):
             raise ValueError("iir_exact must be True or False")
         self.iir_exact = iir_exact
@@ -594,12 +630,12 @@ class SSR_Eval_Helper:
                 values = self.audio_metrics.evaluation_multi(by_key, [all_tgt[i * K] for i in range(len(items))], resident=True, deferred=True)
             else:
                 values = self.audio_metrics.evaluation_batch(all_proc, all_tgt, resident=True, deferred=True)
-        # the optional families, queued behind the four metrics in the same deferred batch, in _FAMILIES' order, then _LATER_FAMILIES';
-        # the multi path analyses each target once for its K estimates
+        # the optional families, queued behind the four metrics in the same deferred batch, in _FAMILIES' order, then
+        # _LATER_FAMILIES' and _NEWER_FAMILIES'; the multi path analyses each target once for its K estimates
         queued = []
         if all_proc:
             same_keys = multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items)))
-            for option, multi_name, batch_name, arguments, per_key in _FAMILIES + _LATER_FAMILIES:
+            for option, multi_name, batch_name, arguments, per_key in _FAMILIES + _LATER_FAMILIES + _NEWER_FAMILIES:
                 if getattr(self, option) is None:
                     continue
                 if multi and (same_keys or not per_key):
@@ -769,7 +805,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = all_key_order()
+        order_keys = every_key_order()
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

@@ -30,6 +30,7 @@ _QUALITY_NAMES = ("llr", "cep_dist", "wss", "fwseg_snr")   # SSR_QUAL_LLR, SSR_Q
 _PITCH_NAMES = ("f0_rmse", "f0_corr", "gpe", "vde", "ffe")  # SSR_PITCH_F0_RMSE, _F0_CORR, _GPE, _VDE, _FFE: bits 0 .. 4
 _PHASE_NAMES = ("phase_ip", "phase_gd", "phase_iaf")       # SSR_PHASE_IP, SSR_PHASE_GD, SSR_PHASE_IAF: bits 0, 1, 2
 _MRSTFT_NAMES = ("mrstft_sc", "mrstft_mag", "mrstft")     # the means over the resolutions of ssr_mrstft_metrics, and their sum
+_BSS_NAMES = ("sdr", "sdr_lag")                           # the columns of ssr_bss_sdr
 
 
 def which_mask(which, names):
@@ -592,6 +593,43 @@ class AudioMetrics:
         dicts.  The K pairs of a target sit next to each other in one call."""
         ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
         return _regroup(self.mrstft_batch(ests, tgts, resolutions, band, eps, per_resolution, resident, deferred=True), n, K, deferred)
+
+    # ---- filter-invariant SDR (DESIGN §19): BSS Eval's SDR, the estimate projected on the target's `taps` causal shifts - a delay or
+    # a colouring of up to taps - 1 samples costs nothing, where snr and si_sdr collapse
+    def _bss_family(self, taps, return_filter):
+        taps = B.check_bss_taps(taps)
+
+        def call(tgts, ests, index):
+            got = B.bss_sdr(tgts, ests, index, taps, return_filter, self._device, deferred=True)
+            return (lambda: (got[0](), got[1]())) if return_filter else (lambda: (got(), None))
+
+        def dicts(vals):
+            rows, filt = vals
+            out = [{"sdr": float(r[0]), "sdr_lag": float(r[1])} for r in rows]
+            if filt is not None:
+                for d, c in zip(out, filt):
+                    d["filter"] = np.array(c)
+            return out
+        return call, dicts
+
+    def bss_sdr(self, est, target, taps=B.BSS_TAPS, return_filter=False):
+        """{'sdr', 'sdr_lag'} of one (estimate, target) pair: BSS Eval's SDR in dB with a causal `taps`-tap FIR filter of the target
+        as the allowed distortion (1 <= taps <= 512; 512 is mir_eval's), and the tap of the largest filter coefficient - the
+        estimate's latency in samples.  return_filter: also 'filter', the float64 [taps] least-squares filter.  An empty or digitally
+        silent target: NaN for both."""
+        return self.bss_sdr_batch([est], [target], taps, return_filter)[0]
+
+    def bss_sdr_batch(self, ests, targets, taps=B.BSS_TAPS, return_filter=False, resident=False, deferred=False):
+        """bss_sdr() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals,
+        read in their own dtype: one ssr_bss_sdr call per (target dtype, estimate dtype) group).  A target object passed for several
+        pairs next to each other is correlated with itself once.  deferred: as evaluation_batch."""
+        return self._pairs(self._bss_family(taps, return_filter), ests, targets, resident, deferred, by_dtype=True)
+
+    def bss_sdr_multi(self, ests_by_key, targets, taps=B.BSS_TAPS, return_filter=False, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  The K pairs of a target sit next to each other in one call: K + 1 correlations per target, not 2 K."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        return _regroup(self.bss_sdr_batch(ests, tgts, taps, return_filter, resident, deferred=True), n, K, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
