@@ -79,6 +79,8 @@ SIGNATURES = {
     "ssr_stoi_band_edges": (_i, [_vp, _vp]),
     "ssr_wave_metrics_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i]),
     "ssr_wave_metrics": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssr_bss_sdr_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i]),
+    "ssr_bss_sdr": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ssr_quality_metrics_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i, _i]),
     "ssr_quality_metrics": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ssr_quality_bands": (_i, [_i, _vp, _vp, _vp, _vp, _sz]),
@@ -131,12 +133,6 @@ SIGNATURES = {
     "ssr_allreduce_sums": (_i, [_vp, _i, _vp, _vp]),
 }
 
-# name -> (restype, argtypes): exactly the symbols include/ssr_hip_bss.h declares (the part of the C ABI ssr_hip.h includes)
-BSS_SIGNATURES = {
-    "ssr_bss_sdr_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i]),
-    "ssr_bss_sdr": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-}
-
 _lib = None
 
 
@@ -154,7 +150,7 @@ def load():
             "libssrhip.so not found at %s - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  ssr_eval_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **BSS_SIGNATURES}.items():
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

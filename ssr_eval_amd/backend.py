@@ -641,32 +641,46 @@ def _pair_keys_chunked(plan, est_lists, tgt_list, n_cols, budget, keys_per_chunk
         return Pending(out) if deferred else out.cpu().numpy()
 
 
-def spectrogram_lsd_bands(est, target, edges):
-    """est / target: [N, T, F] magnitude images (float32, on one device), edges: int [N][n_bands + 1] -> [N, n_bands] float64 device
-    tensor (ssr_spectrogram_lsd_bands)."""
+def _image_pairs(name, est, target, n_bins, extra):
+    """The image-level entry points ssr_spectrogram_<name> on est / target: [N, T, F] magnitude images (float32, on one device).
+    n_bins: the F a mel family's filterbank asks for - those families skip an empty batch and refuse images without rows here - or
+    None.  extra(N, F, dev) -> (columns of `out`, the query's arguments after max_rows, the call's arguments between n_bins and
+    out: a tensor among them passes its pointer and lives until the call is queued).  -> [N, columns] float64 device tensor."""
     require_gpu()
     lib = _lib.load()
     dev = est.device if isinstance(est, torch.Tensor) and est.is_cuda else default_device()
     with torch.cuda.device(dev):
         x = _dev_f32(est, dev).contiguous()
         y = _dev_f32(target, dev).contiguous()
-        if x.dim() != 3 or x.shape != y.shape:
-            raise ValueError("spectrogram shape mismatch: %s vs %s" % (tuple(x.shape), tuple(y.shape)))
+        if x.dim() != 3 or x.shape != y.shape or (n_bins is not None and int(x.shape[2]) != n_bins):
+            raise ValueError("spectrogram shape mismatch: %s vs %s" % (tuple(x.shape), tuple(y.shape)) if n_bins is None else
+                             "expected two [N, T, %d] images, got %s and %s" % (n_bins, tuple(x.shape), tuple(y.shape)))
         N, T, F = (int(v) for v in x.shape)
+        cols, ws_args, args = extra(N, F, dev)
+        out = torch.empty((N, cols), dtype=torch.float64, device=dev)
+        if N or n_bins is None:
+            if T < 1 and n_bins is not None:
+                raise ValueError("empty spectrogram")
+            off, rows = _uniform_images(N, T, dev)
+            ws_bytes = int(getattr(lib, "ssr_spectrogram_%s_workspace_bytes" % name)(N, T, *ws_args))
+            ws = _workspace(ws_bytes, dev)
+            _lib.check(getattr(lib, "ssr_spectrogram_" + name)(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, *_args(args), _vp(out),
+                                                               _vp(ws), ws_bytes, _stream()))
+        return out
+
+
+def spectrogram_lsd_bands(est, target, edges):
+    """est / target: [N, T, F] magnitude images (float32, on one device), edges: int [N][n_bands + 1] -> [N, n_bands] float64 device
+    tensor (ssr_spectrogram_lsd_bands)."""
+    def extra(N, F, dev):
         e = np.asarray(edges, dtype=np.int32)
         if e.ndim != 2 or e.shape[0] != N:
             raise ValueError("edges must be [n_images][n_bands + 1]")
         nb = e.shape[1] - 1
         if nb < 1:
             raise ValueError("at least one band (two edges) per image")
-        off, rows = _uniform_images(N, T, dev)
-        out = torch.empty((N, nb), dtype=torch.float64, device=dev)
-        ws_bytes = int(lib.ssr_spectrogram_lsd_bands_workspace_bytes(N, T, nb))
-        ws = _workspace(ws_bytes, dev)
-        ep = _host_i32(e, dev)
-        _lib.check(lib.ssr_spectrogram_lsd_bands(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, _vp(ep), nb, _vp(out), _vp(ws),
-                                                 ws_bytes, _stream()))
-        return out
+        return nb, (nb,), (_host_i32(e, dev), nb)
+    return _image_pairs("lsd_bands", est, target, None, extra)
 
 
 def pair_lsd_bands(plan, est_lists, tgt_list, edges, deferred=False, keys_per_chunk=None):
@@ -729,26 +743,8 @@ def spectrogram_mel(sp, fb):
 def spectrogram_mel_metrics(est, target, fb, n_cep, which):
     """est / target: [N, T, F] magnitude images -> [N, 3] float64 device tensor (mel_lsd, mel_l1, mcd; NaN where `which` does not
     ask; ssr_spectrogram_mel_metrics)."""
-    require_gpu()
-    lib = _lib.load()
-    dev = est.device if isinstance(est, torch.Tensor) and est.is_cuda else default_device()
     nb, nm, fp = _fb_arg(fb)
-    with torch.cuda.device(dev):
-        x = _dev_f32(est, dev).contiguous()
-        y = _dev_f32(target, dev).contiguous()
-        if x.dim() != 3 or x.shape != y.shape or int(x.shape[2]) != nb:
-            raise ValueError("expected two [N, T, %d] images, got %s and %s" % (nb, tuple(x.shape), tuple(y.shape)))
-        N, T, F = (int(v) for v in x.shape)
-        out = torch.empty((N, 3), dtype=torch.float64, device=dev)
-        if N:
-            if T < 1:
-                raise ValueError("empty spectrogram")
-            off, rows = _uniform_images(N, T, dev)
-            ws_bytes = int(lib.ssr_spectrogram_mel_metrics_workspace_bytes(N, T, F, nm, int(n_cep)))
-            ws = _workspace(ws_bytes, dev)
-            _lib.check(lib.ssr_spectrogram_mel_metrics(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, fp, nm, int(n_cep), int(which),
-                                                       _vp(out), _vp(ws), ws_bytes, _stream()))
-        return out
+    return _image_pairs("mel_metrics", est, target, nb, lambda N, F, dev: (3, (F, nm, int(n_cep)), (fp, nm, int(n_cep), int(which))))
 
 
 def pair_mel_metrics(plan, est_lists, tgt_list, fb, n_cep, which, deferred=False, keys_per_chunk=None):
@@ -769,26 +765,8 @@ def pair_mel_metrics(plan, est_lists, tgt_list, fb, n_cep, which, deferred=False
 
 def spectrogram_mel_dtw(est, target, fb, n_cep, radius):
     """est / target: [N, T, F] magnitude images -> [N, 3] float64 device tensor (mcd_dtw, dtw_dev, dtw_len; ssr_spectrogram_mel_dtw)."""
-    require_gpu()
-    lib = _lib.load()
-    dev = est.device if isinstance(est, torch.Tensor) and est.is_cuda else default_device()
     nb, nm, fp = _fb_arg(fb)
-    with torch.cuda.device(dev):
-        x = _dev_f32(est, dev).contiguous()
-        y = _dev_f32(target, dev).contiguous()
-        if x.dim() != 3 or x.shape != y.shape or int(x.shape[2]) != nb:
-            raise ValueError("expected two [N, T, %d] images, got %s and %s" % (nb, tuple(x.shape), tuple(y.shape)))
-        N, T, F = (int(v) for v in x.shape)
-        out = torch.empty((N, 3), dtype=torch.float64, device=dev)
-        if N:
-            if T < 1:
-                raise ValueError("empty spectrogram")
-            off, rows = _uniform_images(N, T, dev)
-            ws_bytes = int(lib.ssr_spectrogram_mel_dtw_workspace_bytes(N, T, F, nm, int(n_cep), int(radius)))
-            ws = _workspace(ws_bytes, dev)
-            _lib.check(lib.ssr_spectrogram_mel_dtw(_vp(x), _vp(off), _vp(y), _vp(off), _vp(rows), N, T, F, fp, nm, int(n_cep), int(radius),
-                                                   _vp(out), _vp(ws), ws_bytes, _stream()))
-        return out
+    return _image_pairs("mel_dtw", est, target, nb, lambda N, F, dev: (3, (F, nm, int(n_cep), int(radius)), (fp, nm, int(n_cep), int(radius))))
 
 
 def pair_mel_dtw(plan, est_lists, tgt_list, fb, n_cep, radius, deferred=False, keys_per_chunk=None):

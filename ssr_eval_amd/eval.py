@@ -31,39 +31,10 @@ from .utils import dict_mean, write_json
 _METRIC_KEYS = ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi", "estoi")
 # SSR_Eval_Helper(stoi=...) -> AudioMetrics.stoi_* `extended`
 _STOI_OPTIONS = {"stoi": False, "estoi": True, "both": "both"}
-# the keys of SSR_Eval_Helper(waveform=...), (mel=...), (quality=...) and (pitch=...), in that order after every key of _METRIC_KEYS
-# (only present in runs that ask for them)
-_WAVEFORM_KEYS, _MEL_KEYS, _QUALITY_KEYS, _PITCH_KEYS = _WAVE_NAMES, _MEL_NAMES, _QUALITY_NAMES, _PITCH_NAMES
-# the keys of SSR_Eval_Helper(mel_dtw=...), after the mel keys (dtw_len, a count of path cells, is not a per-key result: its mean
-# over files of different lengths says nothing)
-_MEL_DTW_KEYS = _MEL_DTW_NAMES[:2]
-# the keys of SSR_Eval_Helper(phase=...), after every other key
-_PHASE_KEYS = _PHASE_NAMES
-
-
-def result_key_order():
-    """Every built-in metric key in the order a result lists them."""
-    return _METRIC_KEYS + _WAVEFORM_KEYS + _MEL_KEYS + _MEL_DTW_KEYS + _QUALITY_KEYS + _PITCH_KEYS + _PHASE_KEYS
-
-
-# the keys of SSR_Eval_Helper(mrstft=...), after every key of result_key_order()
-_MRSTFT_KEYS = _MRSTFT_NAMES
-
-
-def all_key_order():
-    """result_key_order(), then the keys of the families queued after _FAMILIES (_LATER_FAMILIES): the order a result lists its
-    metrics in."""
-    return result_key_order() + _MRSTFT_KEYS
-
-
-# the keys of SSR_Eval_Helper(bss_sdr=...), after every key of all_key_order()
-_BSS_KEYS = _BSS_NAMES
-
-
-def every_key_order():
-    """all_key_order(), then the keys of the families queued after _LATER_FAMILIES (_NEWER_FAMILIES): the order a result lists its
-    metrics in.  (result_key_order() and all_key_order() stay what they were when they were pinned.)"""
-    return all_key_order() + _BSS_KEYS
+# the keys of the other families (only present in runs that ask for them).  dtw_len, a count of path cells, is not a per-key
+# result: its mean over files of different lengths says nothing
+_WAVEFORM_KEYS, _MEL_KEYS, _MEL_DTW_KEYS, _QUALITY_KEYS, _PITCH_KEYS = _WAVE_NAMES, _MEL_NAMES, _MEL_DTW_NAMES[:2], _QUALITY_NAMES, _PITCH_NAMES
+_PHASE_KEYS, _MRSTFT_KEYS, _BSS_KEYS = _PHASE_NAMES, _MRSTFT_NAMES, _BSS_NAMES
 
 
 def _option_dict(value):
@@ -73,87 +44,151 @@ def _option_dict(value):
 
 def _which_option(option, value, names, entries):
     """ValueError unless `value` is one of `names`, "all", a non-empty tuple of names, or a non-empty dict of 'which' and / or
-    `entries`; -> its dict form."""
+    `entries`."""
     if isinstance(value, dict) and (not value or set(value) - {"which", *entries}):
         takes = ["'%s'" % k for k in ("which",) + tuple(entries)]
         raise ValueError("a %s dict takes %s and / or %s" % (option, ", ".join(takes[:-1]), takes[-1]))
-    q = _option_dict(value)
-    w = q.get("which", "all")
+    w = _option_dict(value).get("which", "all")
     if not (isinstance(w, str) or (isinstance(w, tuple) and w and all(isinstance(m, str) for m in w))):
         raise ValueError("%s must be None, True, one of %s, a tuple of them or a dict" % (option, names))
     which_mask(w, names)
-    return q
 
 
-def _mel_arguments(h, keys):
-    q = _option_dict(h.mel)
-    return (q.get("which", "all"),), {k: v for k, v in q.items() if k != "which"}
+# A family's two functions: check(helper, value) raises ValueError for a value of the option the family does not take (it sees
+# every value but None: None is "off"), arguments(helper, degradation keys of the call) -> the (positional, keyword) arguments of
+# the family's AudioMetrics methods after the signals.  Where both need an option's defaults, *_args spells them out once.
+def _lsd_split_check(h, v):
+    if not (v is True or (isinstance(v, numbers.Real) and not isinstance(v, bool))):
+        raise ValueError("lsd_split must be None, True or a split frequency in Hz")
 
 
-def _mel_dtw_arguments(h, keys):
-    q = dict(h.mel_dtw) if isinstance(h.mel_dtw, dict) else {}
-    return (q.pop("radius", 16),), dict(q, lengths=False)
+def _stoi_check(h, v):
+    if not (isinstance(v, str) and v in _STOI_OPTIONS):
+        raise ValueError("stoi must be None, 'stoi', 'estoi' or 'both'")
 
 
-def _quality_arguments(h, keys):
-    q = _option_dict(h.quality)
-    return (q.get("which", "all"), q.get("lpc_order")), {}
+def _waveform_check(h, v):
+    try:                                       # True, a name or a tuple of names: no "all", no list, no dict
+        ok = v is True or (isinstance(v, (str, tuple)) and v != "all" and which_mask(v, _WAVEFORM_KEYS) > 0)
+    except ValueError:
+        ok = False
+    if not ok:
+        raise ValueError("waveform must be None, True, one of %s or a tuple of them" % (_WAVEFORM_KEYS,))
 
 
-def _pitch_arguments(h, keys):
-    q = _option_dict(h.pitch)
-    return (q.get("which", "all"), q.get("fmin", 50.0), q.get("fmax", 500.0)), {}
+def _mel_args(v):
+    q = _option_dict(v)
+    return (q.get("which", "all"),), {k: o for k, o in q.items() if k != "which"}
 
 
-def _phase_arguments(h, keys):
-    q = _option_dict(h.phase)
-    return (q.get("which", "all"), q.get("n_fft", 1024), q.get("hop"), q.get("band")), {}
+def _mel_check(h, v):
+    if not (v is True or isinstance(v, dict)):
+        raise ValueError("mel must be None, True or a dict of mel options")
+    if isinstance(v, dict):                        # every option checked here, not at the first batch
+        (which,), opts = _mel_args(v)
+        which_mask(which, _MEL_KEYS)
+        h.audio_metrics._mel_fb(**opts)
 
 
-def _mrstft_arguments(h, keys):
-    q = h.mrstft if isinstance(h.mrstft, dict) else {}
-    return (q.get("resolutions"), q.get("band"), q.get("eps", B.MRSTFT_EPS)), {}
+def _mel_dtw_args(v, **more):
+    q = dict(v) if isinstance(v, dict) else {}
+    return (q.pop("radius", 16),), dict(q, **more)
 
 
-def _bss_option(value):
-    """ValueError unless `value` is None, True or {"taps": an integer in [1, 512]}; -> the tap count (None: the family is off)."""
-    if value is None:
-        return None
-    if value is True:
+def _mel_dtw_check(h, v):
+    if not (v is True or isinstance(v, dict)):
+        raise ValueError("mel_dtw must be None, True or a dict of `radius` and mel options")
+    (radius,), opts = _mel_dtw_args(v)             # every option checked here, not at the first batch
+    AudioMetrics.dtw_radius(radius)
+    h.audio_metrics._mel_fb(**opts)
+
+
+def _quality_args(v):
+    q = _option_dict(v)
+    return q.get("which", "all"), q.get("lpc_order")
+
+
+def _quality_check(h, v):
+    if v is not True:
+        _which_option("quality", v, _QUALITY_KEYS, ("lpc_order",))
+        AudioMetrics._quality_order(_quality_args(v)[1])
+        if h.evaluationset_sr < 8000:
+            raise ValueError("the quality measures need evaluation_sr >= 8000")
+
+
+def _pitch_args(v):
+    q = _option_dict(v)
+    return q.get("which", "all"), q.get("fmin", 50.0), q.get("fmax", 500.0)
+
+
+def _pitch_check(h, v):
+    if v is not True:
+        _which_option("pitch", v, _PITCH_KEYS, ("fmin", "fmax"))
+        AudioMetrics._pitch_range(*_pitch_args(v)[1:])
+    if not 8000 <= h.evaluationset_sr <= 48000:
+        raise ValueError("the pitch metrics need 8000 <= evaluation_sr <= 48000")
+
+
+def _phase_args(v):
+    q = _option_dict(v)
+    return q.get("which", "all"), q.get("n_fft", 1024), q.get("hop"), q.get("band")
+
+
+def _phase_check(h, v):
+    if v is not True:
+        _which_option("phase", v, _PHASE_KEYS, ("n_fft", "hop", "band"))
+        _, n_fft, hop, band = _phase_args(v)
+        AudioMetrics._phase_bins(h.evaluationset_sr, B.check_phase_frames(n_fft, hop)[0], band)
+
+
+def _mrstft_args(v):
+    q = v if isinstance(v, dict) else {}
+    return q.get("resolutions"), q.get("band"), q.get("eps", B.MRSTFT_EPS)
+
+
+def _mrstft_check(h, v):
+    if v is not True:
+        if not isinstance(v, dict) or not v or set(v) - {"resolutions", "band", "eps"}:
+            raise ValueError("mrstft must be None, True or a dict of 'resolutions', 'band' and / or 'eps'")
+        resolutions, band, eps = _mrstft_args(v)
+        B.check_mrstft_eps(eps)
+        AudioMetrics._mrstft_bins(h.evaluationset_sr, B.check_mrstft_resolutions(resolutions), band)
+
+
+def _bss_taps(h, v):
+    """ValueError unless `v` is True or {"taps": an integer in [1, 512]}; -> the tap count."""
+    if v is True:
         return B.BSS_TAPS
-    if not isinstance(value, dict) or set(value) != {"taps"}:
+    if not isinstance(v, dict) or set(v) != {"taps"}:
         raise ValueError("bss_sdr must be None, True or a dict of 'taps'")
-    return B.check_bss_taps(value["taps"])
+    return B.check_bss_taps(v["taps"])
 
 
-def _bss_arguments(h, keys):
-    return (_bss_option(h.bss_sdr),), {}
-
-
-# The optional metric families in the order they are queued on the stream and their keys appear in a result: (SSR_Eval_Helper
-# option, AudioMetrics method for K keys per file, method for a flat list of pairs, (helper, degradation keys of the call) -> the
-# (positional, keyword) arguments after the signals, whether those arguments hold one value per key - such a family takes the
-# multi path only when every file has the same keys).
+# The optional metric families in the order they are queued on the stream and their keys appear in a result.  option: the
+# SSR_Eval_Helper argument; multi / batch: the AudioMetrics methods for K keys per file / for a flat list of pairs; keys: what the
+# family adds to a key's result; check, arguments: above; per_key: the arguments hold one value per degradation key - such a family
+# takes the multi path only when every file has the same keys.
+_Family = collections.namedtuple("_Family", "option multi batch keys check arguments per_key")
 _FAMILIES = (
-    ("lsd_split", "lsd_split_multi", "lsd_split_batch", lambda h, keys: (([h.split_cutoff_hz(k) for k in keys],), {}), True),
-    ("stoi", "stoi_multi", "stoi_batch", lambda h, keys: ((_STOI_OPTIONS[h.stoi],), {}), False),
-    ("waveform", "waveform_multi", "waveform_batch", lambda h, keys: ((_option_dict(h.waveform)["which"],), {}), False),
-    ("mel", "mel_distance_multi", "mel_distance_batch", _mel_arguments, False),
-    ("mel_dtw", "mel_dtw_multi", "mel_dtw_batch", _mel_dtw_arguments, False),
-    ("quality", "quality_multi", "quality_batch", _quality_arguments, False),
-    ("pitch", "pitch_multi", "pitch_batch", _pitch_arguments, False),
-    ("phase", "phase_distance_multi", "phase_distance_batch", _phase_arguments, False),
+    _Family("lsd_split", "lsd_split_multi", "lsd_split_batch", _METRIC_KEYS[4:6], _lsd_split_check,
+            lambda h, keys: (([h.split_cutoff_hz(k) for k in keys],), {}), True),
+    _Family("stoi", "stoi_multi", "stoi_batch", _METRIC_KEYS[6:8], _stoi_check, lambda h, keys: ((_STOI_OPTIONS[h.stoi],), {}), False),
+    _Family("waveform", "waveform_multi", "waveform_batch", _WAVEFORM_KEYS, _waveform_check,
+            lambda h, keys: ((_option_dict(h.waveform)["which"],), {}), False),
+    _Family("mel", "mel_distance_multi", "mel_distance_batch", _MEL_KEYS, _mel_check, lambda h, keys: _mel_args(h.mel), False),
+    _Family("mel_dtw", "mel_dtw_multi", "mel_dtw_batch", _MEL_DTW_KEYS, _mel_dtw_check,
+            lambda h, keys: _mel_dtw_args(h.mel_dtw, lengths=False), False),
+    _Family("quality", "quality_multi", "quality_batch", _QUALITY_KEYS, _quality_check, lambda h, keys: (_quality_args(h.quality), {}), False),
+    _Family("pitch", "pitch_multi", "pitch_batch", _PITCH_KEYS, _pitch_check, lambda h, keys: (_pitch_args(h.pitch), {}), False),
+    _Family("phase", "phase_distance_multi", "phase_distance_batch", _PHASE_KEYS, _phase_check, lambda h, keys: (_phase_args(h.phase), {}), False),
+    _Family("mrstft", "mrstft_multi", "mrstft_batch", _MRSTFT_KEYS, _mrstft_check, lambda h, keys: (_mrstft_args(h.mrstft), {}), False),
+    _Family("bss_sdr", "bss_sdr_multi", "bss_sdr_batch", _BSS_KEYS, _bss_taps, lambda h, keys: ((_bss_taps(h, h.bss_sdr),), {}), False),
 )
 
-# Families added after "phase": queued behind _FAMILIES', their keys behind result_key_order()'s (all_key_order)
-_LATER_FAMILIES = (
-    ("mrstft", "mrstft_multi", "mrstft_batch", _mrstft_arguments, False),
-)
 
-# Families added after "mrstft": queued behind _LATER_FAMILIES', their keys behind all_key_order()'s (every_key_order)
-_NEWER_FAMILIES = (
-    ("bss_sdr", "bss_sdr_multi", "bss_sdr_batch", _bss_arguments, False),
-)
+def result_key_order():
+    """Every built-in metric key in the order a result lists them: the reference's four, then each family's."""
+    return _METRIC_KEYS[:4] + tuple(k for f in _FAMILIES for k in f.keys)
 
 
 def key_cutoff_hz(key):
@@ -273,49 +308,18 @@ class SSR_Eval_Helper:
         result["confidence"] = {"settings": {...}, "averaged": {key: {metric: {"se", "lo", "hi"}}}}, the percentile bootstrap of the
         "averaged" block (ssr_eval_amd.stats.bootstrap_ci)."""
         self.bootstrap = None if bootstrap is None else bootstrap_option(bootstrap)
-        if phase is not None and phase is not True:
-            fq = _which_option("phase", phase, _PHASE_KEYS, ("n_fft", "hop", "band"))
-            AudioMetrics._phase_bins(evaluation_sr, B.check_phase_frames(fq.get("n_fft", 1024), fq.get("hop"))[0], fq.get("band"))
-        self.phase = phase
-        if mrstft is not None and mrstft is not True:
-            if not isinstance(mrstft, dict) or not mrstft or set(mrstft) - {"resolutions", "band", "eps"}:
-                raise ValueError("mrstft must be None, True or a dict of 'resolutions', 'band' and / or 'eps'")
-            B.check_mrstft_eps(mrstft.get("eps", B.MRSTFT_EPS))
-            AudioMetrics._mrstft_bins(evaluation_sr, B.check_mrstft_resolutions(mrstft.get("resolutions")), mrstft.get("band"))
-        self.mrstft = mrstft
-        _bss_option(bss_sdr)
-        self.bss_sdr = bss_sdr
         if not isinstance(iir_exact, bool):
             raise ValueError("iir_exact must be True or False")
         self.iir_exact = iir_exact
-        if pitch is not None:
-            if pitch is not True:
-                pq = _which_option("pitch", pitch, _PITCH_KEYS, ("fmin", "fmax"))
-                AudioMetrics._pitch_range(pq.get("fmin", 50.0), pq.get("fmax", 500.0))
-            if not 8000 <= evaluation_sr <= 48000:
-                raise ValueError("the pitch metrics need 8000 <= evaluation_sr <= 48000")
-        self.pitch = pitch
-        if quality is not None and quality is not True:
-            AudioMetrics._quality_order(_which_option("quality", quality, _QUALITY_KEYS, ("lpc_order",)).get("lpc_order"))
-            if evaluation_sr < 8000:
-                raise ValueError("the quality measures need evaluation_sr >= 8000")
-        self.quality = quality
-        if not (mel is None or mel is True or isinstance(mel, dict)):
-            raise ValueError("mel must be None, True or a dict of mel options")
-        if waveform is not None and waveform is not True:
-            try:                                       # a name or a tuple of names: no "all", no list, no dict
-                ok = isinstance(waveform, (str, tuple)) and waveform != "all" and which_mask(waveform, _WAVEFORM_KEYS) > 0
-            except ValueError:
-                ok = False
-            if not ok:
-                raise ValueError("waveform must be None, True, one of %s or a tuple of them" % (_WAVEFORM_KEYS,))
-        self.waveform = waveform
-        if stoi is not None and not (isinstance(stoi, str) and stoi in _STOI_OPTIONS):
-            raise ValueError("stoi must be None, 'stoi', 'estoi' or 'both'")
-        self.stoi = stoi
-        if lsd_split is not None and not (lsd_split is True or (isinstance(lsd_split, numbers.Real) and not isinstance(lsd_split, bool))):
-            raise ValueError("lsd_split must be None, True or a split frequency in Hz")
-        self.lsd_split = lsd_split
+        self.evaluationset_sr = evaluation_sr
+        self.audio_metrics = AudioMetrics(self.evaluationset_sr, precision=precision, device=device)
+        # every family option is checked here, before the caller's settings are touched (the mel checks need audio_metrics)
+        options = dict(lsd_split=lsd_split, stoi=stoi, waveform=waveform, mel=mel, mel_dtw=mel_dtw, quality=quality, pitch=pitch,
+                       phase=phase, mrstft=mrstft, bss_sdr=bss_sdr)
+        for f in _FAMILIES:
+            if options[f.option] is not None:
+                f.check(self, options[f.option])
+            setattr(self, f.option, options[f.option])
         self.testee = testee
         self.test_name = test_name
         self.test_data_root = test_data_root
@@ -326,21 +330,7 @@ class SSR_Eval_Helper:
         self.setting_mp3_compression = setting_mp3_compression
         self.model_input_sr = input_sr
         self.model_output_sr = output_sr
-        self.evaluationset_sr = evaluation_sr
         assert self.evaluationset_sr <= 48000, "Our evaluation set only support up to 48 kHz target sampling rate"
-        self.audio_metrics = AudioMetrics(self.evaluationset_sr, precision=precision, device=device)
-        self.mel = mel
-        if isinstance(mel, dict):                      # every option checked here, not at the first batch
-            (which,), opts = _mel_arguments(self, ())
-            which_mask(which, _MEL_KEYS)
-            self.audio_metrics._mel_fb(**opts)
-        if not (mel_dtw is None or mel_dtw is True or isinstance(mel_dtw, dict)):
-            raise ValueError("mel_dtw must be None, True or a dict of `radius` and mel options")
-        self.mel_dtw = mel_dtw
-        if mel_dtw is not None:
-            opts = dict(mel_dtw) if isinstance(mel_dtw, dict) else {}          # every option checked here, not at the first batch
-            AudioMetrics.dtw_radius(opts.pop("radius", 16))
-            self.audio_metrics._mel_fb(**opts)
         self.unexpected_symbol_test_folder = "_.*#()_+=!@$%^&~"
         self._device = device
         if test_data_root is not None and not os.path.exists(test_data_root):
@@ -630,22 +620,22 @@ class SSR_Eval_Helper:
                 values = self.audio_metrics.evaluation_multi(by_key, [all_tgt[i * K] for i in range(len(items))], resident=True, deferred=True)
             else:
                 values = self.audio_metrics.evaluation_batch(all_proc, all_tgt, resident=True, deferred=True)
-        # the optional families, queued behind the four metrics in the same deferred batch, in _FAMILIES' order, then
-        # _LATER_FAMILIES' and _NEWER_FAMILIES'; the multi path analyses each target once for its K estimates
+        # the optional families, queued behind the four metrics in the same deferred batch, in _FAMILIES' order; the multi path
+        # analyses each target once for its K estimates
         queued = []
         if all_proc:
             same_keys = multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items)))
-            for option, multi_name, batch_name, arguments, per_key in _FAMILIES + _LATER_FAMILIES + _NEWER_FAMILIES:
-                if getattr(self, option) is None:
+            for f in _FAMILIES:
+                if getattr(self, f.option) is None:
                     continue
-                if multi and (same_keys or not per_key):
-                    args, kw = arguments(self, all_keys[:K])
-                    rows = getattr(self.audio_metrics, multi_name)(by_key, [all_tgt[i * K] for i in range(len(items))], *args,
-                                                                   resident=True, deferred=True, **kw)
+                if multi and (same_keys or not f.per_key):
+                    args, kw = f.arguments(self, all_keys[:K])
+                    rows = getattr(self.audio_metrics, f.multi)(by_key, [all_tgt[i * K] for i in range(len(items))], *args,
+                                                                resident=True, deferred=True, **kw)
                     queued.append(lambda rows=rows: [r for row in rows() for r in row])
                 else:
-                    args, kw = arguments(self, all_keys)
-                    queued.append(getattr(self.audio_metrics, batch_name)(all_proc, all_tgt, *args, resident=True, deferred=True, **kw))
+                    args, kw = f.arguments(self, all_keys)
+                    queued.append(getattr(self.audio_metrics, f.batch)(all_proc, all_tgt, *args, resident=True, deferred=True, **kw))
         self._last_processed = None
         keep = list(zip(owner, all_keys, all_proc)) if self.save_processed_result else None
 
@@ -805,7 +795,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = every_key_order()
+        order_keys = result_key_order()
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

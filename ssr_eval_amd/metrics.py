@@ -67,6 +67,11 @@ def _regroup(flat, n, K, deferred):
     return finish if deferred else finish()
 
 
+def _by_dtype(j, wide):
+    """The keyed drivers' group of a family whose estimates of one dtype share a call."""
+    return wide
+
+
 def _shared_targets(targets):
     """-> (the distinct target objects, the index of every entry among them): a target object passed for several pairs (at one
     length) is analysed once."""
@@ -239,68 +244,92 @@ class AudioMetrics:
         v = B.spectrogram_lsd_bands(est.reshape(Bn * Cn, T, F), target.reshape(Bn * Cn, T, F), e.reshape(Bn * Cn, -1))
         return v.to(est.device).reshape(Bn, Cn, -1)
 
+    # The image families (band-split LSD, the mel distances, mel_dtw) hold K + 1 magnitude images per item: estimates that may share
+    # a launch sequence form a group.  group(j, float64 estimates) -> the group of pair / key j, None: no call, the entry is
+    # `default`; run(est_lists, tgt_list, members) -> Pending of [n, K, cols] for the group's members; to_dict(row, j) -> the dict.
+    def _keyed_batch(self, group, run, to_dict, default, ests, targets, resident, deferred):
+        """Lists of pairs with evaluation_batch's input rules: one call of one key per group of pairs."""
+        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
+        groups = {}
+        for i, (e, _) in enumerate(pairs):
+            g = group(i, bool(B._is_f64(e)))
+            if g is not None:
+                groups.setdefault(g, []).append(i)
+        pending = [(idx, run([[pairs[i][0] for i in idx]], [pairs[i][1] for i in idx], idx)) for idx in groups.values()]
+
+        def finish():
+            out = [default if default is None else dict(default) for _ in pairs]
+            for idx, p in pending:
+                vals = p()
+                for r, i in enumerate(idx):
+                    out[i] = to_dict(vals[r, 0], i)
+            return out
+        return finish if deferred else finish()
+
+    def _keyed_multi(self, group, run, to_dict, default, batch, ests_by_key, targets, resident, deferred):
+        """K estimates per target: the keys of a group share one multi-key launch sequence (the target transformed once per chunk of
+        keys); lengths that differ between keys, or a key with both dtypes, send the pairs through batch(ests, targets) (deferred,
+        resident)."""
+        K, n = len(ests_by_key), len(targets)
+        pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for i in range(n)] for k in range(K)]
+        same_len = all(len({pairs[k][i][0].shape[0] for k in range(K)}) == 1 for i in range(n))
+        kinds = [{bool(B._is_f64(pairs[k][i][0])) for i in range(n)} for k in range(K)]
+        if n == 0 or not same_len or any(len(kd) != 1 for kd in kinds):
+            flat = _item_major(pairs, n, K)
+            return _regroup(batch([e for e, _ in flat], [t for _, t in flat]), n, K, deferred)
+        tgts = [pairs[0][i][1] for i in range(n)]
+        groups = {}
+        for k in range(K):
+            g = group(k, next(iter(kinds[k])))
+            if g is not None:
+                groups.setdefault(g, []).append(k)
+        pending = [(keys, run([[pairs[k][i][0] for i in range(n)] for k in keys], tgts, keys)) for keys in groups.values()]
+
+        def finish():
+            out = [[default if default is None else dict(default) for _ in range(K)] for _ in range(n)]
+            for keys, p in pending:
+                vals = p()
+                for i in range(n):
+                    for j, k in enumerate(keys):
+                        out[i][k] = to_dict(vals[i, j], k)
+            return out
+        return finish if deferred else finish()
+
     def lsd_split(self, est, target, cutoff_hz):
         """{'lsd_lf', 'lsd_hf'} of one (estimate, target) pair split at cutoff_hz."""
         return self.lsd_split_batch([est], [target], [cutoff_hz])[0]
 
+    def _split_family(self, cutoffs_hz):
+        """-> (group, to_dict, default) of the keyed drivers, and the band edges per cutoff: estimates of one dtype and band count
+        share a call, a cutoff of None has none."""
+        split = [self._split_edges(c) for c in cutoffs_hz]
+        return (lambda j, wide: None if split[j][0] is None else (wide, len(split[j][0]) - 1),
+                lambda row, j: self._split_dict(row, split[j][1]), self._split_dict((), (None, None))), [edges for edges, _ in split]
+
     def lsd_split_batch(self, ests, targets, cutoffs_hz, resident=False, deferred=False):
         """lsd_split for lists of pairs (the input rules of evaluation_batch: metrics.py:89-90 truncation, float64 estimates kept
         float64; float32 targets).  cutoffs_hz: one value for every pair, or one per pair (None: both values NaN)."""
-        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
-        cuts = list(cutoffs_hz) if isinstance(cutoffs_hz, (list, tuple)) else [cutoffs_hz] * len(pairs)
-        if len(cuts) != len(pairs):
+        n = min(len(ests), len(targets))
+        cuts = list(cutoffs_hz) if isinstance(cutoffs_hz, (list, tuple)) else [cutoffs_hz] * n
+        if len(cuts) != n:
             raise ValueError("one cutoff per pair")
-        split = [self._split_edges(c) for c in cuts]
-        groups = {}                      # (float64 estimate, number of bands) -> pair indices: one ssr_pair_lsd_bands call each
-        for i, (edges, _) in enumerate(split):
-            if edges is not None:
-                groups.setdefault((bool(B._is_f64(pairs[i][0])), len(edges) - 1), []).append(i)
-        pending = [(idx, B.pair_lsd_bands(self._plan(), [[pairs[i][0] for i in idx]], [pairs[i][1] for i in idx],
-                                          [[split[i][0] for i in idx]], deferred=True)) for idx in groups.values()]
-
-        def finish():
-            out = [self._split_dict((), (None, None)) for _ in pairs]
-            for idx, p in pending:
-                vals = p()
-                for r, i in enumerate(idx):
-                    out[i] = self._split_dict(vals[r, 0], split[i][1])
-            return out
-        return finish if deferred else finish()
+        (group, to_dict, default), edges = self._split_family(cuts)
+        return self._keyed_batch(group, lambda e, t, idx: B.pair_lsd_bands(self._plan(), e, t, [[edges[i] for i in idx]], deferred=True),
+                                 to_dict, default, ests, targets, resident, deferred)
 
     def lsd_split_multi(self, ests_by_key, targets, cutoffs_hz, resident=False, deferred=False, keys_per_chunk=None):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms, cutoffs_hz = one
         split frequency per key (None: NaN) -> n lists of K {'lsd_lf', 'lsd_hf'}.  Keys with the same estimate dtype and band count
         share one multi-key launch sequence (the target transformed once per chunk of keys); otherwise - lengths that differ between
         keys, a key with both dtypes - the pairs go through lsd_split_batch."""
-        K, n = len(ests_by_key), len(targets)
-        if len(cutoffs_hz) != K:
+        n = len(targets)
+        if len(cutoffs_hz) != len(ests_by_key):
             raise ValueError("one cutoff per key")
-        pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for i in range(n)] for k in range(K)]
-        same_len = all(len({pairs[k][i][0].shape[0] for k in range(K)}) == 1 for i in range(n))
-        kinds = [{bool(B._is_f64(pairs[k][i][0])) for i in range(n)} for k in range(K)]
-        if n == 0 or not same_len or any(len(kd) != 1 for kd in kinds):
-            flat = _item_major(pairs, n, K)
-            return _regroup(self.lsd_split_batch([e for e, _ in flat], [t for _, t in flat], list(cutoffs_hz) * n, True, deferred=True),
-                            n, K, deferred)
-        tgts = [pairs[0][i][1] for i in range(n)]
-        split = [self._split_edges(c) for c in cutoffs_hz]
-        groups = {}
-        for k, (edges, _) in enumerate(split):
-            if edges is not None:
-                groups.setdefault((next(iter(kinds[k])), len(edges) - 1), []).append(k)
-        pending = [(keys, B.pair_lsd_bands(self._plan(), [[pairs[k][i][0] for i in range(n)] for k in keys], tgts,
-                                           [[split[k][0]] * n for k in keys], deferred=True, keys_per_chunk=keys_per_chunk))
-                   for keys in groups.values()]
-
-        def finish():
-            out = [[self._split_dict((), (None, None)) for _ in range(K)] for _ in range(n)]
-            for keys, p in pending:
-                vals = p()
-                for i in range(n):
-                    for j, k in enumerate(keys):
-                        out[i][k] = self._split_dict(vals[i, j], split[k][1])
-            return out
-        return finish if deferred else finish()
+        (group, to_dict, default), edges = self._split_family(cutoffs_hz)
+        return self._keyed_multi(group, lambda e, t, keys: B.pair_lsd_bands(self._plan(), e, t, [[edges[k]] * n for k in keys], deferred=True,
+                                                                           keys_per_chunk=keys_per_chunk),
+                                 to_dict, default, lambda e, t: self.lsd_split_batch(e, t, list(cutoffs_hz) * n, True, deferred=True),
+                                 ests_by_key, targets, resident, deferred)
 
     # ---- the per-pair metric families (not in the reference): estimate e against target index[e].  A family is two functions -
     # call(tgts, ests, index) queues its backend call and returns the Pending, dicts(rows) names the columns - and the drivers
@@ -326,6 +355,12 @@ class AudioMetrics:
                     out[i] = d
             return out
         return finish if deferred else finish()
+
+    def _multi_flat(self, family, ests_by_key, targets, resident, deferred):
+        """K estimates per target, as evaluation_multi, through _pairs: the K pairs of a target next to each other in one call per
+        dtype group."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        return _regroup(self._pairs(family, ests, tgts, resident, True, by_dtype=True), n, K, deferred)
 
     def _multi_shared(self, family, ests_by_key, targets, resident, deferred):
         """K estimates per target, as evaluation_multi, in ONE call that names each target once for its K estimates."""
@@ -401,8 +436,7 @@ class AudioMetrics:
     def waveform_multi(self, ests_by_key, targets, which="all", resident=False, deferred=False):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  The K pairs of a target sit next to each other in one call: each tile of the target is read once for all of them."""
-        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
-        return _regroup(self.waveform_batch(ests, tgts, which, resident, deferred=True), n, K, deferred)
+        return self._multi_flat(self._wave_family(which), ests_by_key, targets, resident, deferred)
 
     # ---- objective quality measures (DESIGN §12): Loizou's LLR, LPC cepstral distance, WSS and fwSNRseg at self.rate.  WSS and
     # fwSNRseg look at Loizou's 25 critical bands only, 50 Hz to about 3.9 kHz at every rate: they score the band a model was
@@ -451,8 +485,7 @@ class AudioMetrics:
     def quality_multi(self, ests_by_key, targets, which="all", lpc_order=None, resident=False, deferred=False):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  The K pairs of a target sit next to each other in one call: the target's frames are analysed once for all of them."""
-        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
-        return _regroup(self.quality_batch(ests, tgts, which, lpc_order, resident, deferred=True), n, K, deferred)
+        return self._multi_flat(self._quality_family(which, lpc_order), ests_by_key, targets, resident, deferred)
 
     # ---- pitch (DESIGN §13): YIN F0 tracks on 16 kHz float64 signals, 10 ms frames, and the pair statistics F0 RMSE (cents), F0
     # correlation, GPE, VDE and FFE of an estimate's track against its target's
@@ -543,8 +576,7 @@ class AudioMetrics:
     def phase_distance_multi(self, ests_by_key, targets, which="all", n_fft=1024, hop=None, band=None, resident=False, deferred=False):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  The K pairs of a target sit next to each other in one call."""
-        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
-        return _regroup(self.phase_distance_batch(ests, tgts, which, n_fft, hop, band, resident, deferred=True), n, K, deferred)
+        return self._multi_flat(self._phase_family(which, n_fft, hop, band), ests_by_key, targets, resident, deferred)
 
     # ---- multi-resolution STFT distance (DESIGN §18): Parallel WaveGAN's spectral convergence and log-magnitude distance, averaged
     # over several (n_fft, hop, win) - in SAMPLES whatever self.rate is; the defaults are the paper's, chosen at 24 kHz
@@ -591,8 +623,7 @@ class AudioMetrics:
                      deferred=False):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  The K pairs of a target sit next to each other in one call."""
-        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
-        return _regroup(self.mrstft_batch(ests, tgts, resolutions, band, eps, per_resolution, resident, deferred=True), n, K, deferred)
+        return self._multi_flat(self._mrstft_family(resolutions, band, eps, per_resolution), ests_by_key, targets, resident, deferred)
 
     # ---- filter-invariant SDR (DESIGN §19): BSS Eval's SDR, the estimate projected on the target's `taps` causal shifts - a delay or
     # a colouring of up to taps - 1 samples costs nothing, where snr and si_sdr collapse
@@ -628,8 +659,7 @@ class AudioMetrics:
     def bss_sdr_multi(self, ests_by_key, targets, taps=B.BSS_TAPS, return_filter=False, resident=False, deferred=False):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  The K pairs of a target sit next to each other in one call: K + 1 correlations per target, not 2 K."""
-        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
-        return _regroup(self.bss_sdr_batch(ests, tgts, taps, return_filter, resident, deferred=True), n, K, deferred)
+        return self._multi_flat(self._bss_family(taps, return_filter), ests_by_key, targets, resident, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
@@ -678,57 +708,13 @@ class AudioMetrics:
         """{'mel_lsd', 'mel_l1', 'mcd'} (or the subset `which` names) of one (estimate, target) pair."""
         return self.mel_distance_batch([est], [target], which, **mel)[0]
 
-    def _mel_batch(self, run, to_dict, ests, targets, resident, deferred):
-        """A mel pair family on lists of pairs: run(est_lists, tgt_list) -> Pending of [n, K, 3], one call per estimate dtype;
-        to_dict(row) -> the pair's dict."""
-        pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
-        groups = {}
-        for i, (e, _) in enumerate(pairs):
-            groups.setdefault(bool(B._is_f64(e)), []).append(i)
-        pending = [(idx, run([[pairs[i][0] for i in idx]], [pairs[i][1] for i in idx])) for idx in groups.values()]
-
-        def finish():
-            out = [None] * len(pairs)
-            for idx, p in pending:
-                vals = p()
-                for r, i in enumerate(idx):
-                    out[i] = to_dict(vals[r, 0])
-            return out
-        return finish if deferred else finish()
-
-    def _mel_multi(self, run, to_dict, batch, ests_by_key, targets, resident, deferred):
-        """The same for K estimates per target: keys of one estimate dtype share one multi-key launch sequence; lengths that differ
-        between keys, or a key with both dtypes, send the pairs through batch(ests, targets) (deferred, resident)."""
-        K, n = len(ests_by_key), len(targets)
-        pairs = [[self._prepare_pair(ests_by_key[k][i], targets[i], resident) for i in range(n)] for k in range(K)]
-        same_len = all(len({pairs[k][i][0].shape[0] for k in range(K)}) == 1 for i in range(n))
-        kinds = [{bool(B._is_f64(pairs[k][i][0])) for i in range(n)} for k in range(K)]
-        if n == 0 or not same_len or any(len(kd) != 1 for kd in kinds):
-            flat = _item_major(pairs, n, K)
-            return _regroup(batch([e for e, _ in flat], [t for _, t in flat]), n, K, deferred)
-        tgts = [pairs[0][i][1] for i in range(n)]
-        groups = {}
-        for k in range(K):
-            groups.setdefault(next(iter(kinds[k])), []).append(k)
-        pending = [(keys, run([[pairs[k][i][0] for i in range(n)] for k in keys], tgts)) for keys in groups.values()]
-
-        def finish():
-            out = [[None] * K for _ in range(n)]
-            for keys, p in pending:
-                vals = p()
-                for i in range(n):
-                    for j, k in enumerate(keys):
-                        out[i][k] = to_dict(vals[i, j])
-            return out
-        return finish if deferred else finish()
-
     def mel_distance_batch(self, ests, targets, which="all", resident=False, deferred=False, **mel):
         """mel_distance for lists of pairs, with evaluation_batch's input rules (metrics.py:89-90 truncation, float64 estimates kept
         float64; float32 targets): one ssr_pair_mel_metrics call per estimate dtype.  deferred: as evaluation_batch."""
         mask = self._mel_which(which)
         fb, n_cep = self._mel_fb(**mel)
-        return self._mel_batch(lambda e, t: B.pair_mel_metrics(self._plan(), e, t, fb, n_cep, mask, deferred=True),
-                               lambda row: self._mel_dict(row, mask), ests, targets, resident, deferred)
+        return self._keyed_batch(_by_dtype, lambda e, t, idx: B.pair_mel_metrics(self._plan(), e, t, fb, n_cep, mask, deferred=True),
+                                 lambda row, i: self._mel_dict(row, mask), None, ests, targets, resident, deferred)
 
     def mel_distance_multi(self, ests_by_key, targets, which="all", resident=False, deferred=False, keys_per_chunk=None, **mel):
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
@@ -736,10 +722,11 @@ class AudioMetrics:
         lengths that differ between keys, or a key with both dtypes, send the pairs through mel_distance_batch."""
         mask = self._mel_which(which)
         fb, n_cep = self._mel_fb(**mel)
-        return self._mel_multi(lambda e, t: B.pair_mel_metrics(self._plan(), e, t, fb, n_cep, mask, deferred=True, keys_per_chunk=keys_per_chunk),
-                               lambda row: self._mel_dict(row, mask),
-                               lambda e, t: self.mel_distance_batch(e, t, which, True, deferred=True, **mel),
-                               ests_by_key, targets, resident, deferred)
+        return self._keyed_multi(_by_dtype, lambda e, t, keys: B.pair_mel_metrics(self._plan(), e, t, fb, n_cep, mask, deferred=True,
+                                                                                  keys_per_chunk=keys_per_chunk),
+                                 lambda row, k: self._mel_dict(row, mask), None,
+                                 lambda e, t: self.mel_distance_batch(e, t, which, True, deferred=True, **mel),
+                                 ests_by_key, targets, resident, deferred)
 
     def mel_distance_spectrogram(self, est_sp, tgt_sp, which="all", **mel):
         """[B, C, T, F] magnitude tensors x2 (F = n_fft // 2 + 1) -> {name: [B, C] float64 tensor} for the names `which` asks for."""
@@ -774,17 +761,18 @@ class AudioMetrics:
         """mel_dtw for lists of pairs, with mel_distance_batch's input rules.  lengths=False: the dicts carry no dtw_len."""
         radius = self.dtw_radius(radius)
         fb, n_cep = self._mel_fb(**mel)
-        return self._mel_batch(lambda e, t: B.pair_mel_dtw(self._plan(), e, t, fb, n_cep, radius, deferred=True),
-                               lambda row: self._dtw_dict(row, lengths), ests, targets, resident, deferred)
+        return self._keyed_batch(_by_dtype, lambda e, t, idx: B.pair_mel_dtw(self._plan(), e, t, fb, n_cep, radius, deferred=True),
+                                 lambda row, i: self._dtw_dict(row, lengths), None, ests, targets, resident, deferred)
 
     def mel_dtw_multi(self, ests_by_key, targets, radius=16, resident=False, deferred=False, keys_per_chunk=None, lengths=True, **mel):
         """K estimates per target, as mel_distance_multi -> n lists of K dicts."""
         radius = self.dtw_radius(radius)
         fb, n_cep = self._mel_fb(**mel)
-        return self._mel_multi(lambda e, t: B.pair_mel_dtw(self._plan(), e, t, fb, n_cep, radius, deferred=True, keys_per_chunk=keys_per_chunk),
-                               lambda row: self._dtw_dict(row, lengths),
-                               lambda e, t: self.mel_dtw_batch(e, t, radius, True, deferred=True, lengths=lengths, **mel),
-                               ests_by_key, targets, resident, deferred)
+        return self._keyed_multi(_by_dtype, lambda e, t, keys: B.pair_mel_dtw(self._plan(), e, t, fb, n_cep, radius, deferred=True,
+                                                                              keys_per_chunk=keys_per_chunk),
+                                 lambda row, k: self._dtw_dict(row, lengths), None,
+                                 lambda e, t: self.mel_dtw_batch(e, t, radius, True, deferred=True, lengths=lengths, **mel),
+                                 ests_by_key, targets, resident, deferred)
 
     def mel_dtw_spectrogram(self, est_sp, tgt_sp, radius=16, **mel):
         """[B, C, T, F] magnitude tensors x2 (F = n_fft // 2 + 1) -> {'mcd_dtw', 'dtw_dev', 'dtw_len'}: [B, C] float64 tensors."""

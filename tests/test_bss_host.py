@@ -253,17 +253,15 @@ def test_bss_sdr_rejects_bad_arguments_before_launch():
 
 def test_header_ctypes_table_and_library_agree():
     from ssr_eval_amd import _lib
-    strip = lambda s: re.sub(r"/\*.*?\*/", "", s, flags=re.S)      # noqa: E731
-    main = strip(open(os.path.join(ROOT, "include", "ssr_hip.h")).read())
-    part = strip(open(os.path.join(ROOT, "include", "ssr_hip_bss.h")).read())
-    assert '#include "ssr_hip_bss.h"' in main
-    declared = set(re.findall(r"\b(ssr_[a-z_0-9]+)\s*\(", part))
-    assert declared == {"ssr_bss_sdr", "ssr_bss_sdr_workspace_bytes"} == set(_lib.BSS_SIGNATURES)
-    assert not declared & set(_lib.SIGNATURES)
+    inc = os.path.join(ROOT, "include")
+    assert os.listdir(inc) == ["ssr_hip.h"]                         # one header: the family has none of its own
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "ssr_hip.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(ssr_[a-z_0-9]+)\s*\(", header))
     lib = _lib.load()
-    for name in declared:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == _lib.BSS_SIGNATURES[name][1], name
-    assert "#define SSR_BSS_MAX_TAPS 512" in part and _lib.BSS_MAX_TAPS == 512
+    for name in ("ssr_bss_sdr", "ssr_bss_sdr_workspace_bytes"):
+        assert name in declared and name in _lib.SIGNATURES, name
+        assert hasattr(lib, name) and getattr(lib, name).argtypes == _lib.SIGNATURES[name][1], name
+    assert "#define SSR_BSS_MAX_TAPS 512" in header and _lib.BSS_MAX_TAPS == 512
     exported = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert " T ssr_bss_sdr\n" in exported and " T ssr_bss_sdr_workspace_bytes\n" in exported
 
@@ -301,16 +299,16 @@ def test_helper_bss_option_and_metric_order():
                 {"which": "all"}, {"taps": 64, "which": "sdr"}, ("sdr",), [512]):
         with pytest.raises(ValueError):
             mk(bss_sdr=bad)
-    # the orders pinned before this family existed stay; the new keys close every_key_order(), the order a result is listed in
+    # the one registry in queue order, and the one order a result is listed in: this family and its keys close both
     assert E._BSS_KEYS == ("sdr", "sdr_lag")
-    assert [f[0] for f in E._FAMILIES] == ["lsd_split", "stoi", "waveform", "mel", "mel_dtw", "quality", "pitch", "phase"]
-    assert [f[0] for f in E._LATER_FAMILIES] == ["mrstft"] and [f[0] for f in E._NEWER_FAMILIES] == ["bss_sdr"]
+    assert [f[0] for f in E._FAMILIES] == ["lsd_split", "stoi", "waveform", "mel", "mel_dtw", "quality", "pitch", "phase", "mrstft", "bss_sdr"]
     order = E.result_key_order()
-    assert order[-3:] == ("phase_ip", "phase_gd", "phase_iaf") and len(order) == 28
-    assert E.all_key_order() == order + ("mrstft_sc", "mrstft_mag", "mrstft")
-    assert E.every_key_order() == E.all_key_order() + ("sdr", "sdr_lag") and E.every_key_order()[-2:] == ("sdr", "sdr_lag")
-    assert len(set(E.every_key_order())) == len(E.every_key_order())
-    args = E._NEWER_FAMILIES[0][3]
+    assert order == ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi", "estoi", "snr", "si_sdr", "seg_snr", "mel_lsd",
+                     "mel_l1", "mcd", "mcd_dtw", "dtw_dev", "llr", "cep_dist", "wss", "fwseg_snr", "f0_rmse", "f0_corr", "gpe", "vde",
+                     "ffe", "phase_ip", "phase_gd", "phase_iaf", "mrstft_sc", "mrstft_mag", "mrstft", "sdr", "sdr_lag")
+    assert len(order) == 33 and len(set(order)) == len(order)
+    assert order == E._METRIC_KEYS[:4] + tuple(k for f in E._FAMILIES for k in f.keys)      # every row's keys, in row order
+    args = E._FAMILIES[-1].arguments
     assert args(mk(bss_sdr=True), ["k"]) == ((512,), {}) and args(mk(bss_sdr={"taps": 64}), ["k"]) == ((64,), {})
 
 

@@ -1,8 +1,8 @@
 """GPU tests (-m gpu) of the filter-invariant SDR (ssr_bss_sdr): the input list and the geometry shapes of
 tests/test_bss_host.py through the C ABI against the float64 oracle (tests/bss_oracle.py) at the same bars - sdr within 1e-6 dB,
 sdr_lag equal, the filter within 1e-10 of max|c| on the white target -, a 64-pair ragged batch, the exact facts, the multi path
-against single calls bit for bit, guard bands and poison on every device buffer of the call (tests/guarded.py), a 60 s pair, and
-SSR_Eval_Helper(bss_sdr=True) with the bootstrap on a small wav tree.
+against single calls bit for bit, a 60 s pair, and SSR_Eval_Helper(bss_sdr=True) with the bootstrap on a small wav tree.  (Guard
+bands and poison on every device buffer of the call: tests/test_gpu_memory_discipline.py.)
 
 The worst sdr difference seen on the GPU is 5.8e-10 dB."""
 import numpy as np
@@ -10,7 +10,6 @@ import pytest
 import torch
 
 import bss_oracle as O
-import guarded as G
 
 pytestmark = pytest.mark.gpu
 
@@ -167,64 +166,6 @@ def test_multi_is_three_batch_calls():
             assert a["filter"].tobytes() == b["filter"].tobytes(), (i, k)
     deferred = am.bss_sdr_multi(by_key, tgts, taps=64, deferred=True)
     assert [[d["sdr"] for d in row] for row in deferred()] == [[d["sdr"] for d in row] for row in multi]
-
-
-# ---- guard bands and poison: inputs, offsets, out, filt, workspace --------------------------------------------------------------
-def _family_inputs(dtype):
-    rng = np.random.default_rng(7)
-    lens = [1, 2, 700, TILE + 3]
-    tgt = [(0.1 * rng.standard_normal(n)).astype(dtype) for n in lens]
-    idx = list(range(len(lens))) + [len(lens) - 1]                        # two estimates of the last target
-    est = [(tgt[i] + 0.02 * rng.standard_normal(len(tgt[i]))).astype(dtype) for i in idx]
-    return tgt, est, idx
-
-
-@pytest.mark.parametrize("placement", ["odd", "quad"])
-@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
-@pytest.mark.parametrize("with_filter", [True, False], ids=["filt", "null"])
-def test_guard_bands_and_poison(monkeypatch, dtype, placement, with_filter):
-    """The call on separate device tensors, then on views into NaN-filled arenas with `out`, `filt` and the workspace between
-    0xFF guard bands and 0xFF inside: the same bits, no guard damaged, no arena written, everything finite."""
-    from ssr_eval_amd import backend as B
-    gaps = {"odd": G.GAPS_ODD, "quad": G.GAPS_QUAD}[placement]
-    tgt, est, idx = _family_inputs(dtype)
-    for taps in (512, 5):
-        def call(put):
-            return B.bss_sdr(put(tgt), put(est), idx, taps, return_filter=with_filter)
-        plain = G.bits(call(lambda arrays: [torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in arrays]))
-        torch.cuda.synchronize()
-        with monkeypatch.context() as m:
-            g = G.Guarded().route(m)
-            got = call(lambda arrays: g.arena(arrays, gaps, torch.from_numpy(arrays[0]).dtype, DEV)[0])
-            assert len(g.blocks) >= (3 if with_filter else 2), "out, filt and the workspace come from the guarded allocator"
-            assert g.arenas and g.read_in_place(), "an input arena was packed before the library read it"
-            g.check()
-            got = G.bits(got)
-        G.assert_same_bits(plain, got, ("bss", taps))
-        for shape, dt, raw in got:
-            assert np.isfinite(np.frombuffer(raw, np.dtype(dt))).all(), (taps, shape)
-
-
-def test_one_byte_less_than_reported_is_refused(monkeypatch):
-    from ssr_eval_amd import backend as B
-    lib = B._lib.load()
-    real = lib.ssr_bss_sdr_workspace_bytes
-    tgt, est, idx = _family_inputs(np.float32)
-    asked = []
-
-    def one_less(*a):
-        n = int(real(*a))
-        assert n > 0
-        asked.append(n)
-        return n - 1
-    with monkeypatch.context() as m:
-        g = G.Guarded().route(m)
-        m.setattr(lib, "ssr_bss_sdr_workspace_bytes", one_less)
-        with pytest.raises(B.SsrHipError, match=r"libssrhip error -4\b"):
-            B.bss_sdr(tgt, est, idx, 512, return_filter=True)
-        assert asked
-        g.check()
-        assert g.untouched_payloads(("backend.py:put", "backend.py:_uniform_images")) == []
 
 
 def test_a_minute_at_48_khz():

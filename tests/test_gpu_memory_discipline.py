@@ -68,12 +68,12 @@ def pair_of(lens, est_dtype, tgt_dtype, keys=1, seed=0):
     return ests, [t.astype(tgt_dtype) for t in tgt]
 
 
-def twice(monkeypatch, call, gaps, what="", in_place=True):
+def twice(monkeypatch, call, gaps, what="", in_place=True, blocks=1):
     """call(put) twice: put(arrays) hands the arrays over as separate device tensors (an entry point that takes a list packs them),
     then as views into a poisoned arena of their dtype under guarded allocations.  in_place: the product must build its Ragged
     batches on the arenas as they lie (a wrapper that packed them would lose the poison); False only where the entry point takes
-    the tensors' own pointers or where the inputs are not what the case is about.  -> the guarded result, after the guard / arena
-    check and the bit comparison."""
+    the tensors' own pointers or where the inputs are not what the case is about.  blocks: how many buffers of the call, at least,
+    must have come from the guarded allocator.  -> the guarded result, after the guard / arena check and the bit comparison."""
     plain = G.bits(call(lambda arrays: [torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in arrays]))
     torch.cuda.synchronize()
     with monkeypatch.context() as m:
@@ -82,7 +82,7 @@ def twice(monkeypatch, call, gaps, what="", in_place=True):
         def put(arrays):
             return g.arena(arrays, gaps, torch.from_numpy(np.asarray(arrays[0])).dtype, DEV)[0]
         got = call(put)
-        assert g.blocks, "no allocation of the call went through the guarded allocator"
+        assert len(g.blocks) >= blocks, "%d allocation(s) of the call went through the guarded allocator, not %d" % (len(g.blocks), blocks)
         assert not in_place or (g.arenas and g.read_in_place()), "%r: an input arena was packed before the library read it" % (what,)
         g.check()
         got = G.bits(got)
@@ -349,6 +349,32 @@ def test_per_pair_families(monkeypatch, dtype, placement):
     tracks = twice(monkeypatch, lambda put: [list(tr) for tr in bk.f0_track(put(tgt), fs)], gaps, "f0_track", in_place=False)
     for f0, vo, ap, en in zip(*[iter(tracks)] * 4):
         assert np.isfinite(ap).all() and np.isfinite(en).all() and np.isfinite(f0[en > 0]).all()
+
+
+TILE = 16384                                                              # ssr_bss_sdr's tile, in samples
+
+
+def bss_inputs(dtype):
+    rng = np.random.default_rng(7)
+    lens = [1, 2, 700, TILE + 3]
+    tgt = [(0.1 * rng.standard_normal(n)).astype(dtype) for n in lens]
+    idx = list(range(len(lens))) + [len(lens) - 1]                        # two estimates of the last target
+    est = [(tgt[i] + 0.02 * rng.standard_normal(len(tgt[i]))).astype(dtype) for i in idx]
+    return tgt, est, idx
+
+
+@pytest.mark.parametrize("placement", list(PLACEMENTS))
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("with_filter", [True, False], ids=["filt", "null"])
+def test_guard_bands_and_poison(monkeypatch, dtype, placement, with_filter):
+    """ssr_bss_sdr on separate device tensors, then on views into NaN-filled arenas with `out`, `filt` and the workspace between
+    0xFF guard bands and 0xFF inside: the same bits, no guard damaged, no arena written, everything finite."""
+    bk = B()
+    tgt, est, idx = bss_inputs(dtype)
+    for taps in (512, 5):
+        got = twice(monkeypatch, lambda put: bk.bss_sdr(put(tgt), put(est), idx, taps, return_filter=with_filter), PLACEMENTS[placement],
+                    ("bss", taps), blocks=3 if with_filter else 2)            # out, filt and the workspace
+        all_finite(got, ("bss", taps))
 
 
 def twice_direct(monkeypatch, call, groups, gaps, what="", unit=1, lead=None):
@@ -796,8 +822,9 @@ WS_QUERIES = [n for n in SIGNATURES if "_workspace_bytes" in n]
 WRITTEN_OK = ("backend.py:put", "backend.py:_uniform_images", "backend.py:_resample_f64")
 
 
-def refused(monkeypatch, query, call):
-    """call(g) under guarded allocations with `query` reporting one byte less than it should: SSR_ERR_WORKSPACE, nothing enqueued."""
+def refused(monkeypatch, query, call, written_ok=WRITTEN_OK):
+    """call(g) under guarded allocations with `query` reporting one byte less than it should: SSR_ERR_WORKSPACE, nothing enqueued -
+    every payload but those allocated in the functions `written_ok` names still holds only 0xFF."""
     bk = B()
     lib = bk._lib.load()
     real = getattr(lib, query)
@@ -815,7 +842,7 @@ def refused(monkeypatch, query, call):
             call(g)
         assert asked, query
         g.check()
-        assert g.untouched_payloads(WRITTEN_OK) == [], query
+        assert g.untouched_payloads(written_ok) == [], query
 
 
 def _ws_cases():
@@ -840,6 +867,7 @@ def _ws_cases():
     lsig = signals([2000, 3000], np.float32, 22)
     w64 = [x.astype(np.float64) for x in sig]
     re, im = ([torch.zeros((lp.frames(n), lp.n_bins), dtype=torch.float32) for n in (2000, 3000)] for _ in range(2))
+    bt, be, bidx = bss_inputs(np.float32)
     return {
         "ssr_pair_metrics_workspace_bytes_for": [lambda g: bk.pair_metrics(plan, e32[0], t32, M_LSD), lambda g: bk.pair_metrics(plan, e32[0], t32, M_ALL),
                                                  lambda g: bk.pair_metrics(plan3, e64[0], t3, M_ALL),
@@ -857,6 +885,7 @@ def _ws_cases():
         "ssr_pair_mel_dtw_workspace_bytes": lambda g: bk.pair_mel_dtw(plan, e32, t32, fb, 5, 3),
         "ssr_stoi_workspace_bytes": lambda g: bk.stoi(wt, we, idx, 16000),
         "ssr_wave_metrics_workspace_bytes": lambda g: bk.wave_metrics(wt, we, idx, 16000),
+        "ssr_bss_sdr_workspace_bytes": lambda g: bk.bss_sdr(bt, be, bidx, 512, return_filter=True),
         "ssr_quality_metrics_workspace_bytes": lambda g: bk.quality_metrics(wt, we, idx, 16000),
         "ssr_phase_metrics_workspace_bytes": lambda g: bk.phase_metrics(wt, we, idx),
         "ssr_mrstft_workspace_bytes": lambda g: bk.mrstft_metrics(wt, we, idx),
@@ -897,8 +926,10 @@ def test_one_byte_less_than_reported_is_refused(monkeypatch, query):
         return
     cases = _ws_cases()
     assert query in cases, "a *_workspace_bytes query of the header without a refusal case: %s" % query
+    # (nothing is resampled in front of ssr_bss_sdr: its refused call may leave the descriptor uploads written and nothing else)
+    written_ok = WRITTEN_OK[:2] if query == "ssr_bss_sdr_workspace_bytes" else WRITTEN_OK
     for call in (cases[query] if isinstance(cases[query], list) else [cases[query]]):
-        refused(monkeypatch, query, call)
+        refused(monkeypatch, query, call, written_ok)
 
 
 def test_every_workspace_query_of_the_header_has_a_refusal_case():
@@ -937,6 +968,7 @@ COVERAGE = {
     "ssr_pair_mel_dtw_est64": "test_pair_image_families (est64)",
     "ssr_stoi": "test_stoi_and_pitch_read_where_the_signals_lie (inputs), test_per_pair_families (wrapper: outputs, workspace)",
     "ssr_wave_metrics": "test_per_pair_families",
+    "ssr_bss_sdr": "test_guard_bands_and_poison",
     "ssr_quality_metrics": "test_per_pair_families",
     "ssr_phase_metrics": "test_per_pair_families",
     "ssr_mrstft_metrics": "test_per_pair_families",

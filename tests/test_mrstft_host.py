@@ -405,16 +405,15 @@ def test_helper_mrstft_option_and_metric_order():
                 {"band": (3001, 3010)}, {"eps": 0}, {"eps": "x"}, {"eps": float("inf")}):
         with pytest.raises(ValueError):
             mk(mrstft=bad)
-    # the order pinned before this family existed stays; the new keys follow it in all_key_order()
+    # the family is queued behind the eight before it, and its keys follow theirs
     assert E._MRSTFT_KEYS == ("mrstft_sc", "mrstft_mag", "mrstft")
     names = [f[0] for f in E._FAMILIES]
-    assert names == ["lsd_split", "stoi", "waveform", "mel", "mel_dtw", "quality", "pitch", "phase"]
-    assert [f[0] for f in E._LATER_FAMILIES] == ["mrstft"]
+    assert names[:9] == ["lsd_split", "stoi", "waveform", "mel", "mel_dtw", "quality", "pitch", "phase", "mrstft"]
     order = E.result_key_order()
-    assert order == ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi", "estoi", "snr", "si_sdr", "seg_snr", "mel_lsd",
-                     "mel_l1", "mcd", "mcd_dtw", "dtw_dev", "llr", "cep_dist", "wss", "fwseg_snr", "f0_rmse", "f0_corr", "gpe", "vde",
-                     "ffe", "phase_ip", "phase_gd", "phase_iaf")
-    assert E.all_key_order() == order + E._MRSTFT_KEYS and len(set(E.all_key_order())) == len(order) + 3
-    args = E._LATER_FAMILIES[0][3]
+    assert order[:28] == ("lsd", "log_sispec", "sispec", "ssim", "lsd_lf", "lsd_hf", "stoi", "estoi", "snr", "si_sdr", "seg_snr", "mel_lsd",
+                          "mel_l1", "mcd", "mcd_dtw", "dtw_dev", "llr", "cep_dist", "wss", "fwseg_snr", "f0_rmse", "f0_corr", "gpe", "vde",
+                          "ffe", "phase_ip", "phase_gd", "phase_iaf")
+    assert order[28:31] == E._MRSTFT_KEYS and len(set(order)) == len(order)
+    args = E._FAMILIES[8].arguments
     assert args(mk(mrstft=True), ["k"]) == ((None, None, 1e-7), {})
     assert args(mk(mrstft={"band": (0, 8000), "eps": 1e-5}), ["k"]) == ((None, (0, 8000), 1e-5), {})
