@@ -792,6 +792,8 @@ int ssr_comm_init_rank(const void* uid128, int n_ranks, int rank, void** comm);
 int ssr_comm_destroy(void* comm);
 int ssr_allreduce_sums(double* buf, int n, void* comm, void* stream);
 
+#include "../ssr_eval_amd/csrc/ssr_hip_coherence.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,11 @@ SIGNATURES = {
     "ssr_comm_destroy": (_i, [_vp]),
     "ssr_allreduce_sums": (_i, [_vp, _i, _vp, _vp]),
 }
+# name -> (restype, argtypes): exactly the symbols ssr_eval_amd/csrc/ssr_hip_coherence.h declares (include/ssr_hip.h includes it)
+COHERENCE_SIGNATURES = {
+    "ssr_coherence_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i, _i]),
+    "ssr_coherence": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+}
 
 _lib = None
 
@@ -150,7 +155,7 @@ def load():
             "libssrhip.so not found at %s - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  ssr_eval_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -1119,6 +1119,69 @@ def bss_sdr(tgt_list, est_list, tgt_index, taps=BSS_TAPS, return_filter=False, d
         return (rows, Pending(filt)) if deferred else (rows, filt.cpu().numpy())
 
 
+# ---- magnitude-squared coherence: Welch-averaged MSC per bin, and per band its mean, the coherence SDR and the coherent bins ------
+COHERENCE_THRESHOLD = 0.5
+
+
+def check_coherence_frames(n_fft, hop):
+    """(n_fft, hop) as ints (hop None: n_fft // 2), or ValueError: n_fft one of PHASE_N_FFTS, 1 <= hop <= n_fft (the C ABI's own
+    check)."""
+    ints = (int, np.integer)
+    if isinstance(n_fft, bool) or not isinstance(n_fft, ints) or int(n_fft) not in PHASE_N_FFTS:
+        raise ValueError("n_fft must be one of %s" % (PHASE_N_FFTS,))
+    hop = int(n_fft) // 2 if hop is None else hop
+    if isinstance(hop, bool) or not isinstance(hop, ints) or not 1 <= int(hop) <= int(n_fft):
+        raise ValueError("hop must be None (n_fft // 2) or an integer in [1, n_fft]")
+    return int(n_fft), int(hop)
+
+
+def check_coherence_threshold(thr):
+    """thr as a float, or ValueError: a number in (0, 1] (the C ABI's own check)."""
+    if isinstance(thr, bool) or not isinstance(thr, (int, float, np.integer, np.floating)) or not 0.0 < float(thr) <= 1.0:
+        raise ValueError("threshold must be a number in (0, 1]")
+    return float(thr)
+
+
+def coherence_metrics(tgt_list, est_list, tgt_index, n_fft=1024, hop=None, bands=None, thr=COHERENCE_THRESHOLD, return_spectrum=False,
+                      device=None, deferred=False):
+    """Magnitude-squared coherence of estimate e against target tgt_index[e] (ssr_coherence): waveforms (float32 or
+    float64, each estimate as long as its target; a list holding both dtypes is widened to float64) -> [n_est, n_bands, 3] float64,
+    (msc, coh_sdr in dB, coh_bins) per band; return_spectrum: (that, the per-bin coherence [n_est, n_fft // 2 + 1]).  n_fft: 256,
+    512, 1024 or 2048; hop: None = n_fft // 2; bands: None = every bin, a list of up to 8 inclusive (lo, hi) bin pairs for every
+    estimate, or one such list per estimate ([n_est][n_bands][2]); lo > hi is the empty band (NaN), otherwise 0 <= lo <= hi <=
+    n_fft // 2; thr: a bin counts into coh_bins where its coherence is >= thr.  Fewer than two segments: NaN.  Device views of one
+    buffer are read where they lie.  deferred: a function that returns the array (return_spectrum: the pair)."""
+    n_fft, hop = check_coherence_frames(n_fft, hop)
+    thr = check_coherence_threshold(thr)
+    n_e, nb = len(est_list), n_fft // 2 + 1
+    tab = np.asarray([(0, n_fft // 2)] if bands is None else bands)
+    if tab.ndim == 2:
+        tab = np.broadcast_to(tab, (n_e,) + tab.shape)
+    if tab.ndim != 3 or tab.shape[0] != n_e or tab.shape[2] != 2 or not 1 <= tab.shape[1] <= _lib.MAX_BANDS or tab.dtype.kind not in "iu":
+        raise ValueError("bands must be None, 1 to %d integer (lo, hi) pairs, or one such list per estimate" % _lib.MAX_BANDS)
+    if np.any((tab[..., 0] <= tab[..., 1]) & ((tab[..., 0] < 0) | (tab[..., 1] > n_fft // 2))):
+        raise ValueError("bands must be empty (lo > hi) or satisfy 0 <= lo <= hi <= n_fft // 2")
+    tab = np.ascontiguousarray(tab, dtype=np.int32)                  # read by the library when the call is queued
+    B_ = tab.shape[1]
+    lib = _lib.load()
+    spec = None
+    if return_spectrum:
+        dev = torch.device(device) if device is not None else default_device()
+        spec = torch.empty((n_e, nb), dtype=torch.float64, device=dev)
+    sp = _vp(spec)
+
+    def entry(*a):      # the spectrum goes between `out` and the workspace
+        return lib.ssr_coherence(*a[:-3], sp, *a[-3:])
+    rows = _pair_index_metrics(tgt_list, est_list, tgt_index, 3 * B_, _placed_where_they_lie,
+                               lambda *a: lib.ssr_coherence_workspace_bytes(*a, n_fft, hop, B_), entry,
+                               (n_fft, hop, B_, tab.ctypes.data_as(C.c_void_p), thr), device, deferred)
+    shaped = (lambda: rows().reshape(-1, B_, 3)) if deferred else rows.reshape(-1, B_, 3)
+    if not return_spectrum:
+        return shaped
+    with torch.cuda.device(spec.device):
+        return (shaped, Pending(spec)) if deferred else (shaped, spec.cpu().numpy())
+
+
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
 PITCH_FS = 16000                 # the rate every signal is tracked at
 PITCH_HOP = 160

@@ -21,8 +21,8 @@ import torch
 from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
-from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, \
-    _WAVE_NAMES
+from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
+    _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
 
@@ -35,6 +35,7 @@ _STOI_OPTIONS = {"stoi": False, "estoi": True, "both": "both"}
 # result: its mean over files of different lengths says nothing
 _WAVEFORM_KEYS, _MEL_KEYS, _MEL_DTW_KEYS, _QUALITY_KEYS, _PITCH_KEYS = _WAVE_NAMES, _MEL_NAMES, _MEL_DTW_NAMES[:2], _QUALITY_NAMES, _PITCH_NAMES
 _PHASE_KEYS, _MRSTFT_KEYS, _BSS_KEYS = _PHASE_NAMES, _MRSTFT_NAMES, _BSS_NAMES
+_COH_KEYS = _COH_NAMES + _COH_HF_NAMES
 
 
 def _option_dict(value):
@@ -191,6 +192,37 @@ def result_key_order():
     return _METRIC_KEYS[:4] + tuple(k for f in _FAMILIES for k in f.keys)
 
 
+def _coherence_args(h, v, keys):
+    """-> (n_fft, hop, band, one split frequency per degradation key, threshold): the split is `split` Hz for every key where the
+    option names one, else the key's own cutoff (key_cutoff_hz; None for mp3 keys - NaN values)."""
+    q = v if isinstance(v, dict) else {}
+    split = [float(q["split"])] * len(keys) if "split" in q else [key_cutoff_hz(k) for k in keys]
+    return q.get("n_fft", 1024), q.get("hop"), q.get("band"), split, q.get("threshold", B.COHERENCE_THRESHOLD)
+
+
+def _coherence_check(h, v):
+    if v is not True:
+        if not isinstance(v, dict) or not v or set(v) - {"n_fft", "hop", "band", "threshold", "split"}:
+            raise ValueError("coherence must be None, True or a dict of 'n_fft', 'hop', 'band', 'threshold' and / or 'split'")
+        if "split" in v and v["split"] is None:
+            raise ValueError("split must be a frequency in Hz (leave it out to split every key at its own cutoff)")
+        n_fft, hop, band, split, thr = _coherence_args(h, {k: o for k, o in v.items() if k != "split"}, ["k"])
+        B.check_coherence_threshold(thr)
+        h.audio_metrics._coh_bands(B.check_coherence_frames(n_fft, hop)[0], band, v.get("split"), 1)
+
+
+# The families added after the registry above was pinned by its tests: queued after _FAMILIES, their keys behind its keys.
+_LATER_FAMILIES = (
+    _Family("coherence", "coherence_multi", "coherence_batch", _COH_KEYS, _coherence_check,
+            lambda h, keys: (_coherence_args(h, h.coherence, keys), {}), True),
+)
+
+
+def all_key_order():
+    """result_key_order() and the keys of the later families behind it: the order a result lists its metrics in."""
+    return result_key_order() + tuple(k for f in _LATER_FAMILIES for k in f.keys)
+
+
 def key_cutoff_hz(key):
     """Cutoff in Hz of a degradation key: the integer after the tag, floor-divided by 2 - what preprocess passed to lowpass()
     (proc_bw_8000_4_44100 -> 4000, proc_fft_44099_44100 -> 22049: the sr - 1 quirk).  proc_mp3_* carries none: None."""
@@ -266,7 +298,8 @@ class SSR_Eval_Helper:
                  test_data_root="./datasets/vctk_test", setting_lowpass_filtering=None, setting_subsampling=None,
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
-                 quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None):
+                 quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None,
+                 coherence=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -300,6 +333,13 @@ class SSR_Eval_Helper:
         512-tap FIR filter of the target as the allowed distortion - a delay or a colouring of the output costs nothing - and the
         tap of that filter's largest coefficient, the output's latency in samples (AudioMetrics.bss_sdr_multi / bss_sdr_batch at
         evaluation_sr); a dict = `taps` (1 .. 512).
+        coherence (not in the reference): None = off; True = every key also gets msc / coh_sdr / coh_bw, the mean Welch-averaged
+        magnitude-squared coherence of the output with the target, the power of the output that is a linear function of the target
+        over the power that is not, in dB, and the width in Hz of the bins with a coherence of at least 0.5 - and msc_hf /
+        coh_sdr_hf, the first two above the key's own cutoff (key_cutoff_hz; mp3 keys: NaN) (AudioMetrics.coherence_multi /
+        coherence_batch at evaluation_sr); a dict = `n_fft` (256, 512, 1024 or 2048; default 1024), `hop`
+        (default n_fft // 2), `band` ((lo_hz, hi_hz), the band scored), `threshold` (of coh_bw, in (0, 1]) and / or `split` (the
+        same split frequency in Hz for every key, mp3 included).
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -315,8 +355,8 @@ class SSR_Eval_Helper:
         self.audio_metrics = AudioMetrics(self.evaluationset_sr, precision=precision, device=device)
         # every family option is checked here, before the caller's settings are touched (the mel checks need audio_metrics)
         options = dict(lsd_split=lsd_split, stoi=stoi, waveform=waveform, mel=mel, mel_dtw=mel_dtw, quality=quality, pitch=pitch,
-                       phase=phase, mrstft=mrstft, bss_sdr=bss_sdr)
-        for f in _FAMILIES:
+                       phase=phase, mrstft=mrstft, bss_sdr=bss_sdr, coherence=coherence)
+        for f in _FAMILIES + _LATER_FAMILIES:
             if options[f.option] is not None:
                 f.check(self, options[f.option])
             setattr(self, f.option, options[f.option])
@@ -620,12 +660,12 @@ class SSR_Eval_Helper:
                 values = self.audio_metrics.evaluation_multi(by_key, [all_tgt[i * K] for i in range(len(items))], resident=True, deferred=True)
             else:
                 values = self.audio_metrics.evaluation_batch(all_proc, all_tgt, resident=True, deferred=True)
-        # the optional families, queued behind the four metrics in the same deferred batch, in _FAMILIES' order; the multi path
+        # the optional families, queued behind the four metrics in the same deferred batch, in the registries' order; the multi path
         # analyses each target once for its K estimates
         queued = []
         if all_proc:
             same_keys = multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items)))
-            for f in _FAMILIES:
+            for f in _FAMILIES + _LATER_FAMILIES:
                 if getattr(self, f.option) is None:
                     continue
                 if multi and (same_keys or not f.per_key):
@@ -795,7 +835,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = result_key_order()
+        order_keys = all_key_order()
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

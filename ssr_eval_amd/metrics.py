@@ -31,6 +31,8 @@ _PITCH_NAMES = ("f0_rmse", "f0_corr", "gpe", "vde", "ffe")  # SSR_PITCH_F0_RMSE,
 _PHASE_NAMES = ("phase_ip", "phase_gd", "phase_iaf")       # SSR_PHASE_IP, SSR_PHASE_GD, SSR_PHASE_IAF: bits 0, 1, 2
 _MRSTFT_NAMES = ("mrstft_sc", "mrstft_mag", "mrstft")     # the means over the resolutions of ssr_mrstft_metrics, and their sum
 _BSS_NAMES = ("sdr", "sdr_lag")                           # the columns of ssr_bss_sdr
+_COH_NAMES = ("msc", "coh_sdr", "coh_bw")                 # a band's columns of ssr_coherence (coh_bw: coh_bins in Hz)
+_COH_HF_NAMES = ("msc_hf", "coh_sdr_hf")                  # the same above a split frequency
 
 
 def which_mask(which, names):
@@ -334,10 +336,11 @@ class AudioMetrics:
     # ---- the per-pair metric families (not in the reference): estimate e against target index[e].  A family is two functions -
     # call(tgts, ests, index) queues its backend call and returns the Pending, dicts(rows) names the columns - and the drivers
     # below are the same for all of them
-    def _pairs(self, family, ests, targets, resident, deferred, by_dtype):
+    def _pairs(self, family, ests, targets, resident, deferred, by_dtype, per_pair=False):
         """Lists of pairs with evaluation_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals).  by_dtype:
         one call per (target dtype, estimate dtype) group - the family reads the signals in their own dtype; otherwise one call
-        (it widens them itself).  A target object passed for several pairs of a call appears once in it."""
+        (it widens them itself).  A target object passed for several pairs of a call appears once in it.  per_pair: the family's
+        arguments hold one value per pair - call() also gets the positions of its pairs in the lists."""
         call, dicts = family
         pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
         groups = {}
@@ -346,7 +349,7 @@ class AudioMetrics:
         pending = []
         for idx in groups.values():
             tgts, index = _shared_targets([pairs[i][1] for i in idx])
-            pending.append((idx, call(tgts, [pairs[i][0] for i in idx], index)))
+            pending.append((idx, call(tgts, [pairs[i][0] for i in idx], index, *((idx,) if per_pair else ()))))
 
         def finish():
             out = [None] * len(pairs)
@@ -660,6 +663,90 @@ class AudioMetrics:
         """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
         dicts.  The K pairs of a target sit next to each other in one call: K + 1 correlations per target, not 2 K."""
         return self._multi_flat(self._bss_family(taps, return_filter), ests_by_key, targets, resident, deferred)
+
+    # ---- magnitude-squared coherence (DESIGN §20): is the estimate's band a linear function of the target's, or texture unrelated
+    # to it?  Welch-averaged MSC per bin on n_fft-point periodic-Hann segments of the signals at self.rate (no padding); per band
+    # its mean (msc), the coherence SDR in dB (coh_sdr) and the width of the coherent bins in Hz (coh_bw)
+    def _coh_bands(self, n_fft, band, split, n):
+        """The (lo, hi) bin pairs of n pairs: the band by _phase_bins' rule (None: every bin) and, with a split, the band from bin
+        ceil(split n_fft / rate) to the band's hi.  split: None, one frequency in Hz for every pair, or a list of one per pair
+        (None: no split for that pair - the empty band, NaN).  A split above the band leaves the empty band too."""
+        lo, hi = self._phase_bins(self.rate, n_fft, band) or (0, n_fft // 2)
+        if split is None:
+            return [[(lo, hi)]] * n
+        per_pair = isinstance(split, list)
+        splits = split if per_pair else [split] * n
+        if len(splits) != n:
+            raise ValueError("one split frequency per pair")
+        rows = []
+        for s in splits:
+            if s is None and per_pair:
+                rows.append([(lo, hi), (1, 0)])
+                continue
+            if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= float(s) < math.inf:
+                raise ValueError("a split frequency is a finite number >= 0 in Hz")
+            k = math.ceil(fractions.Fraction(float(s)) * n_fft / fractions.Fraction(float(self.rate)))
+            rows.append([(lo, hi), (k, hi) if k <= hi else (1, 0)])
+        return rows
+
+    def _coh_dicts(self, n_fft, split, spectrum):
+        """(rows [n, n_bands, 3], spectra [n, n_fft / 2 + 1] or None) -> one dict per pair."""
+        hz = float(self.rate) / n_fft
+
+        def dicts(vals):
+            rows, spec = vals
+            out = []
+            for i, r in enumerate(rows):
+                d = {"msc": float(r[0, 0]), "coh_sdr": float(r[0, 1]), "coh_bw": float(r[0, 2]) * hz}
+                if split:
+                    d.update({"msc_hf": float(r[1, 0]), "coh_sdr_hf": float(r[1, 1])})
+                if spectrum:
+                    d["msc_spectrum"] = np.array(spec[i])
+                out.append(d)
+            return out
+        return dicts
+
+    def _coh_family(self, n_fft, hop, band, split, threshold, spectrum, n):
+        n_fft, hop = B.check_coherence_frames(n_fft, hop)
+        thr = B.check_coherence_threshold(threshold)
+        bands = self._coh_bands(n_fft, band, split, n)
+
+        def call(tgts, ests, index, idx):
+            got = B.coherence_metrics(tgts, ests, index, n_fft, hop, [bands[i] for i in idx], thr, spectrum, self._device, deferred=True)
+            return (lambda: (got[0](), got[1]())) if spectrum else (lambda: (got(), None))
+        return call, self._coh_dicts(n_fft, split is not None, spectrum)
+
+    def coherence(self, est, target, n_fft=1024, hop=None, band=None, split_hz=None, threshold=0.5, return_spectrum=False):
+        """{'msc', 'coh_sdr', 'coh_bw'} of one (estimate, target) pair on `band`: the mean magnitude-squared coherence, the power of
+        the estimate that is a linear function of the target over the power that is not, in dB, and the width in Hz of the bins whose
+        coherence is >= threshold.  Invariant to any linear filtering of the estimate.  n_fft: 256, 512, 1024 or 2048; hop: None =
+        n_fft // 2; band: None = every bin, or (lo_hz, hi_hz), mapped to bins as phase_distance maps it; split_hz: also 'msc_hf' and
+        'coh_sdr_hf', on the bins from ceil(split_hz n_fft / rate) to the band's upper edge (NaN where that leaves none);
+        return_spectrum: also 'msc_spectrum', the float64 [n_fft // 2 + 1] coherence per bin.  Fewer than two segments (n < n_fft +
+        hop): NaN.  For unrelated signals the estimator's mean is about 1 / K at K segments, not 0."""
+        return self.coherence_batch([est], [target], n_fft, hop, band, split_hz, threshold, return_spectrum)[0]
+
+    def coherence_batch(self, ests, targets, n_fft=1024, hop=None, band=None, split_hz=None, threshold=0.5, return_spectrum=False,
+                        resident=False, deferred=False):
+        """coherence() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals,
+        read in their own dtype: one ssr_coherence call per (target dtype, estimate dtype) group).  split_hz: None, one frequency for
+        every pair, or a list of one per pair (None: that pair's two _hf values are NaN).  deferred: as evaluation_batch."""
+        n = min(len(ests), len(targets))
+        return self._pairs(self._coh_family(n_fft, hop, band, split_hz, threshold, return_spectrum, n), ests, targets, resident, deferred,
+                           by_dtype=True, per_pair=True)
+
+    def coherence_multi(self, ests_by_key, targets, n_fft=1024, hop=None, band=None, split_hz=None, threshold=0.5, return_spectrum=False,
+                        resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
+        to each other in one call."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        if isinstance(split_hz, list):
+            if len(split_hz) != K:
+                raise ValueError("one split frequency per key")
+            split_hz = list(split_hz) * n
+        family = self._coh_family(n_fft, hop, band, split_hz, threshold, return_spectrum, n * K)
+        return _regroup(self._pairs(family, ests, tgts, resident, True, by_dtype=True, per_pair=True), n, K, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
