@@ -793,6 +793,7 @@ int ssr_comm_destroy(void* comm);
 int ssr_allreduce_sums(double* buf, int n, void* comm, void* stream);
 
 #include "../ssr_eval_amd/csrc/ssr_hip_coherence.h"
+#include "../ssr_eval_amd/csrc/ssr_hip_loudness.h"
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,11 @@ COHERENCE_SIGNATURES = {
     "ssr_coherence_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i, _i]),
     "ssr_coherence": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _sz, _vp]),
 }
+# name -> (restype, argtypes): exactly the symbols ssr_eval_amd/csrc/ssr_hip_loudness.h declares (include/ssr_hip.h includes it)
+LOUDNESS_SIGNATURES = {
+    "ssr_loudness_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "ssr_loudness": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
 
 _lib = None
 
@@ -155,7 +160,7 @@ def load():
             "libssrhip.so not found at %s - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  ssr_eval_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(LOUDNESS_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -1182,6 +1182,70 @@ def coherence_metrics(tgt_list, est_list, tgt_index, n_fft=1024, hop=None, bands
         return (shaped, Pending(spec)) if deferred else (shaped, spec.cpu().numpy())
 
 
+# ---- loudness: BS.1770-4 integrated loudness, momentary / short-term maxima, loudness range, sample and true peak of ONE signal ----
+LOUDNESS_RATES = (8000, 192000)          # SSR_LOUD_MIN_RATE, SSR_LOUD_MAX_RATE
+LOUDNESS_MAX_SUB_BLOCKS = 6144           # SSR_LOUD_MAX_SUB: sub-blocks of 100 ms per signal
+LOUDNESS_COLUMNS = 6
+
+
+def check_loudness_rate(rate):
+    """rate as an int, or ValueError: a whole number of Hz in LOUDNESS_RATES (the C ABI's own check)."""
+    ok = not isinstance(rate, bool) and isinstance(rate, (int, float, np.integer, np.floating)) and float(rate) == int(rate)
+    if not ok or not LOUDNESS_RATES[0] <= int(rate) <= LOUDNESS_RATES[1]:
+        raise ValueError("the loudness family needs an integer rate in [%d, %d] Hz" % LOUDNESS_RATES)
+    return int(rate)
+
+
+def loudness_sub_len(rate):
+    """Samples per 100 ms sub-block at `rate`: round(rate / 10), halves up."""
+    return (int(rate) + 5) // 10
+
+
+def loudness_metrics(sig_list, rate, return_blocks=False, device=None, deferred=False):
+    """The six EBU R128 meter quantities of every signal (ssr_loudness): waveforms (float32 or float64; a list holding
+    both dtypes is widened to float64) at the integer `rate` -> [n, 6] float64, columns lufs, lra, lufs_m_max, lufs_s_max,
+    peak_db, true_peak_db (NaN where a block set is empty; both peaks NaN for digital silence).  return_blocks: (that, a list of
+    n float64 arrays, the K-weighted energies E[s] of the signals' 100 ms sub-blocks).  Device views of one buffer are read where
+    they lie.  A signal of more than LOUDNESS_MAX_SUB_BLOCKS sub-blocks is refused.  deferred: a function that returns the array
+    (return_blocks: the pair)."""
+    rate = check_loudness_rate(rate)
+    sigs = list(sig_list)
+    n = len(sigs)
+    require_gpu()
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else default_device()
+    with torch.cuda.device(dev):
+        out = torch.empty((n, LOUDNESS_COLUMNS), dtype=torch.float64, device=dev)
+        blocks, counts = None, None
+        if n:
+            f64 = any(_is_f64(w) for w in sigs)
+            data, off, lens = _ragged_where_they_lie(sigs, dev, torch.float64 if f64 else torch.float32)
+            counts = lens // loudness_sub_len(rate)
+            if counts.max() > LOUDNESS_MAX_SUB_BLOCKS:
+                raise ValueError("a signal may hold at most %d sub-blocks of 100 ms" % LOUDNESS_MAX_SUB_BLOCKS)
+            lens32 = lens.astype(np.int32)
+            ws_bytes = int(lib.ssr_loudness_workspace_bytes(lens32.ctypes.data_as(C.c_void_p), n, rate))
+            ws = _workspace(ws_bytes, dev)
+            lens_h = _host_i32(lens32, dev)
+            boff = None
+            if return_blocks:
+                boff = np.ascontiguousarray(_offsets(counts), dtype=np.int64)            # read by the library when the call is queued
+                blocks = torch.empty(int(counts.sum()), dtype=torch.float64, device=dev)
+            _lib.check(lib.ssr_loudness(_vp(data), int(f64), _vp(off), _vp(lens_h), n, rate, _vp(out),
+                                        boff.ctypes.data_as(C.c_void_p) if return_blocks else None, _vp(blocks), _vp(ws), ws_bytes,
+                                        _stream()))
+        rows = Pending(out) if deferred else out.cpu().numpy()
+        if not return_blocks:
+            return rows
+        if blocks is None or blocks.numel() == 0:
+            empty = [np.empty(0) for _ in range(n)]
+            return (rows, (lambda: empty)) if deferred else (rows, empty)
+        edges = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+        split = lambda flat: [np.array(flat[edges[i]:edges[i + 1]]) for i in range(n)]      # noqa: E731
+        flat = Pending(blocks) if deferred else blocks.cpu().numpy()
+        return (rows, (lambda: split(flat()))) if deferred else (rows, split(flat))
+
+
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
 PITCH_FS = 16000                 # the rate every signal is tracked at
 PITCH_HOP = 160

@@ -21,7 +21,7 @@ import torch
 from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
-from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
+from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _LOUD_DIFF_NAMES, _LOUD_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
     _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
@@ -36,6 +36,8 @@ _STOI_OPTIONS = {"stoi": False, "estoi": True, "both": "both"}
 _WAVEFORM_KEYS, _MEL_KEYS, _MEL_DTW_KEYS, _QUALITY_KEYS, _PITCH_KEYS = _WAVE_NAMES, _MEL_NAMES, _MEL_DTW_NAMES[:2], _QUALITY_NAMES, _PITCH_NAMES
 _PHASE_KEYS, _MRSTFT_KEYS, _BSS_KEYS = _PHASE_NAMES, _MRSTFT_NAMES, _BSS_NAMES
 _COH_KEYS = _COH_NAMES + _COH_HF_NAMES
+# the loudness range stays out of a key's result: it is NaN for files under 3 s and the aggregate is a plain mean
+_LOUD_KEYS = (_LOUD_NAMES[0], _LOUD_DIFF_NAMES[0], _LOUD_NAMES[5], _LOUD_DIFF_NAMES[2])
 
 
 def _option_dict(value):
@@ -219,8 +221,25 @@ _LATER_FAMILIES = (
 
 
 def all_key_order():
-    """result_key_order() and the keys of the later families behind it: the order a result lists its metrics in."""
+    """result_key_order() and the keys of the later families behind it (full_key_order() adds the tail families')."""
     return result_key_order() + tuple(k for f in _LATER_FAMILIES for k in f.keys)
+
+
+def _loudness_check(h, v):
+    if v is not True:
+        raise ValueError("loudness must be None or True")
+    B.check_loudness_rate(h.evaluationset_sr)
+
+
+# The open end of the registry: a new family appends HERE (queued after the two tuples above, its keys behind theirs).
+_TAIL_FAMILIES = (
+    _Family("loudness", "loudness_multi", "loudness_batch", _LOUD_KEYS, _loudness_check, lambda h, keys: ((), {"names": _LOUD_KEYS}), False),
+)
+
+
+def full_key_order():
+    """all_key_order() and the keys of the tail families behind it: the order a result lists its metrics in."""
+    return all_key_order() + tuple(k for f in _TAIL_FAMILIES for k in f.keys)
 
 
 def key_cutoff_hz(key):
@@ -299,7 +318,7 @@ class SSR_Eval_Helper:
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
                  quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None,
-                 coherence=None):
+                 coherence=None, loudness=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -340,6 +359,11 @@ class SSR_Eval_Helper:
         coherence_batch at evaluation_sr); a dict = `n_fft` (256, 512, 1024 or 2048; default 1024), `hop`
         (default n_fft // 2), `band` ((lo_hz, hi_hz), the band scored), `threshold` (of coh_bw, in (0, 1]) and / or `split` (the
         same split frequency in Hz for every key, mp3 included).
+        loudness (not in the reference): None = off; True = every key also gets lufs / true_peak_db, the gated integrated loudness
+        (ITU-R BS.1770-4) in LUFS and the 4x oversampled peak in dBTP of the output, and lufs_diff / true_peak_diff, those minus the
+        target's - a testee that rescales or clips its output shows here, whatever the level-sensitive keys say
+        (AudioMetrics.loudness_multi / loudness_batch at evaluation_sr, an integer in 8000 .. 192000 Hz).  A
+        file shorter than 400 ms, or below -70 LUFS throughout, has NaN for lufs and lufs_diff.
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -355,8 +379,8 @@ class SSR_Eval_Helper:
         self.audio_metrics = AudioMetrics(self.evaluationset_sr, precision=precision, device=device)
         # every family option is checked here, before the caller's settings are touched (the mel checks need audio_metrics)
         options = dict(lsd_split=lsd_split, stoi=stoi, waveform=waveform, mel=mel, mel_dtw=mel_dtw, quality=quality, pitch=pitch,
-                       phase=phase, mrstft=mrstft, bss_sdr=bss_sdr, coherence=coherence)
-        for f in _FAMILIES + _LATER_FAMILIES:
+                       phase=phase, mrstft=mrstft, bss_sdr=bss_sdr, coherence=coherence, loudness=loudness)
+        for f in _FAMILIES + _LATER_FAMILIES + _TAIL_FAMILIES:
             if options[f.option] is not None:
                 f.check(self, options[f.option])
             setattr(self, f.option, options[f.option])
@@ -665,7 +689,7 @@ class SSR_Eval_Helper:
         queued = []
         if all_proc:
             same_keys = multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items)))
-            for f in _FAMILIES + _LATER_FAMILIES:
+            for f in _FAMILIES + _LATER_FAMILIES + _TAIL_FAMILIES:
                 if getattr(self, f.option) is None:
                     continue
                 if multi and (same_keys or not f.per_key):
@@ -835,7 +859,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = all_key_order()
+        order_keys = full_key_order()
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

@@ -33,6 +33,8 @@ _MRSTFT_NAMES = ("mrstft_sc", "mrstft_mag", "mrstft")     # the means over the r
 _BSS_NAMES = ("sdr", "sdr_lag")                           # the columns of ssr_bss_sdr
 _COH_NAMES = ("msc", "coh_sdr", "coh_bw")                 # a band's columns of ssr_coherence (coh_bw: coh_bins in Hz)
 _COH_HF_NAMES = ("msc_hf", "coh_sdr_hf")                  # the same above a split frequency
+_LOUD_NAMES = ("lufs", "lra", "lufs_m_max", "lufs_s_max", "peak_db", "true_peak_db")     # the columns of ssr_loudness
+_LOUD_DIFF_NAMES = ("lufs_diff", "lra_diff", "true_peak_diff")                           # estimate minus target
 
 
 def which_mask(which, names):
@@ -747,6 +749,89 @@ class AudioMetrics:
             split_hz = list(split_hz) * n
         family = self._coh_family(n_fft, hop, band, split_hz, threshold, return_spectrum, n * K)
         return _regroup(self._pairs(family, ests, tgts, resident, True, by_dtype=True, per_pair=True), n, K, deferred)
+
+    # ---- loudness: the EBU R128 meter quantities of ONE signal at self.rate - BS.1770-4 integrated loudness with gating,
+    # the largest momentary and short-term loudness, the loudness range, the sample peak and the 4x oversampled peak - and, with a
+    # target, the estimate's values minus the target's: is a difference between two testees content, or gain and clipping?
+    @staticmethod
+    def _loudness_names(names, with_target):
+        """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
+        allowed = _LOUD_NAMES + (_LOUD_DIFF_NAMES if with_target else ())
+        if names is None:
+            return allowed
+        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(k, str) and k in allowed for k in names):
+            raise ValueError("names must be None or a tuple of %s" % (allowed,))
+        return tuple(k for k in allowed if k in names)
+
+    def _loudness_signal(self, wav):
+        if isinstance(wav, str):
+            from .io import load_audio
+            wav = load_audio(wav, self.rate)
+        if len(wav.shape) != 1:
+            raise ValueError("expected a 1-D signal, got shape %s" % (tuple(wav.shape),))
+        return wav
+
+    def loudness(self, est, target=None, return_blocks=False):
+        """{'lufs', 'lra', 'lufs_m_max', 'lufs_s_max', 'peak_db', 'true_peak_db'} of one signal at self.rate (an integer in 8000 ..
+        192000 Hz; mono, channel weight 1): the gated integrated loudness of ITU-R BS.1770-4 in LUFS, the loudness range of EBU Tech
+        3342 in LU, the largest momentary (400 ms) and short-term (3 s) loudness, the sample peak in dBFS and the 4x oversampled
+        peak in dBTP.  With a target also 'lufs_diff', 'lra_diff' and 'true_peak_diff', the estimate's value minus the target's.
+        return_blocks: also 'blocks' (and 'target_blocks'), the K-weighted energies of the 100 ms sub-blocks.  A value whose block
+        set is empty - shorter than 400 ms / 3 s, or nothing above -70 LUFS - is NaN, and so are both peaks of digital silence."""
+        return self.loudness_batch([est], None if target is None else [target], return_blocks)[0]
+
+    def loudness_batch(self, ests, targets=None, return_blocks=False, names=None, resident=False, deferred=False):
+        """loudness() for lists of signals or, with targets, of pairs (waveform_batch's input rules: metrics.py:89-90 truncation;
+        float32 or float64 signals, read in their own dtype: one ssr_loudness call per dtype).  A target object passed for several
+        pairs is measured once.  names: None, or the result keys wanted.  deferred: as evaluation_batch."""
+        rate = B.check_loudness_rate(self.rate)
+        if not isinstance(return_blocks, bool):
+            raise ValueError("return_blocks must be True or False")
+        with_t = targets is not None
+        keys = self._loudness_names(names, with_t)
+        if with_t:
+            pairs = [self._prepare_pair(e, t, resident) for e, t in zip(ests, targets)]
+            sigs = [self._loudness_signal(e) for e, _ in pairs]
+            tgts, index = _shared_targets([self._loudness_signal(t) for _, t in pairs])
+        else:
+            sigs, tgts, index = [self._loudness_signal(e) for e in ests], [], []
+        n_e = len(sigs)
+        every = sigs + tgts
+        groups = {}
+        for i, w in enumerate(every):
+            groups.setdefault(bool(B._is_f64(w)), []).append(i)
+        pending = [(idx, B.loudness_metrics([every[i] for i in idx], rate, return_blocks, self._device, deferred=True))
+                   for idx in groups.values()]
+
+        def finish():
+            rows, blocks = np.empty((len(every), len(_LOUD_NAMES))), [None] * len(every)
+            for idx, p in pending:
+                got = p if return_blocks else (p, None)
+                vals, blk = got[0](), (got[1]() if return_blocks else None)
+                for j, i in enumerate(idx):
+                    rows[i] = vals[j]
+                    if return_blocks:
+                        blocks[i] = blk[j]
+            out = []
+            for j in range(n_e):
+                d = dict(zip(_LOUD_NAMES, (float(v) for v in rows[j])))
+                if with_t:
+                    t = rows[n_e + index[j]]
+                    d.update(lufs_diff=float(rows[j][0] - t[0]), lra_diff=float(rows[j][1] - t[1]), true_peak_diff=float(rows[j][5] - t[5]))
+                d = {k: d[k] for k in keys}
+                if return_blocks:
+                    d["blocks"] = blocks[j]
+                    if with_t:
+                        d["target_blocks"] = blocks[n_e + index[j]]
+                out.append(d)
+            return out
+        return finish if deferred else finish()
+
+    def loudness_multi(self, ests_by_key, targets, return_blocks=False, names=None, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  Each target is measured once for its K estimates."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        return _regroup(self.loudness_batch(ests, tgts, return_blocks, names, resident, True), n, K, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
