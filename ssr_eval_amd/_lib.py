@@ -27,6 +27,7 @@ PHASE_IP, PHASE_GD, PHASE_IAF = 1, 2, 4                                         
 MRSTFT_MAX_RES = 8                                                              # SSR_MRSTFT_MAX_RES
 BSS_MAX_TAPS = 512                                                              # SSR_BSS_MAX_TAPS
 BOOTSTRAP_UTTERANCE, BOOTSTRAP_SPEAKER, BOOTSTRAP_MAX_Q = 0, 1, 8                # SSR_BOOTSTRAP_*
+SPECTRUM_MAX_BANDS = 40                                                         # SSR_SPECTRUM_MAX_BANDS
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -142,6 +143,12 @@ LOUDNESS_SIGNATURES = {
     "ssr_loudness_workspace_bytes": (_sz, [_vp, _i, _i]),
     "ssr_loudness": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
+# name -> (restype, argtypes): exactly the symbols ssr_eval_amd/csrc/ssr_hip_spectrum.h declares (include/ssr_hip.h includes it)
+SPECTRUM_SIGNATURES = {
+    "ssr_spectrum_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i, _i]),
+    "ssr_spectrum": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp,
+                          _vp, _sz, _vp]),
+}
 
 _lib = None
 
@@ -160,7 +167,8 @@ def load():
             "libssrhip.so not found at %s - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  ssr_eval_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(LOUDNESS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(LOUDNESS_SIGNATURES.items()) + \
+            list(SPECTRUM_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

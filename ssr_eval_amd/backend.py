@@ -1246,6 +1246,89 @@ def loudness_metrics(sig_list, rate, return_blocks=False, device=None, deferred=
         return (rows, (lambda: split(flat()))) if deferred else (rows, split(flat))
 
 
+# ---- spectrum: rolloff bandwidth, spectral edge, centroid, HF level and LTAS distance from the long-term average spectrum -----------
+SPECTRUM_ROLLOFF = 0.97                  # the reference's BasicTestee._find_cutoff threshold
+SPECTRUM_DROP_DB = 60.0
+SPECTRUM_MAX_BANDS = _lib.SPECTRUM_MAX_BANDS
+SPECTRUM_SIG_COLUMNS, SPECTRUM_PAIR_COLUMNS = 3, 8      # SSR_SPECTRUM_SIG_COLS, SSR_SPECTRUM_PAIR_COLS
+
+
+def check_spectrum_rolloff(rho):
+    """rho as a float, or ValueError: a number in (0, 1) (the C ABI's own check)."""
+    if isinstance(rho, bool) or not isinstance(rho, (int, float, np.integer, np.floating)) or not 0.0 < float(rho) < 1.0:
+        raise ValueError("rolloff must be a number in (0, 1)")
+    return float(rho)
+
+
+def check_spectrum_drop(drop_db):
+    """drop_db as a float, or ValueError: a number in (0, 150] (the C ABI's own check)."""
+    if isinstance(drop_db, bool) or not isinstance(drop_db, (int, float, np.integer, np.floating)) or not 0.0 < float(drop_db) <= 150.0:
+        raise ValueError("drop_db must be a number in (0, 150]")
+    return float(drop_db)
+
+
+def spectrum_metrics(tgt_list, est_list, tgt_index, n_fft=2048, hop=None, band_bins=None, rolloff=SPECTRUM_ROLLOFF,
+                     drop_db=SPECTRUM_DROP_DB, bands=None, split_bins=None, return_ltas=False, device=None, deferred=False):
+    """The spectrum family (ssr_spectrum) on the signals tgt_list + est_list, estimate e belonging to target tgt_index[e]
+    and as long as it (float32 or float64 waveforms; a list holding both dtypes is widened to float64) -> (sig [n_tgt + n_est, 3]
+    float64: rolloff bin, edge bin, centroid in bins; pair [n_est, 8] float64: hf_db of the estimate and of the target, the rolloff /
+    edge / centroid differences in bins, hf_diff, ltas_dist, ltas_max); return_ltas: also c P / K per bin, [n_tgt + n_est,
+    n_fft // 2 + 1].  est_list = [] measures the targets alone.  n_fft: 256, 512, 1024 or 2048; hop: None = n_fft // 2; band_bins:
+    None = every bin, or (lo, hi) - lo > hi is the empty band (NaN); bands: None = one analysis band over every bin, or up to 40
+    disjoint ascending inclusive (lo, hi) bin pairs; split_bins: None, or per estimate the first bin of the upper part (-1: none).
+    Device views of one buffer are read where they lie.  deferred: a function that returns the tuple."""
+    n_fft, hop = check_coherence_frames(n_fft, hop)                 # (§20's framing)
+    rho, drop = check_spectrum_rolloff(rolloff), check_spectrum_drop(drop_db)
+    lo, hi = (0, n_fft // 2) if band_bins is None else (int(band_bins[0]), int(band_bins[1]))
+    if lo <= hi and (lo < 0 or hi > n_fft // 2):
+        raise ValueError("band_bins must be empty (lo > hi) or satisfy 0 <= lo <= hi <= n_fft // 2")
+    tab = np.asarray([(0, n_fft // 2)] if bands is None else bands)
+    if tab.ndim != 2 or tab.shape[1] != 2 or not 1 <= tab.shape[0] <= SPECTRUM_MAX_BANDS or tab.dtype.kind not in "iu":
+        raise ValueError("bands must be None or 1 to %d integer (lo, hi) pairs" % SPECTRUM_MAX_BANDS)
+    if np.any(tab[:, 0] < 0) or np.any(tab[:, 0] > tab[:, 1]) or np.any(tab[:, 1] > n_fft // 2) or np.any(tab[1:, 0] <= tab[:-1, 1]):
+        raise ValueError("bands must be disjoint ascending ranges with 0 <= lo <= hi <= n_fft // 2")
+    tab = np.ascontiguousarray(tab, dtype=np.int32)                      # read by the library when the call is queued
+    tgts, ests = list(tgt_list), list(est_list)
+    n_t, n_e, nb = len(tgts), len(ests), n_fft // 2 + 1
+    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
+    if idx.shape[0] != n_e:
+        raise ValueError("one target index per estimate")
+    if n_e and (idx.min() < 0 or idx.max() >= n_t):
+        raise ValueError("tgt_index out of range")
+    sp = np.full(n_e, -1, np.int32) if split_bins is None else np.asarray(split_bins, dtype=np.int32).reshape(-1)
+    if sp.shape[0] != n_e or (n_e and sp.min() < -1):
+        raise ValueError("split_bins must hold one bin >= 0, or -1 for none, per estimate")
+    require_gpu()
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else default_device()
+    with torch.cuda.device(dev):
+        sig = torch.empty((n_t + n_e, SPECTRUM_SIG_COLUMNS), dtype=torch.float64, device=dev)
+        pair = torch.empty((n_e, SPECTRUM_PAIR_COLUMNS), dtype=torch.float64, device=dev)
+        ltas = torch.empty((n_t + n_e, nb), dtype=torch.float64, device=dev) if return_ltas else None
+        if n_t:
+            if n_e:
+                tgt_side, est_side, tl, el = _placed_where_they_lie(tgts, ests, idx, dev)
+                if not np.array_equal(el, tl[idx]):
+                    raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+            else:
+                f64 = any(_is_f64(w) for w in tgts)
+                data, off, tl = _ragged_where_they_lie(tgts, dev, torch.float64 if f64 else torch.float32)
+                tgt_side, est_side = (data, int(f64), off), (None, 0, None)
+            lens = tl.astype(np.int32)
+            B_ = tab.shape[0]
+            ws_bytes = int(lib.ssr_spectrum_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p), n_e,
+                                                            n_fft, hop, B_))
+            ws = _workspace(ws_bytes, dev)
+            lens_h, idx_h, sp_h = _host_i32(lens, dev), _host_i32(idx, dev), _host_i32(sp, dev)
+            _lib.check(lib.ssr_spectrum(*_args(tgt_side), _vp(lens_h), n_t, *_args(est_side), _vp(idx_h) if n_e else None, n_e, n_fft, hop,
+                                        lo, hi, rho, drop, B_, tab.ctypes.data_as(C.c_void_p), _vp(sp_h) if n_e else None, _vp(sig),
+                                        _vp(pair) if n_e else None, _vp(ltas), _vp(ws), ws_bytes, _stream()))
+        take = lambda t: (Pending(t) if t.numel() else (lambda: np.empty(tuple(t.shape))))      # noqa: E731
+        got = [take(sig), take(pair)] + ([take(ltas)] if return_ltas else [])
+        collect = lambda: tuple(g() for g in got)      # noqa: E731
+        return collect if deferred else collect()
+
+
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
 PITCH_FS = 16000                 # the rate every signal is tracked at
 PITCH_HOP = 160

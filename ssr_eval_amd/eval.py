@@ -22,7 +22,7 @@ from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
 from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _LOUD_DIFF_NAMES, _LOUD_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
-    _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _WAVE_NAMES
+    _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _SPEC_NAMES, _SPEC_PAIR_NAMES, _WAVE_NAMES
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
 
@@ -38,6 +38,9 @@ _PHASE_KEYS, _MRSTFT_KEYS, _BSS_KEYS = _PHASE_NAMES, _MRSTFT_NAMES, _BSS_NAMES
 _COH_KEYS = _COH_NAMES + _COH_HF_NAMES
 # the loudness range stays out of a key's result: it is NaN for files under 3 s and the aggregate is a plain mean
 _LOUD_KEYS = (_LOUD_NAMES[0], _LOUD_DIFF_NAMES[0], _LOUD_NAMES[5], _LOUD_DIFF_NAMES[2])
+# of the spectrum family a key's result keeps the output's bandwidth, its difference to the target's, the HF level difference and the
+# third-octave LTAS distance
+_BW_KEYS = (_SPEC_NAMES[0], _SPEC_PAIR_NAMES[0], _SPEC_PAIR_NAMES[3], _SPEC_PAIR_NAMES[4])
 
 
 def _option_dict(value):
@@ -231,9 +234,34 @@ def _loudness_check(h, v):
     B.check_loudness_rate(h.evaluationset_sr)
 
 
+def _bandwidth_args(h, v, keys):
+    """-> ((n_fft, hop, band, one split frequency per degradation key, rolloff, drop_db), {"names": the family's keys}): the split is
+    `split` Hz for every key where the option names one, else the key's own cutoff (key_cutoff_hz; None for mp3 keys - NaN hf_diff)."""
+    q = v if isinstance(v, dict) else {}
+    split = [float(q["split"])] * len(keys) if "split" in q else [key_cutoff_hz(k) for k in keys]
+    return ((q.get("n_fft", 2048), q.get("hop"), q.get("band"), split, q.get("rolloff", B.SPECTRUM_ROLLOFF), q.get("drop_db", B.SPECTRUM_DROP_DB)),
+            {"names": _BW_KEYS})
+
+
+def _bandwidth_check(h, v):
+    if v is not True:
+        if not isinstance(v, dict) or not v or set(v) - {"n_fft", "hop", "band", "split", "rolloff", "drop_db"}:
+            raise ValueError("bandwidth must be None, True or a dict of 'n_fft', 'hop', 'band', 'split', 'rolloff' and / or 'drop_db'")
+        if "split" in v and (v["split"] is None or isinstance(v["split"], (bool, str, list, tuple, dict))):
+            raise ValueError("split must be a frequency in Hz (leave it out to split every key at its own cutoff)")
+    (n_fft, hop, band, split, rho, drop), _ = _bandwidth_args(h, v, ["k"])
+    n_fft, hop = B.check_coherence_frames(n_fft, hop)
+    B.check_spectrum_rolloff(rho)
+    B.check_spectrum_drop(drop)
+    h.audio_metrics._ltas_bands(h.evaluationset_sr, n_fft, band)
+    h.audio_metrics._bandwidth_splits(n_fft, split, 1)
+
+
 # The open end of the registry: a new family appends HERE (queued after the two tuples above, its keys behind theirs).
 _TAIL_FAMILIES = (
     _Family("loudness", "loudness_multi", "loudness_batch", _LOUD_KEYS, _loudness_check, lambda h, keys: ((), {"names": _LOUD_KEYS}), False),
+    _Family("bandwidth", "bandwidth_multi", "bandwidth_batch", _BW_KEYS, _bandwidth_check,
+            lambda h, keys: _bandwidth_args(h, h.bandwidth, keys), True),
 )
 
 
@@ -318,7 +346,7 @@ class SSR_Eval_Helper:
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
                  quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None,
-                 coherence=None, loudness=None):
+                 coherence=None, loudness=None, bandwidth=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -364,6 +392,13 @@ class SSR_Eval_Helper:
         target's - a testee that rescales or clips its output shows here, whatever the level-sensitive keys say
         (AudioMetrics.loudness_multi / loudness_batch at evaluation_sr, an integer in 8000 .. 192000 Hz).  A
         file shorter than 400 ms, or below -70 LUFS throughout, has NaN for lufs and lufs_diff.
+        bandwidth (not in the reference): None = off; True = every key also gets bw_hz, the frequency below which 0.97 of the output's
+        summed spectral magnitudes lies (BasicTestee's cutoff rule as a metric), bw_diff, that minus the target's, hf_diff, the
+        output's power above the key's own cutoff relative to its total minus the target's, in dB (key_cutoff_hz; mp3 keys and keys
+        with no bin above the cutoff: NaN), and ltas_dist, the RMS difference in dB of the two long-term average spectra in
+        third-octave bands - all invariant to gain (AudioMetrics.bandwidth_multi / bandwidth_batch at evaluation_sr, DESIGN.md
+        section 22); a dict = `n_fft` (256, 512, 1024 or 2048; default 2048), `hop` (default n_fft // 2), `band` ((lo_hz, hi_hz), the
+        band scored), `split` (the same split frequency in Hz for every key, mp3 included), `rolloff` (in (0, 1)) and / or `drop_db`.
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -379,7 +414,8 @@ class SSR_Eval_Helper:
         self.audio_metrics = AudioMetrics(self.evaluationset_sr, precision=precision, device=device)
         # every family option is checked here, before the caller's settings are touched (the mel checks need audio_metrics)
         options = dict(lsd_split=lsd_split, stoi=stoi, waveform=waveform, mel=mel, mel_dtw=mel_dtw, quality=quality, pitch=pitch,
-                       phase=phase, mrstft=mrstft, bss_sdr=bss_sdr, coherence=coherence, loudness=loudness)
+                       phase=phase, mrstft=mrstft, bss_sdr=bss_sdr, coherence=coherence, loudness=loudness,
+                       bandwidth=bandwidth)
         for f in _FAMILIES + _LATER_FAMILIES + _TAIL_FAMILIES:
             if options[f.option] is not None:
                 f.check(self, options[f.option])

@@ -35,6 +35,8 @@ _COH_NAMES = ("msc", "coh_sdr", "coh_bw")                 # a band's columns of 
 _COH_HF_NAMES = ("msc_hf", "coh_sdr_hf")                  # the same above a split frequency
 _LOUD_NAMES = ("lufs", "lra", "lufs_m_max", "lufs_s_max", "peak_db", "true_peak_db")     # the columns of ssr_loudness
 _LOUD_DIFF_NAMES = ("lufs_diff", "lra_diff", "true_peak_diff")                           # estimate minus target
+_SPEC_NAMES = ("bw_hz", "edge_hz", "centroid_hz", "hf_db")                                # of one signal (ssr_spectrum)
+_SPEC_PAIR_NAMES = ("bw_diff", "edge_diff", "centroid_diff", "hf_diff", "ltas_dist", "ltas_max")     # estimate against target
 
 
 def which_mask(which, names):
@@ -832,6 +834,154 @@ class AudioMetrics:
         dicts.  Each target is measured once for its K estimates."""
         ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
         return _regroup(self.loudness_batch(ests, tgts, return_blocks, names, resident, True), n, K, deferred)
+
+    # ---- spectrum (DESIGN §22): what bandwidth did a signal come out with?  From its long-term average spectrum on n_fft-point
+    # periodic-Hann segments at self.rate (no padding): the rolloff (the reference's BasicTestee._find_cutoff as a metric), the
+    # spectral edge, the centroid, the level above a split frequency - and, with a target, their differences and the distance of the
+    # two spectra in third-octave bands.  Every value is invariant to gain
+    @staticmethod
+    def _bandwidth_names(names, with_target):
+        """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
+        allowed = _SPEC_NAMES + (_SPEC_PAIR_NAMES if with_target else ())
+        if names is None:
+            return allowed
+        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(k, str) and k in allowed for k in names):
+            raise ValueError("names must be None or a tuple of %s" % (allowed,))
+        return tuple(k for k in allowed if k in names)
+
+    @staticmethod
+    def _ltas_bands(rate, n_fft, band):
+        """The analysis bands of ltas_dist / ltas_max as inclusive bin pairs: base-2 third-octave bands, centres 1000 2^(i / 3) Hz,
+        edges 2^(+-1/6) around them, a band's bins those with f_lo <= k rate / n_fft < f_hi.  The table starts at the lowest band
+        with f_lo >= lo_hz that holds at least 2 bins; the top band is clipped at the scored band's last bin and kept if it still
+        holds at least 2; at most 40 bands (the lowest 40)."""
+        lo_bin, hi_bin = AudioMetrics._phase_bins(rate, n_fft, band) or (0, n_fft // 2)
+        lo_hz = 0.0 if band is None else float(band[0])
+        edge = lambda j: 1000.0 * 2.0 ** ((2 * j - 1) / 6.0)      # noqa: E731  (the lower edge of band j, the upper edge of band j - 1)
+        out = []
+        for i in range(-60, 40):
+            f_lo, f_hi = edge(i), edge(i + 1)
+            k0, k1 = math.ceil(f_lo * n_fft / rate), math.ceil(f_hi * n_fft / rate) - 1
+            if f_lo < lo_hz or k0 < lo_bin or k0 > hi_bin:
+                continue
+            clipped = k1 > hi_bin
+            k1 = min(k1, hi_bin)
+            if (not out or clipped) and k1 - k0 + 1 < 2:
+                continue
+            if k1 >= k0 and len(out) < B.SPECTRUM_MAX_BANDS:
+                out.append((k0, k1))
+        if not out:
+            raise ValueError("band %r holds no third-octave band of 2 bins of a %d-point transform at %r Hz" % (band, n_fft, rate))
+        return out
+
+    def _bandwidth_splits(self, n_fft, split, n):
+        """None, or the first upper bin of n pairs by coherence's rule, ceil(split n_fft / rate): split = one frequency in Hz for every
+        pair, or a list of one per pair (None: no split for that pair, -1)."""
+        if split is None:
+            return None
+        per_pair = isinstance(split, list)
+        splits = split if per_pair else [split] * n
+        if len(splits) != n:
+            raise ValueError("one split frequency per pair")
+        bins = []
+        for s in splits:
+            if s is None and per_pair:
+                bins.append(-1)
+                continue
+            if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= float(s) < math.inf:
+                raise ValueError("a split frequency is a finite number >= 0 in Hz")
+            bins.append(min(math.ceil(fractions.Fraction(float(s)) * n_fft / fractions.Fraction(float(self.rate))), n_fft // 2 + 1))
+        return bins
+
+    def bandwidth(self, est, target=None, n_fft=2048, hop=None, band=None, split_hz=None, rolloff=B.SPECTRUM_ROLLOFF,
+                  drop_db=B.SPECTRUM_DROP_DB, names=None, return_ltas=False):
+        """{'bw_hz', 'edge_hz', 'centroid_hz', 'hf_db'} of one signal at self.rate, from its long-term average spectrum: the rolloff -
+        the frequency below which `rolloff` of the summed magnitudes lies (0.97: the reference's BasicTestee cutoff) -, the highest
+        frequency whose power is within drop_db of the largest bin's, the power centroid, and the power at and above split_hz
+        relative to the whole band's, in dB (NaN without split_hz or where no bin lies above it).  With a target also 'bw_diff',
+        'edge_diff', 'centroid_diff', 'hf_diff' - the estimate's value minus the target's - and 'ltas_dist' / 'ltas_max', the RMS and
+        the largest difference in dB of the two spectra's third-octave band levels, each relative to its signal's own total.  Every
+        value is invariant to gain.  n_fft: 256, 512, 1024 or 2048; hop: None = n_fft // 2; band: None = every bin, or (lo_hz, hi_hz),
+        mapped to bins as phase_distance maps it; names: None, or the result keys wanted; return_ltas: also 'ltas' (and
+        'target_ltas'), the float64 [n_fft // 2 + 1] one-sided power per bin averaged over the segments.  Shorter than n_fft, or
+        digitally silent in the band: NaN."""
+        return self.bandwidth_batch([est], None if target is None else [target], n_fft, hop, band, split_hz, rolloff, drop_db, names,
+                                    return_ltas)[0]
+
+    def bandwidth_batch(self, ests, targets=None, n_fft=2048, hop=None, band=None, split_hz=None, rolloff=B.SPECTRUM_ROLLOFF,
+                        drop_db=B.SPECTRUM_DROP_DB, names=None, return_ltas=False, resident=False, deferred=False):
+        """bandwidth() for lists of signals or, with targets, of pairs (waveform_batch's input rules: metrics.py:89-90 truncation;
+        float32 or float64 signals, read in their own dtype: one ssr_spectrum call per dtype group).  A target object passed for
+        several pairs is transformed once.  split_hz: None, one frequency for every signal, or a list of one per signal (None:
+        that signal's hf values are NaN).  deferred: as evaluation_batch."""
+        n_fft, hop = B.check_coherence_frames(n_fft, hop)                   # (§20's framing)
+        rho, drop = B.check_spectrum_rolloff(rolloff), B.check_spectrum_drop(drop_db)
+        if not isinstance(return_ltas, bool):
+            raise ValueError("return_ltas must be True or False")
+        with_t = targets is not None
+        keys = self._bandwidth_names(names, with_t)
+        bins = self._phase_bins(self.rate, n_fft, band)
+        table = self._ltas_bands(self.rate, n_fft, band)
+        n = min(len(ests), len(targets)) if with_t else len(ests)
+        splits = self._bandwidth_splits(n_fft, split_hz, n)
+        hz = float(self.rate) / n_fft
+
+        def row_dict(sig, pair, ltas, t_ltas):
+            d = dict(zip(_SPEC_NAMES, (float(sig[0]) * hz, float(sig[1]) * hz, float(sig[2]) * hz, float(pair[0]) if pair is not None else math.nan)))
+            if with_t:
+                d.update(zip(_SPEC_PAIR_NAMES, (float(pair[2]) * hz, float(pair[3]) * hz, float(pair[4]) * hz, float(pair[5]), float(pair[6]),
+                                                float(pair[7]))))
+            d = {k: d[k] for k in keys}
+            if return_ltas:
+                d["ltas"] = np.array(ltas)
+                if with_t:
+                    d["target_ltas"] = np.array(t_ltas)
+            return d
+
+        if not with_t and splits is None:          # signals alone: they are the call's targets, there is no estimate
+            sigs = [self._loudness_signal(e) for e in ests]
+            groups = {}
+            for i, w in enumerate(sigs):
+                groups.setdefault(bool(B._is_f64(w)), []).append(i)
+            pending = [(idx, B.spectrum_metrics([sigs[i] for i in idx], [], [], n_fft, hop, bins, rho, drop, table, None, return_ltas,
+                                                self._device, deferred=True)) for idx in groups.values()]
+
+            def finish():
+                out = [None] * len(sigs)
+                for idx, p in pending:
+                    got = p()
+                    for j, i in enumerate(idx):
+                        out[i] = row_dict(got[0][j], None, got[2][j] if return_ltas else None, None)
+                return out
+            return finish if deferred else finish()
+
+        # pairs - or signals alone with a split: the level above it is a pair's value, so each signal is paired with itself
+        sigs = [self._loudness_signal(e) for e in ests[:n]]
+        tgts = [self._loudness_signal(t) for t in targets[:n]] if with_t else sigs
+
+        def call(tg, es, index, idx):
+            got = B.spectrum_metrics(tg, es, index, n_fft, hop, bins, rho, drop, table, None if splits is None else [splits[i] for i in idx],
+                                     return_ltas, self._device, deferred=True)
+            return lambda: (got(), len(tg), list(index))
+
+        def dicts(vals):
+            got, n_t, index = vals
+            return [row_dict(got[0][n_t + j], got[1][j], got[2][n_t + j] if return_ltas else None, got[2][index[j]] if return_ltas else None)
+                    for j in range(len(index))]
+        return self._pairs((call, dicts), sigs, tgts, resident, deferred, by_dtype=True, per_pair=True)
+
+    def bandwidth_multi(self, ests_by_key, targets, n_fft=2048, hop=None, band=None, split_hz=None, rolloff=B.SPECTRUM_ROLLOFF,
+                        drop_db=B.SPECTRUM_DROP_DB, names=None, return_ltas=False, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
+        to each other in one call and the target is transformed once."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        if isinstance(split_hz, list):
+            if len(split_hz) != K:
+                raise ValueError("one split frequency per key")
+            split_hz = list(split_hz) * n
+        return _regroup(self.bandwidth_batch(ests, tgts, n_fft, hop, band, split_hz, rolloff, drop_db, names, return_ltas, resident, True),
+                        n, K, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
