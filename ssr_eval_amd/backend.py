@@ -1329,6 +1329,136 @@ def spectrum_metrics(tgt_list, est_list, tgt_index, n_fft=2048, hop=None, band_b
         return collect if deferred else collect()
 
 
+# ---- auditory: neurogram similarity (NSIM) of gammatone spectrograms --------------------------------------------------------------
+AUDITORY_BANDS = (3, 64)                 # SSR_AUDITORY_MIN_BANDS, SSR_AUDITORY_MAX_BANDS
+AUDITORY_N_BANDS = 32
+AUDITORY_RANGE_DB = 60.0
+AUDITORY_MAX_BLOCKS = 65536              # SSR_AUDITORY_MAX_BLOCKS: hop-blocks per signal
+AUDITORY_PAIR_COLUMNS = 3                # SSR_AUDITORY_PAIR_COLS
+_GAMMATONE_A = math.pi * 720.0 * 2.0 ** -6 / 36.0      # a_gamma of order 4: pi 6! 2^-6 / (3!)^2
+
+
+def check_auditory_bands(n_bands):
+    """n_bands as an int, or ValueError: an integer in AUDITORY_BANDS (the C ABI's own check)."""
+    if isinstance(n_bands, bool) or not isinstance(n_bands, (int, np.integer)) or not AUDITORY_BANDS[0] <= int(n_bands) <= AUDITORY_BANDS[1]:
+        raise ValueError("n_bands must be an integer in [%d, %d]" % AUDITORY_BANDS)
+    return int(n_bands)
+
+
+def check_auditory_range(range_db):
+    """range_db as a float, or ValueError: a number in (0, 150] (the C ABI's own check)."""
+    if isinstance(range_db, bool) or not isinstance(range_db, (int, float, np.integer, np.floating)) or not 0.0 < float(range_db) <= 150.0:
+        raise ValueError("range_db must be a number in (0, 150]")
+    return float(range_db)
+
+
+def auditory_hop(fs):
+    """Samples per 10 ms block at `fs`: round(fs / 100), halves up; the image's window is two of them."""
+    if isinstance(fs, bool) or not isinstance(fs, (int, float, np.integer, np.floating)) or not 50.0 <= float(fs) < math.inf:
+        raise ValueError("the auditory family needs a rate of at least 50 Hz")
+    return int(math.floor(float(fs) / 100.0 + 0.5))
+
+
+def gammatone_design(fs, n_bands=AUDITORY_N_BANDS, band=None):
+    """Hohmann's complex all-pole gammatone filterbank of order 4 at rate fs -> (f_c [n_bands] in Hz, coef [n_bands, 3]
+    float64 = Re a, Im a, g): centres equally spaced on the ERB-number scale 21.4 log10(1 + 0.00437 f) from band[0] to band[1]
+    inclusive (None: 50 Hz to 0.45 fs); b = ERBN(f_c) / a_gamma, lambda = exp(-2 pi b / fs), a = lambda exp(i 2 pi f_c / fs),
+    g = 2 (1 - lambda)^4, so that |H(f_c)| = 2.  ValueError unless 3 <= n_bands <= 64 and 0 < lo < hi < fs / 2."""
+    n_bands = check_auditory_bands(n_bands)
+    auditory_hop(fs)
+    fs = float(fs)
+    if band is None:
+        band = (50.0, 0.45 * fs)
+    ok = isinstance(band, (tuple, list)) and len(band) == 2 and \
+        all(not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) for v in band)
+    if not ok or not 0.0 < float(band[0]) < float(band[1]) < fs / 2.0:
+        raise ValueError("band must be None or (lo_hz, hi_hz) with 0 < lo_hz < hi_hz < fs / 2")
+    scale = lambda f: 21.4 * math.log10(1.0 + 0.00437 * f)      # noqa: E731
+    e = np.linspace(scale(float(band[0])), scale(float(band[1])), n_bands)
+    fc = (10.0 ** (e / 21.4) - 1.0) / 0.00437
+    lam = np.exp(-2.0 * np.pi * (24.7 * (1.0 + 0.00437 * fc) / _GAMMATONE_A) / fs)
+    coef = np.stack([lam * np.cos(2.0 * np.pi * fc / fs), lam * np.sin(2.0 * np.pi * fc / fs), 2.0 * (1.0 - lam) ** 4], axis=1)
+    return fc, np.ascontiguousarray(coef, dtype=np.float64)
+
+
+def auditory_metrics(tgt_list, est_list, tgt_index, fs, n_bands=AUDITORY_N_BANDS, band=None, range_db=AUDITORY_RANGE_DB, match_level=True,
+                     split_bands=None, return_bands=False, return_images=False, hop=None, device=None, deferred=False):
+    """The auditory family (ssr_auditory) on the signals tgt_list + est_list at rate fs, estimate e belonging to target
+    tgt_index[e] and as long as it (float32 or float64 waveforms; a list holding both dtypes is widened to float64) -> (pair [n_est, 3]
+    float64: nsim, nsim_hf, nsim_lf; bands [n_est, n_bands]: the mean NSIM of every interior band, NaN in the two edge bands, or None
+    without return_bands; images: a list of the n_tgt + n_est dB images [T, n_bands] - an estimate's level matched and on its target's
+    floor - or None without return_images).  est_list = [] with return_images yields the targets' images.  split_bands: None, or per
+    estimate the first interior band of its upper part (n_bands - 1: none above; -1: no split); hop: None = auditory_hop(fs) (the
+    definition's 10 ms), or the samples per block.  A signal of more than AUDITORY_MAX_BLOCKS blocks is refused.  Device views of
+    one buffer are read where they lie.  The library keeps a small table (about 120 n_bands bytes) per distinct (fs, n_bands, band,
+    hop) for the life of the process: a sweep over thousands of designs pays that memory.  deferred: a function that returns the
+    tuple."""
+    _, coef = gammatone_design(fs, n_bands, band)
+    C_ = coef.shape[0]
+    rng_db = check_auditory_range(range_db)
+    if not isinstance(match_level, (bool, np.bool_)):
+        raise ValueError("match_level must be True or False")
+    hop = auditory_hop(fs) if hop is None else hop
+    if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or int(hop) < 1:
+        raise ValueError("hop must be None or an integer >= 1")
+    hop = int(hop)
+    tgts, ests = list(tgt_list), list(est_list)
+    n_t, n_e = len(tgts), len(ests)
+    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
+    if idx.shape[0] != n_e:
+        raise ValueError("one target index per estimate")
+    if n_e and (idx.min() < 0 or idx.max() >= n_t):
+        raise ValueError("tgt_index out of range")
+    sp = np.full(n_e, -1, np.int32) if split_bands is None else np.asarray(split_bands, dtype=np.int32).reshape(-1)
+    if sp.shape[0] != n_e or (n_e and (sp.min() < -1 or sp.max() > C_ - 1 or np.any(sp == 0))):
+        raise ValueError("split_bands must hold -1 or a band in [1, n_bands - 1] per estimate")
+    require_gpu()
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else default_device()
+    with torch.cuda.device(dev):
+        pair = torch.empty((n_e, AUDITORY_PAIR_COLUMNS), dtype=torch.float64, device=dev)
+        bands = torch.empty((n_e, C_), dtype=torch.float64, device=dev) if return_bands else None
+        images, rows = None, np.zeros(0, np.int64)
+        if n_t:
+            if n_e:
+                tgt_side, est_side, tl, el = _placed_where_they_lie(tgts, ests, idx, dev)
+                if not np.array_equal(el, tl[idx]):
+                    raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+            else:
+                f64 = any(_is_f64(w) for w in tgts)
+                data, off, tl = _ragged_where_they_lie(tgts, dev, torch.float64 if f64 else torch.float32)
+                tgt_side, est_side = (data, int(f64), off), (None, 0, None)
+            blocks = np.where(tl >= 2 * hop, tl // hop, 0)
+            if blocks.max() > AUDITORY_MAX_BLOCKS:
+                raise ValueError("a signal may hold at most %d blocks of %d samples" % (AUDITORY_MAX_BLOCKS, hop))
+            rows = np.maximum(blocks - 1, 0).astype(np.int64)
+            rows = np.concatenate([rows, rows[idx]])
+            if return_images:
+                images = torch.empty((int(rows.sum()), C_), dtype=torch.float64, device=dev)
+            lens = tl.astype(np.int32)
+            ws_bytes = int(lib.ssr_auditory_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p), n_e, hop, C_))
+            ws = _workspace(ws_bytes, dev)
+            lens_h, idx_h, sp_h = _host_i32(lens, dev), _host_i32(idx, dev), _host_i32(sp, dev)
+            # (coef is read by the library before the call returns: its table of the call is built on the host)
+            _lib.check(lib.ssr_auditory(*_args(tgt_side), _vp(lens_h), n_t, *_args(est_side), _vp(idx_h) if n_e else None, n_e, hop, C_,
+                                        coef.ctypes.data_as(C.c_void_p), rng_db, int(bool(match_level)), _vp(sp_h) if n_e else None,
+                                        _vp(pair) if n_e else None, _vp(bands), _vp(images), _vp(ws), ws_bytes, _stream()))
+        take = lambda t: (Pending(t) if t.numel() else (lambda: np.empty(tuple(t.shape))))      # noqa: E731
+        got = [take(pair), take(bands) if return_bands else (lambda: None)]
+        if return_images:
+            edges = np.concatenate(([0], np.cumsum(rows))).astype(np.int64)
+            flat = take(images) if images is not None else (lambda: np.empty((0, C_)))
+
+            def cut():
+                a = flat()
+                return [np.array(a[edges[i]:edges[i + 1]]) for i in range(len(rows))]
+            got.append(cut)
+        else:
+            got.append(lambda: None)
+        collect = lambda: tuple(g() for g in got)      # noqa: E731
+        return collect if deferred else collect()
+
+
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
 PITCH_FS = 16000                 # the rate every signal is tracked at
 PITCH_HOP = 160

@@ -123,7 +123,7 @@ inline bool ssr_multi_fast_path(const ssr_plan* pl, bool est64) {
   return ssr_stft_uses_wave_engine(pl, false) || ssr_stft_rn_wave_radix(pl) != 0;
 }
 
-// ---- the per-pair families (tu_stoi / tu_wave_metrics / tu_quality / tu_pitch / tu_phase / tu_mrstft / tu_bss / tu_coherence / tu_spectrum): estimate e is scored
+// ---- the per-pair families (tu_stoi / tu_wave_metrics / tu_quality / tu_pitch / tu_phase / tu_mrstft / tu_bss / tu_coherence / tu_spectrum / tu_auditory): estimate e is scored
 // against target tgt_index[e].  The device side of what they share is ssr_pairs.h ----
 // host-side validation of the two descriptor arrays (host memory): lengths in [0, len_limit), indices in [0, n_tgt)
 inline int ssr_check_pair_index(const int32_t* tgt_len, int n_tgt, const int32_t* tgt_index, int n_est, int64_t len_limit,

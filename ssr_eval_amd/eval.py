@@ -22,7 +22,7 @@ from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
 from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _LOUD_DIFF_NAMES, _LOUD_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
-    _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _SPEC_NAMES, _SPEC_PAIR_NAMES, _WAVE_NAMES
+    _NSIM_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _SPEC_NAMES, _SPEC_PAIR_NAMES, _WAVE_NAMES
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
 
@@ -41,6 +41,8 @@ _LOUD_KEYS = (_LOUD_NAMES[0], _LOUD_DIFF_NAMES[0], _LOUD_NAMES[5], _LOUD_DIFF_NA
 # of the spectrum family a key's result keeps the output's bandwidth, its difference to the target's, the HF level difference and the
 # third-octave LTAS distance
 _BW_KEYS = (_SPEC_NAMES[0], _SPEC_PAIR_NAMES[0], _SPEC_PAIR_NAMES[3], _SPEC_PAIR_NAMES[4])
+# of the auditory family a key's result keeps the similarity over all bands and over the bands above the key's cutoff
+_AUD_KEYS = _NSIM_NAMES[:2]
 
 
 def _option_dict(value):
@@ -257,11 +259,35 @@ def _bandwidth_check(h, v):
     h.audio_metrics._bandwidth_splits(n_fft, split, 1)
 
 
+def _auditory_args(h, v, keys):
+    """-> ((one split frequency per degradation key, n_bands, band, range_db, match_level), {"names": the family's keys}): the split is
+    `split` Hz for every key where the option names one, else the key's own cutoff (key_cutoff_hz; None for mp3 keys - NaN nsim_hf)."""
+    q = v if isinstance(v, dict) else {}
+    split = [float(q["split"])] * len(keys) if "split" in q else [key_cutoff_hz(k) for k in keys]
+    return ((split, q.get("n_bands", B.AUDITORY_N_BANDS), q.get("band"), q.get("range_db", B.AUDITORY_RANGE_DB), q.get("match_level", True)),
+            {"names": _AUD_KEYS})
+
+
+def _auditory_check(h, v):
+    if v is not True:
+        if not isinstance(v, dict) or not v or set(v) - {"n_bands", "band", "range_db", "split", "match_level"}:
+            raise ValueError("auditory must be None, True or a dict of 'n_bands', 'band', 'range_db', 'split' and / or 'match_level'")
+        if "split" in v and (isinstance(v["split"], bool) or not isinstance(v["split"], (int, float, np.integer, np.floating))):
+            raise ValueError("split must be a frequency in Hz (leave it out to split every key at its own cutoff)")
+    (split, n_bands, band, range_db, match), _ = _auditory_args(h, v, ["k"])
+    fc, _ = B.gammatone_design(h.evaluationset_sr, n_bands, band)
+    B.check_auditory_range(range_db)
+    if not isinstance(match, bool):
+        raise ValueError("match_level must be True or False")
+    h.audio_metrics._nsim_splits(fc, split, 1)
+
+
 # The open end of the registry: a new family appends HERE (queued after the two tuples above, its keys behind theirs).
 _TAIL_FAMILIES = (
     _Family("loudness", "loudness_multi", "loudness_batch", _LOUD_KEYS, _loudness_check, lambda h, keys: ((), {"names": _LOUD_KEYS}), False),
     _Family("bandwidth", "bandwidth_multi", "bandwidth_batch", _BW_KEYS, _bandwidth_check,
             lambda h, keys: _bandwidth_args(h, h.bandwidth, keys), True),
+    _Family("auditory", "nsim_multi", "nsim_batch", _AUD_KEYS, _auditory_check, lambda h, keys: _auditory_args(h, h.auditory, keys), True),
 )
 
 
@@ -346,7 +372,7 @@ class SSR_Eval_Helper:
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
                  quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None,
-                 coherence=None, loudness=None, bandwidth=None):
+                 coherence=None, auditory=None, loudness=None, bandwidth=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -399,6 +425,12 @@ class SSR_Eval_Helper:
         third-octave bands - all invariant to gain (AudioMetrics.bandwidth_multi / bandwidth_batch at evaluation_sr, DESIGN.md
         section 22); a dict = `n_fft` (256, 512, 1024 or 2048; default 2048), `hop` (default n_fft // 2), `band` ((lo_hz, hi_hz), the
         band scored), `split` (the same split frequency in Hz for every key, mp3 included), `rolloff` (in (0, 1)) and / or `drop_db`.
+        auditory (not in the reference): None = off; True = every key also gets nsim, the neurogram similarity index of the output's
+        and the target's gammatone spectrograms (Hines & Harte 2012; 1 = identical images), and nsim_hf, the same over the bands
+        whose centre frequency is at or above the key's own cutoff (key_cutoff_hz; mp3 keys and keys with no band above the cutoff:
+        NaN) - invariant to the output's gain (AudioMetrics.nsim_multi / nsim_batch at evaluation_sr); a dict =
+        `n_bands` (3 to 64; default 32), `band` ((lo_hz, hi_hz) of the centre frequencies; default 50 Hz to 0.45 evaluation_sr),
+        `range_db` (default 60), `split` (the same split frequency in Hz for every key, mp3 included) and / or `match_level`.
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -415,7 +447,7 @@ class SSR_Eval_Helper:
         # every family option is checked here, before the caller's settings are touched (the mel checks need audio_metrics)
         options = dict(lsd_split=lsd_split, stoi=stoi, waveform=waveform, mel=mel, mel_dtw=mel_dtw, quality=quality, pitch=pitch,
                        phase=phase, mrstft=mrstft, bss_sdr=bss_sdr, coherence=coherence, loudness=loudness,
-                       bandwidth=bandwidth)
+                       bandwidth=bandwidth, auditory=auditory)
         for f in _FAMILIES + _LATER_FAMILIES + _TAIL_FAMILIES:
             if options[f.option] is not None:
                 f.check(self, options[f.option])

@@ -37,6 +37,7 @@ _LOUD_NAMES = ("lufs", "lra", "lufs_m_max", "lufs_s_max", "peak_db", "true_peak_
 _LOUD_DIFF_NAMES = ("lufs_diff", "lra_diff", "true_peak_diff")                           # estimate minus target
 _SPEC_NAMES = ("bw_hz", "edge_hz", "centroid_hz", "hf_db")                                # of one signal (ssr_spectrum)
 _SPEC_PAIR_NAMES = ("bw_diff", "edge_diff", "centroid_diff", "hf_diff", "ltas_dist", "ltas_max")     # estimate against target
+_NSIM_NAMES = ("nsim", "nsim_hf", "nsim_lf")                                              # the columns of ssr_auditory
 
 
 def which_mask(which, names):
@@ -982,6 +983,102 @@ class AudioMetrics:
             split_hz = list(split_hz) * n
         return _regroup(self.bandwidth_batch(ests, tgts, n_fft, hop, band, split_hz, rolloff, drop_db, names, return_ltas, resident, True),
                         n, K, deferred)
+
+    # ---- auditory: how alike do estimate and target look to the ear's filterbank?  The neurogram similarity index (NSIM,
+    # Hines & Harte 2012; the core of ViSQOL) of their gammatone spectrograms at self.rate: a 4th-order complex gammatone filterbank on
+    # the ERB scale, 20 ms power frames every 10 ms, dB over a range below the target's largest cell, a 3 x 3 SSIM-like index
+    @staticmethod
+    def _nsim_names(names):
+        """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
+        if names is None:
+            return _NSIM_NAMES
+        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(k, str) and k in _NSIM_NAMES for k in names):
+            raise ValueError("names must be None or a tuple of %s" % (_NSIM_NAMES,))
+        return tuple(k for k in _NSIM_NAMES if k in names)
+
+    @staticmethod
+    def _nsim_splits(fc, split, n):
+        """The first interior band at or above the split of n pairs (len(fc) - 1: the split lies above every interior band): split = None
+        (no split: -1 for every pair), one frequency in Hz for every pair, or a list of one per pair (None: -1 for that pair)."""
+        per_pair = isinstance(split, list)
+        splits = split if per_pair else [split] * n
+        if len(splits) != n:
+            raise ValueError("one split frequency per pair")
+        out = []
+        for s in splits:
+            if s is None and (per_pair or split is None):
+                out.append(-1)
+                continue
+            if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= float(s) < math.inf:
+                raise ValueError("a split frequency is a finite number >= 0 in Hz")
+            out.append(1 + int(np.searchsorted(fc[1:-1], float(s), side="left")))
+        return out
+
+    def nsim(self, est, target, split_hz=None, n_bands=B.AUDITORY_N_BANDS, band=None, range_db=B.AUDITORY_RANGE_DB, match_level=True,
+             return_bands=False):
+        """{'nsim', 'nsim_hf', 'nsim_lf'} of one (estimate, target) pair at self.rate: the neurogram similarity index of their
+        gammatone spectrograms - 1 for identical images, lower the less the estimate's time-frequency pattern resembles the
+        target's - over all interior bands, and over the interior bands whose centre frequency is at / above and below split_hz (NaN
+        without split_hz or where no such band exists).  n_bands: 3 to 64 bands with centres equally spaced on the ERB scale over
+        band = (lo_hz, hi_hz) (None: 50 Hz to 0.45 rate); range_db: the dB range below the target's largest cell that is scored;
+        match_level: the estimate's image is scaled to the target's total power first, so that the value is invariant to the
+        estimate's gain.  return_bands: also 'fvnsim', the mean over time of every band (NaN in the two edge bands), and
+        'centre_hz'.  Shorter than 40 ms (fewer than 3 image rows), or a digitally silent target: NaN."""
+        return self.nsim_batch([est], [target], split_hz, n_bands, band, range_db, match_level, return_bands)[0]
+
+    def nsim_batch(self, ests, targets, split_hz=None, n_bands=B.AUDITORY_N_BANDS, band=None, range_db=B.AUDITORY_RANGE_DB, match_level=True,
+                   return_bands=False, names=None, resident=False, deferred=False):
+        """nsim() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals, read
+        in their own dtype: one ssr_auditory call per (target dtype, estimate dtype) group).  A target object passed for several pairs
+        is filtered once.  split_hz: None, one frequency for every pair, or a list of one per pair (None: that pair's nsim_hf and
+        nsim_lf are NaN).  names: None, or the result keys wanted.  deferred: as evaluation_batch."""
+        fc, _ = B.gammatone_design(self.rate, n_bands, band)
+        rng_db = B.check_auditory_range(range_db)
+        if not isinstance(match_level, bool) or not isinstance(return_bands, bool):
+            raise ValueError("match_level and return_bands must be True or False")
+        keys = self._nsim_names(names)
+        n = min(len(ests), len(targets))
+        splits = self._nsim_splits(fc, split_hz, n)
+
+        def call(tgts, es, index, idx):
+            return B.auditory_metrics(tgts, es, index, self.rate, n_bands, band, rng_db, match_level, [splits[i] for i in idx], return_bands,
+                                      False, None, self._device, deferred=True)
+
+        def dicts(vals):
+            pair, bands, _ = vals
+            out = []
+            for j, row in enumerate(pair):
+                d = {k: float(v) for k, v in zip(_NSIM_NAMES, row) if k in keys}
+                if return_bands:
+                    d["fvnsim"], d["centre_hz"] = np.array(bands[j]), np.array(fc)
+                out.append(d)
+            return out
+        for w in list(ests[:n]) + list(targets[:n]):
+            if not isinstance(w, str) and len(w.shape) != 1:
+                raise ValueError("expected a 1-D signal, got shape %s" % (tuple(w.shape),))
+        return self._pairs((call, dicts), ests[:n], targets[:n], resident, deferred, by_dtype=True, per_pair=True)
+
+    def nsim_multi(self, ests_by_key, targets, split_hz=None, n_bands=B.AUDITORY_N_BANDS, band=None, range_db=B.AUDITORY_RANGE_DB,
+                   match_level=True, return_bands=False, names=None, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
+        to each other in one call and the target is filtered once."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        if isinstance(split_hz, list):
+            if len(split_hz) != K:
+                raise ValueError("one split frequency per key")
+            split_hz = list(split_hz) * n
+        return _regroup(self.nsim_batch(ests, tgts, split_hz, n_bands, band, range_db, match_level, return_bands, names, resident, True),
+                        n, K, deferred)
+
+    def gammatone_spectrogram(self, wav, n_bands=B.AUDITORY_N_BANDS, band=None, range_db=B.AUDITORY_RANGE_DB):
+        """(image [T, n_bands] float64, centre_hz [n_bands]): the gammatone power spectrogram of one signal at self.rate in dB re
+        full-scale power - 20 ms frames every 10 ms, no padding (T = 1 + (len - win) // hop), clamped range_db below its largest
+        cell; NaN for a digitally silent signal."""
+        fc, _ = B.gammatone_design(self.rate, n_bands, band)
+        _, _, images = B.auditory_metrics([self._loudness_signal(wav)], [], [], self.rate, n_bands, band, range_db, True, None, False, True,
+                                          None, self._device)
+        return images[0], np.array(fc)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
