@@ -293,6 +293,28 @@ template <typename T> SSR_DEV cx<T> csub(cx<T> a, cx<T> b) { return {a.x - b.x, 
 template <typename T> SSR_DEV cx<T> cmul(cx<T> a, cx<T> b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 template <typename T> SSR_DEV cx<T> cmul_negi(cx<T> a) { return {a.y, -a.x}; }   // a * (-i)
 
+// a * b + c rounded once, whatever -ffp-contract says: the device and the g++ host emulation run the same arithmetic
+SSR_DEV float ssr_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+SSR_DEV double ssr_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// Radix-2 butterfly with the twiddle on the second input, six fused multiply-adds:  a, b  <-  a + W b,  a - W b.
+// The difference is 2 a - (a + W b): the doubling is exact, so it is the sum's rounding error mirrored, not a second one
+// on top of it.  NEGI: the twiddle is -i W - the same six instructions with W's parts exchanged (a sign is an operand
+// modifier).
+template <bool NEGI = false, typename T> SSR_DEV void ssr_bfly2_tw(cx<T>& a, cx<T>& b, cx<T> W) {
+  cx<T> p;
+  if constexpr (!NEGI) {
+    p.x = ssr_fma(-W.y, b.y, ssr_fma(W.x, b.x, a.x));
+    p.y = ssr_fma(W.y, b.x, ssr_fma(W.x, b.y, a.y));
+  } else {
+    p.x = ssr_fma(W.x, b.y, ssr_fma(W.y, b.x, a.x));
+    p.y = ssr_fma(-W.x, b.x, ssr_fma(W.y, b.y, a.y));
+  }
+  b = {ssr_fma((T)2, a.x, -p.x), ssr_fma((T)2, a.y, -p.y)};
+  a = p;
+}
+template <typename T> SSR_DEV void ssr_bfly2_tw_negi(cx<T>& a, cx<T>& b, cx<T> W) { ssr_bfly2_tw<true>(a, b, W); }
+
 // LDS index padding for the FFT arrays: one spare element per 16.  An ADDITIVE pad keeps
 // pad(j + q*stride) = pad(j) + q*stride' for the power-of-two strides of the passes, so the compiler folds
 // the eight per-register offsets into the ds_read/ds_write immediate field (one address VALU op per

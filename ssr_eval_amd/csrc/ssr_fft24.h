@@ -114,6 +114,10 @@ SSR_DEV SsrWave24Base ssr_wave24_bases(int lane) {
 #define SSR_W24_LOAD_TW2 { const unsigned l_ = SSR_UIDX(tid & 63); \
                            SSR_UNROLL for (int i = 0; i < 9; ++i) R.tw2[i] = VT.at(l_ + (SSR_W24_N + 576 + 64 * i)); }
 // a radix-8 pass of the lane's three butterflies with twiddles w^(c t), t = 1..7, from the three loaded powers w^c, w^2c, w^4c
+// (multiplies, then ssr_bfly8 - NOT ssr_bfly8_tw as the 2048-point tail: the float64-estimate rotating engine is held to
+// 1e-9 of the block engine's metrics (tests/test_emu_kernels.py), whose log-SISpec sums log10(|Z| + 1e-12) over bins at
+// the transform's rounding floor; the fused butterflies are as accurate - 2.39e-16 against 2.37e-16 rms - but round
+// differently, and that comparison then reads 1.25e-9; profiles/fft_fma_notes.md section 6)
 #define SSR_W24_PASS(TW)                                                                                      \
   SSR_UNROLL for (int b = 0; b < SSR_W24_PB; ++b) {                                                           \
     cx<T>* x = R.v + 8 * b;                                                                                   \

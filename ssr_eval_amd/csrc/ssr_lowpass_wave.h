@@ -24,7 +24,7 @@ template <typename T> struct SsrLowpassWaveRegs {
   float pa[SSR_W_P], pb[SSR_W_P];     // the unit's samples (analysis mode)
   T wl[SSR_W_P / 2];                  // hann[tid + 64 r], r < 16  (hann[m + N/2] = 1 - hann[m]); requested twice per unit -
                                       // ahead of the analysis and ahead of the synthesis - instead of living through it
-  cx<T> tw1[7];
+  cx<T> tw1[3];
   cx<T> tw2[12];
 };
 

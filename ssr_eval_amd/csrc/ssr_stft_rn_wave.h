@@ -26,7 +26,7 @@ template <typename T, bool SUMS, int NQ, int P = 32, typename SA = float, typena
   T tx[P];
   SA pa[4 * NQ];                  // the next unit's decimated samples m = lane + 64 i, requested a unit ahead
   SB pb[4 * NQ];
-  cx<T> tw1[P == 32 ? 7 : 9];
+  cx<T> tw1[P == 32 ? 3 : 9];
   cx<T> tw2[P == 32 ? 12 : 9];
 };
 template <int P> SSR_HD constexpr int ssr_rn_wave_pn() { return P == 32 ? SSR_W_PN : SSR_W24_PN; }

@@ -8,8 +8,9 @@
 //   * exchanges are ordered by the hardware (the DS operations of one wave execute in order), so a "phase boundary" is a
 //     compiler-only wave-scope fence: no s_barrier, no s_waitcnt between a wave's writes and its reads;
 //   * what a lane needs every frame is loop-invariant and stays in registers: its 16 window values
-//     (w[m + N/2] = 1/2 - w[m]) and the 7 twiddles of the second pass (w^(8 (l mod 32) q) does not depend on the
-//     butterfly); the first pass needs none.  Only the third pass loads 3 table twiddles per butterfly;
+//     (w[m + N/2] = 1/2 - w[m]) and the 3 twiddles of the second pass (t, t^2, t^4 of t = w^(8 (l mod 32)), which does not
+//     depend on the butterfly); the first pass needs none.  Only the third pass loads 3 table twiddles per butterfly.
+//     Both radix-8 passes run the twiddles INSIDE the butterfly (ssr_bfly8_tw: three layers of fused radix-2 butterflies);
 //   * the per-frame LSD reduction is a wave shuffle, the silent-frame vote a ballot.
 // Occupancy is bounded by LDS, not by registers: one wave owns one 2048-point buffer (33 KB float64: 4 waves per CU, one
 // per SIMD, up to 512 VGPRs each) - or, with the re / im parts exchanged one after the other through a single array
@@ -97,7 +98,7 @@ template <typename T, bool SUMS> struct SsrWaveRegs {
   T wl[SSR_W_P / 2];         // 0.5 * hann[tid + 64 r], r < 16 of the next frame: requested at the TOP of the epilogue, ahead of
                              // the magnitude stores (behind them in the in-order memory counter every frame would wait for
                              // the stores' acknowledgements)
-  cx<T> tw1[7];              // w^(8 (tid mod 32) q), q = 1..7: requested while the first exchange is in flight
+  cx<T> tw1[3];              // t, t^2, t^4 of t = w^(8 (tid mod 32)): requested while the first exchange is in flight
   cx<T> tw2[12];             // w^j, w^2j, w^4j of the four third-pass butterflies: requested while the second one is
   double lsd_total;          // lane 0: sum over the chunk's frames of the per-frame LSD
 };
@@ -199,7 +200,7 @@ SSR_DEV int ssr_w_rd_paired(const SsrWavePBase& B, int i) {
     SSR_UNROLL for (int i = 9; i < 12; ++i) R.tw2[i] = VT.at(o3_ + (SSR_W_N + 224 + 64 * i)); }
 
 // The rest of the transform after the in-register radix-32 pass (ssr_dft32 applied to R.v): exchange, radix-8 pass with the
-// lane's seven twiddles, exchange, radix-8 pass with table twiddles.  On exit register 8 b + q holds Z[tid + 64 b + 256 q].
+// lane's three twiddles, exchange, radix-8 pass with table twiddles.  On exit register 8 b + q holds Z[tid + 64 b + 256 q].
 // BLK0: the untouched block descriptor (a fresh opaque lane index per stage: addresses are formed where they are used).
 // The lane index is `tid & 63` throughout: a workgroup of several autonomous waves (ssr_stft_rn_wave.h) passes an L whose
 // arrays are the calling wave's own.
@@ -207,40 +208,27 @@ SSR_DEV int ssr_w_rd_paired(const SsrWavePBase& B, int i) {
 // (VT: a view of the plan's twiddle table INCLUDING the lane-ordered copies behind it, SSR_W_N + SSR_W_TWP entries -
 // ssr_tables.h: every load below is one contiguous run of 32 / 64 table entries)
 #define SSR_W_LOAD_TW1 { const unsigned l_ = SSR_UIDX(tid & 31); \
-                         SSR_UNROLL for (int q = 1; q < 8; ++q) R.tw1[q - 1] = VT.at(l_ + (SSR_W_N + 32 * (q - 1))); }
+                         SSR_UNROLL for (int m = 0; m < 3; ++m) R.tw1[m] = VT.at(l_ + (SSR_W_N + 32 * ((1 << m) - 1))); }
 #define SSR_W_LOAD_TW2 { const unsigned l_ = SSR_UIDX(tid & 63); \
                          SSR_UNROLL for (int i = 0; i < 12; ++i) R.tw2[i] = VT.at(l_ + (SSR_W_N + 224 + 64 * i)); }
 #define SSR_W_FFT_TAIL(blk, BLK0, regs, L, EXTRA2)                                                                        \
   SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, SSR_W_EXCHANGE(blk, regs, L, st1, ssr_w_off_st1, ld8, ssr_w_off_ld8, SSR_W_LOAD_TW2 EXTRA2))
 #define SSR_W_FFT_TAIL_PAIRED(blk, BLK0, regs, L)                                                                         \
   SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, SSR_W_EXCHANGE_G(blk, regs, L, st1, ssr_w_off_st1, ssr_wave_pbases, SSR_W_RIDX_PAIRED, SSR_W_LOAD_TW2_PAIRED))
-#define SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, EXCH2)                                                                       \
-  blk = BLK0; ssr_launder(blk);                                                                                     \
-  SSR_W_EXCHANGE(blk, regs, L, st0, ssr_w_off_st0, ld8, ssr_w_off_ld8, SSR_W_LOAD_TW1);                             \
-  /* pass 1: four radix-8 butterflies, twiddles w^(8 (j mod 32) q) - the same seven for every butterfly of the lane */ \
-  SSR_WPHASE(blk, regs, {                                                                                           \
-    SSR_UNROLL for (int b = 0; b < 4; ++b) {                                                                        \
-      SSR_UNROLL for (int q = 1; q < 8; ++q) R.v[8 * b + q] = cmul(R.v[8 * b + q], R.tw1[q - 1]);                   \
-      ssr_bfly8(R.v + 8 * b);                                                                                       \
-    }                                                                                                               \
-  });                                                                                                               \
-  blk = BLK0; ssr_launder(blk);                                                                                     \
-  EXCH2;                                                                                                            \
-  /* pass 2: four radix-8 butterflies, twiddles w^(j q), j = tid + 64 b: three table values + four products each */  \
-  SSR_WPHASE(blk, regs, {                                                                                           \
-    SSR_UNROLL for (int b = 0; b < 4; ++b) {                                                                        \
-      cx<T>* x = R.v + 8 * b;                                                                                       \
-      const cx<T> w1 = R.tw2[3 * b], w2 = R.tw2[3 * b + 1], w4 = R.tw2[3 * b + 2];                                  \
-      x[1] = cmul(x[1], w1);                                                                                        \
-      x[2] = cmul(x[2], w2);                                                                                        \
-      x[4] = cmul(x[4], w4);                                                                                        \
-      const cx<T> w3 = cmul(w1, w2);                                                                                \
-      x[3] = cmul(x[3], w3);                                                                                        \
-      x[5] = cmul(x[5], cmul(w1, w4));                                                                              \
-      x[6] = cmul(x[6], cmul(w2, w4));                                                                              \
-      x[7] = cmul(x[7], cmul(w3, w4));                                                                              \
-      ssr_bfly8(x);                                                                                                 \
-    }                                                                                                               \
+#define SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, EXCH2)                                                                   \
+  blk = BLK0; ssr_launder(blk);                                                                                       \
+  SSR_W_EXCHANGE(blk, regs, L, st0, ssr_w_off_st0, ld8, ssr_w_off_ld8, SSR_W_LOAD_TW1);                               \
+  /* pass 1: four radix-8 butterflies, base twiddle t = w^(8 (j mod 32)) - the same for every butterfly of the lane */\
+  SSR_WPHASE(blk, regs, {                                                                                             \
+    const cx<T> s1_ = ssr_tw_w8(R.tw1[0]);                                                                            \
+    SSR_UNROLL for (int b = 0; b < 4; ++b) ssr_bfly8_tw(R.v + 8 * b, R.tw1[0], R.tw1[1], R.tw1[2], s1_);              \
+  });                                                                                                                 \
+  blk = BLK0; ssr_launder(blk);                                                                                       \
+  EXCH2;                                                                                                              \
+  /* pass 2: four radix-8 butterflies, base twiddle w^j, j = tid + 64 b: three table values each */                   \
+  SSR_WPHASE(blk, regs, {                                                                                             \
+    SSR_UNROLL for (int b = 0; b < 4; ++b)                                                                            \
+      ssr_bfly8_tw(R.v + 8 * b, R.tw2[3 * b], R.tw2[3 * b + 1], R.tw2[3 * b + 2], ssr_tw_w8(R.tw2[3 * b]));           \
   });
 
 // Request unit u's samples into the prefetch registers (branch-free, always valid addresses, reflection only at the ends).

@@ -144,7 +144,7 @@ template <typename T> bool ssr_build_tables_for(int n_fft, SsrEngine eng, SsrTab
   }
   if (N == SSR_WAVE_N) {
     // Lane-ordered copies of the twiddles the wave engines read (ssr_stft_wave.h: SSR_W_LOAD_TW1 / TW2), behind the table:
-    //   [N + 32 (q - 1) + l]          = tw[8 l q],          q = 1..7, l < 32   (pass 1: the lane's seven)
+    //   [N + 32 (q - 1) + l]          = tw[8 l q],          q = 1..7, l < 32   (pass 1 reads q = 1, 2, 4)
     //   [N + 224 + 64 (3 b + k) + l]  = tw[(l + 64 b) 2^k], b < 4, k < 3, l < 64 (pass 2: w^j, w^2j, w^4j of butterfly b)
     // A wave's load of one of them is 512 B / 1 KB contiguous instead of 32 / 64 lines 128..512 B apart.
     t.tw.resize(N + SSR_WAVE_TWP);
