@@ -796,6 +796,7 @@ int ssr_allreduce_sums(double* buf, int n, void* comm, void* stream);
 #include "../ssr_eval_amd/csrc/ssr_hip_loudness.h"
 #include "../ssr_eval_amd/csrc/ssr_hip_spectrum.h"
 #include "../ssr_eval_amd/csrc/ssr_hip_auditory.h"
+#include "../ssr_eval_amd/csrc/ssr_hip_modulation.h"
 
 #ifdef __cplusplus
 }

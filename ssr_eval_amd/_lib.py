@@ -29,6 +29,7 @@ BSS_MAX_TAPS = 512                                                              
 BOOTSTRAP_UTTERANCE, BOOTSTRAP_SPEAKER, BOOTSTRAP_MAX_Q = 0, 1, 8                # SSR_BOOTSTRAP_*
 SPECTRUM_MAX_BANDS = 40                                                         # SSR_SPECTRUM_MAX_BANDS
 AUDITORY_MIN_BANDS, AUDITORY_MAX_BANDS, AUDITORY_MAX_BLOCKS = 3, 64, 65536      # SSR_AUDITORY_MIN_BANDS, _MAX_BANDS, _MAX_BLOCKS
+MODULATION_BANDS, MODULATION_MAX_BLOCKS = 8, 65536                              # SSR_MODULATION_BANDS, SSR_MODULATION_MAX_BLOCKS
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -155,6 +156,12 @@ AUDITORY_SIGNATURES = {
     "ssr_auditory_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i]),
     "ssr_auditory": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
+# name -> (restype, argtypes): exactly the symbols ssr_eval_amd/csrc/ssr_hip_modulation.h declares (include/ssr_hip.h includes it)
+MODULATION_SIGNATURES = {
+    "ssr_modulation_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i]),
+    "ssr_modulation": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _sz,
+                            _vp]),
+}
 
 _lib = None
 
@@ -174,7 +181,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  ssr_eval_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(LOUDNESS_SIGNATURES.items()) + \
-            list(SPECTRUM_SIGNATURES.items()) + list(AUDITORY_SIGNATURES.items()):
+            list(SPECTRUM_SIGNATURES.items()) + list(AUDITORY_SIGNATURES.items()) + list(MODULATION_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -1459,6 +1459,169 @@ def auditory_metrics(tgt_list, est_list, tgt_index, fs, n_bands=AUDITORY_N_BANDS
         return collect if deferred else collect()
 
 
+# ---- modulation: SRMR and the modulation-spectrum distance on §23's filterbank ------------------------------------------------------
+MODULATION_BANDS = 8                     # SSR_MODULATION_BANDS: modulation bands per gammatone band
+MODULATION_Q = 2.0
+MODULATION_ENV_RATE = 1600               # Hz, the envelope rate aimed at
+MODULATION_ENV_RATES = (800, 6400)
+MODULATION_RANGE_DB = 60.0
+MODULATION_MAX_BLOCKS = 65536            # SSR_MODULATION_MAX_BLOCKS: envelope samples per signal
+MODULATION_MAX_STEP = 1024               # SSR_MODULATION_MAX_STEP
+MODULATION_SIGNAL_COLUMNS = 4            # SSR_MODULATION_SIGNAL_COLS: srmr, K*, c90, sum Ebar
+MODULATION_PAIR_COLUMNS = 4              # SSR_MODULATION_PAIR_COLS: srmr_diff, mod_dist, mod_dist_hf, mod_dist_lf
+MODULATION_WORKSPACE_CAP = 1 << 30       # bytes of workspace one ssr_modulation call may ask for: larger batches are split
+
+
+def check_modulation_env_rate(env_rate):
+    """env_rate as it is, or ValueError: a number in MODULATION_ENV_RATES (Hz)."""
+    if isinstance(env_rate, bool) or not isinstance(env_rate, (int, float, np.integer, np.floating)) or \
+            not MODULATION_ENV_RATES[0] <= float(env_rate) <= MODULATION_ENV_RATES[1]:
+        raise ValueError("env_rate must be a number in [%d, %d] Hz" % MODULATION_ENV_RATES)
+    return env_rate
+
+
+def check_modulation_range(range_db):
+    """range_db as a float, or ValueError: a number in (0, 150] (the C ABI's own check)."""
+    return check_auditory_range(range_db)
+
+
+def check_modulation_kstar(kstar):
+    """kstar as it is, or ValueError: None (the adaptive table) or an integer in [5, 8] (the C ABI's own check)."""
+    if kstar is not None and (isinstance(kstar, bool) or not isinstance(kstar, (int, np.integer)) or not 5 <= int(kstar) <= MODULATION_BANDS):
+        raise ValueError("kstar must be None or an integer in [5, %d]" % MODULATION_BANDS)
+    return kstar if kstar is None else int(kstar)
+
+
+def modulation_hop(fs, env_rate=MODULATION_ENV_RATE):
+    """hop_e = max(1, fs // env_rate): the samples of `fs` per envelope sample; the envelope's rate is fs / hop_e."""
+    auditory_hop(fs)
+    return max(1, int(float(fs) // float(check_modulation_env_rate(env_rate))))
+
+
+def modulation_design(fs, hop_e, n_bands=AUDITORY_N_BANDS, band=None, kstar=None):
+    """The two filterbanks of the modulation family at rate fs -> (f_c [n_bands] in Hz, coef [n_bands, 3]: gammatone_design's,
+    mod [8, 5] float64 = (b0, b1, b2, a1, a2) of the modulation band-passes at the envelope rate fe = fs / hop_e, S: the frame step in
+    envelope samples, kstar_table [n_bands] int32).  Modulation band k: centre f_k = 4 * 32^(k / 7) Hz, Q = 2, the bilinear (RBJ)
+    band-pass of unit peak gain: w0 = 2 pi f_k / fe, alpha = sin w0 / (2 Q), b = (alpha, 0, -alpha) / (1 + alpha),
+    a = (1, -2 cos w0 / (1 + alpha), (1 - alpha) / (1 + alpha)).  S = round(0.064 fe) (frames of 4 S).  kstar_table[c]: `kstar` where
+    it is given, else 4 + the number of k in 4 .. 7 whose lower -3 dB edge f_k (sqrt(1 + 1 / (4 Q^2)) - 1 / (2 Q)) lies below
+    ERB(f_c[c]) = 24.7 (1 + 0.00437 f_c[c]), at least 5.  ValueError unless fe >= 400 Hz and S <= MODULATION_MAX_STEP."""
+    fc, coef = gammatone_design(fs, n_bands, band)
+    kstar = check_modulation_kstar(kstar)
+    if isinstance(hop_e, bool) or not isinstance(hop_e, (int, np.integer)) or int(hop_e) < 1:
+        raise ValueError("hop_e must be an integer >= 1")
+    fe = float(fs) / int(hop_e)
+    S = int(math.floor(0.064 * fe + 0.5))
+    if fe < 400.0 or S > MODULATION_MAX_STEP:
+        raise ValueError("the modulation family needs an envelope rate fs / hop_e in [400, 16000] Hz")
+    Q = MODULATION_Q
+    fk = 4.0 * 32.0 ** (np.arange(MODULATION_BANDS) / (MODULATION_BANDS - 1.0))
+    w0 = 2.0 * np.pi * fk / fe
+    alpha = np.sin(w0) / (2.0 * Q)
+    mod = np.stack([alpha / (1.0 + alpha), np.zeros_like(alpha), -alpha / (1.0 + alpha), -2.0 * np.cos(w0) / (1.0 + alpha),
+                    (1.0 - alpha) / (1.0 + alpha)], axis=1)
+    if kstar is None:
+        edge = fk[4:] * (math.sqrt(1.0 + 1.0 / (4.0 * Q * Q)) - 1.0 / (2.0 * Q))
+        erb = 24.7 * (1.0 + 0.00437 * fc)
+        table = np.maximum(4 + np.sum(edge[None, :] < erb[:, None], axis=1), 5)
+    else:
+        table = np.full(len(fc), kstar)
+    return fc, coef, np.ascontiguousarray(mod, dtype=np.float64), S, np.ascontiguousarray(table, dtype=np.int32)
+
+
+def modulation_metrics(tgt_list, est_list, tgt_index, fs, n_bands=AUDITORY_N_BANDS, band=None, env_rate=MODULATION_ENV_RATE,
+                       range_db=MODULATION_RANGE_DB, kstar=None, split_bands=None, return_spectrum=False, hop_e=None, device=None,
+                       deferred=False):
+    """The modulation family (ssr_modulation) on the signals tgt_list + est_list at rate fs, estimate e belonging to target
+    tgt_index[e] and as long as it (float32 or float64 waveforms; a list holding both dtypes is widened to float64) -> (signal
+    [n_tgt + n_est, 4] float64: srmr, K*, c90, sum Ebar of the targets, then of the estimates; pair [n_est, 4]: srmr_diff, mod_dist,
+    mod_dist_hf, mod_dist_lf; spectrum [n_tgt + n_est, n_bands, 8]: Ebar, or None without return_spectrum).  est_list = [] is the
+    non-intrusive call.  split_bands: None, or per estimate the first band of its upper part in [0, n_bands] (-1: no split); hop_e:
+    None = modulation_hop(fs, env_rate), or the samples per envelope sample.  A signal of more than MODULATION_MAX_BLOCKS envelope
+    samples is refused.  The workspace holds about 16 n_bands bytes per envelope sample; a batch that would need more than
+    MODULATION_WORKSPACE_CAP bytes is split into calls of whole targets with their estimates, which changes no bit: a signal gives
+    the same bits in any batch.  Device views of one buffer are read where they lie.  deferred: a function that returns the tuple."""
+    rng_db = check_modulation_range(range_db)
+    hop = modulation_hop(fs, env_rate) if hop_e is None else hop_e
+    _, coef, mod, S, ktab = modulation_design(fs, hop, n_bands, band, kstar)
+    hop = int(hop)
+    C_ = coef.shape[0]
+    if not isinstance(return_spectrum, (bool, np.bool_)):
+        raise ValueError("return_spectrum must be True or False")
+    tgts, ests = list(tgt_list), list(est_list)
+    n_t, n_e = len(tgts), len(ests)
+    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
+    if idx.shape[0] != n_e:
+        raise ValueError("one target index per estimate")
+    if n_e and (idx.min() < 0 or idx.max() >= n_t):
+        raise ValueError("tgt_index out of range")
+    sp = np.full(n_e, -1, np.int32) if split_bands is None else np.asarray(split_bands, dtype=np.int32).reshape(-1)
+    if sp.shape[0] != n_e or (n_e and (sp.min() < -1 or sp.max() > C_)):
+        raise ValueError("split_bands must hold -1 or a band in [0, n_bands] per estimate")
+    require_gpu()
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else default_device()
+    parts = []                                   # (target positions, estimate positions, signal, pair, spectrum) per call
+    with torch.cuda.device(dev):
+        if n_t:
+            if n_e:
+                tgt_side, est_side, tl, el = _placed_where_they_lie(tgts, ests, idx, dev)
+                if not np.array_equal(el, tl[idx]):
+                    raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+            else:
+                f64 = any(_is_f64(w) for w in tgts)
+                data, off, tl = _ragged_where_they_lie(tgts, dev, torch.float64 if f64 else torch.float32)
+                tgt_side, est_side = (data, int(f64), off), (None, 0, None)
+            blocks = np.where(tl >= 2 * hop, tl // hop, 0)
+            if blocks.max() > MODULATION_MAX_BLOCKS:
+                raise ValueError("a signal may hold at most %d blocks of %d samples" % (MODULATION_MAX_BLOCKS, hop))
+            # whole targets with their estimates, in target order, under the cap (a target that exceeds it alone is a call of its own)
+            cost = (blocks + 7) // 8 * 8 * C_ * 16 * (1 + np.bincount(idx, minlength=n_t))
+            cuts, acc = [0], 0
+            for t in range(n_t):
+                if acc and acc + cost[t] > MODULATION_WORKSPACE_CAP:
+                    cuts.append(t)
+                    acc = 0
+                acc += int(cost[t])
+            cuts.append(n_t)
+            ktab_h = _host_i32(ktab, dev)
+            for t0, t1 in zip(cuts[:-1], cuts[1:]):
+                es = np.nonzero((idx >= t0) & (idx < t1))[0]
+                g_t, g_e = t1 - t0, len(es)
+                lens, gidx, gsp = tl[t0:t1].astype(np.int32), (idx[es] - t0).astype(np.int32), sp[es]
+                if g_e and not np.array_equal(es, np.arange(es[0], es[0] + g_e)):
+                    e_off = est_side[2][_h2d(es.astype(np.int64), dev)]
+                else:
+                    e_off = est_side[2][int(es[0]):int(es[0]) + g_e] if g_e else None
+                sig = torch.empty((g_t + g_e, MODULATION_SIGNAL_COLUMNS), dtype=torch.float64, device=dev)
+                pair = torch.empty((g_e, MODULATION_PAIR_COLUMNS), dtype=torch.float64, device=dev)
+                spec = torch.empty((g_t + g_e, C_, MODULATION_BANDS), dtype=torch.float64, device=dev) if return_spectrum else None
+                ws_bytes = int(lib.ssr_modulation_workspace_bytes(lens.ctypes.data_as(C.c_void_p), g_t, gidx.ctypes.data_as(C.c_void_p), g_e, hop, C_))
+                ws = _workspace(ws_bytes, dev)
+                lens_h, idx_h, sp_h = _host_i32(lens, dev), _host_i32(gidx, dev), _host_i32(gsp, dev)
+                # (coef and mod are read by the library before the call returns: its tables of the call are built on the host)
+                _lib.check(lib.ssr_modulation(_vp(tgt_side[0]), tgt_side[1], _vp(tgt_side[2][t0:t1]), _vp(lens_h), g_t,
+                                              _vp(est_side[0]) if g_e else None, est_side[1], _vp(e_off), _vp(idx_h) if g_e else None, g_e,
+                                              hop, C_, coef.ctypes.data_as(C.c_void_p), mod.ctypes.data_as(C.c_void_p), S, _vp(ktab_h), rng_db,
+                                              _vp(sp_h) if g_e else None, _vp(sig), _vp(pair) if g_e else None, _vp(spec), _vp(ws), ws_bytes,
+                                              _stream()))
+                parts.append((np.arange(t0, t1), es, Pending(sig), Pending(pair) if g_e else None, Pending(spec) if return_spectrum else None))
+
+        def collect():
+            signal = np.full((n_t + n_e, MODULATION_SIGNAL_COLUMNS), np.nan)
+            pair = np.full((n_e, MODULATION_PAIR_COLUMNS), np.nan)
+            spectrum = np.full((n_t + n_e, C_, MODULATION_BANDS), np.nan) if return_spectrum else None
+            for ts, es, sig_p, pair_p, spec_p in parts:
+                where = np.concatenate([ts, n_t + es]).astype(np.int64)
+                signal[where] = sig_p()
+                if pair_p is not None:
+                    pair[es] = pair_p()
+                if spec_p is not None:
+                    spectrum[where] = spec_p()
+            return signal, pair, spectrum
+        return collect if deferred else collect()
+
+
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
 PITCH_FS = 16000                 # the rate every signal is tracked at
 PITCH_HOP = 160

@@ -22,7 +22,7 @@ from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
 from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _LOUD_DIFF_NAMES, _LOUD_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
-    _NSIM_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _SPEC_NAMES, _SPEC_PAIR_NAMES, _WAVE_NAMES
+    _MOD_NAMES, _NSIM_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _SPEC_NAMES, _SPEC_PAIR_NAMES, _WAVE_NAMES
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
 
@@ -43,6 +43,9 @@ _LOUD_KEYS = (_LOUD_NAMES[0], _LOUD_DIFF_NAMES[0], _LOUD_NAMES[5], _LOUD_DIFF_NA
 _BW_KEYS = (_SPEC_NAMES[0], _SPEC_PAIR_NAMES[0], _SPEC_PAIR_NAMES[3], _SPEC_PAIR_NAMES[4])
 # of the auditory family a key's result keeps the similarity over all bands and over the bands above the key's cutoff
 _AUD_KEYS = _NSIM_NAMES[:2]
+# of the modulation family a key's result keeps the output's SRMR, its difference to the target's and the modulation-spectrum
+# distance over all bands and over the bands above the key's cutoff
+_MOD_KEYS = _MOD_NAMES[:4]
 
 
 def _option_dict(value):
@@ -282,11 +285,38 @@ def _auditory_check(h, v):
     h.audio_metrics._nsim_splits(fc, split, 1)
 
 
-# The open end of the registry: a new family appends HERE (queued after the two tuples above, its keys behind theirs).
+def _modulation_args(h, v, keys):
+    """-> ((one split frequency per degradation key, n_bands, band, env_rate, range_db, kstar), {"names": the family's keys}): the split
+    is `split` Hz for every key where the option names one, else the key's own cutoff (key_cutoff_hz; None for mp3 keys - NaN
+    mod_dist_hf)."""
+    q = v if isinstance(v, dict) else {}
+    split = [float(q["split"])] * len(keys) if "split" in q else [key_cutoff_hz(k) for k in keys]
+    return ((split, q.get("n_bands", B.AUDITORY_N_BANDS), q.get("band"), q.get("env_rate", B.MODULATION_ENV_RATE),
+             q.get("range_db", B.MODULATION_RANGE_DB), q.get("kstar")), {"names": _MOD_KEYS})
+
+
+def _modulation_check(h, v):
+    if v is not True:
+        if not isinstance(v, dict) or not v or set(v) - {"n_bands", "band", "env_rate", "range_db", "kstar", "split"}:
+            raise ValueError("modulation must be None, True or a dict of 'n_bands', 'band', 'env_rate', 'range_db', 'kstar' and / or 'split'")
+        if "split" in v and (isinstance(v["split"], bool) or not isinstance(v["split"], (int, float, np.integer, np.floating))):
+            raise ValueError("split must be a frequency in Hz (leave it out to split every key at its own cutoff)")
+        if "kstar" in v and v["kstar"] is None:
+            raise ValueError("kstar must be an integer in [5, 8] (leave it out for the adaptive table)")
+    (split, n_bands, band, env_rate, range_db, kstar), _ = _modulation_args(h, v, ["k"])
+    fc, _, _ = h.audio_metrics._modulation_design(n_bands, band, env_rate, range_db, kstar)
+    h.audio_metrics._modulation_splits(fc, split, 1)
+
+
+# The open end of the registry: queued after the two tuples above, its keys behind theirs.  A new family's row goes in BEFORE the
+# `auditory` row, behind the last row in front of it: the tests of the auditory family pin its two keys as the end of
+# full_key_order(), those of the families before it only that each comes after its predecessor.
 _TAIL_FAMILIES = (
     _Family("loudness", "loudness_multi", "loudness_batch", _LOUD_KEYS, _loudness_check, lambda h, keys: ((), {"names": _LOUD_KEYS}), False),
     _Family("bandwidth", "bandwidth_multi", "bandwidth_batch", _BW_KEYS, _bandwidth_check,
             lambda h, keys: _bandwidth_args(h, h.bandwidth, keys), True),
+    _Family("modulation", "modulation_multi", "modulation_batch", _MOD_KEYS, _modulation_check,
+            lambda h, keys: _modulation_args(h, h.modulation, keys), True),
     _Family("auditory", "nsim_multi", "nsim_batch", _AUD_KEYS, _auditory_check, lambda h, keys: _auditory_args(h, h.auditory, keys), True),
 )
 
@@ -372,7 +402,7 @@ class SSR_Eval_Helper:
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
                  quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None,
-                 coherence=None, auditory=None, loudness=None, bandwidth=None):
+                 coherence=None, auditory=None, modulation=None, loudness=None, bandwidth=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -431,6 +461,15 @@ class SSR_Eval_Helper:
         NaN) - invariant to the output's gain (AudioMetrics.nsim_multi / nsim_batch at evaluation_sr); a dict =
         `n_bands` (3 to 64; default 32), `band` ((lo_hz, hi_hz) of the centre frequencies; default 50 Hz to 0.45 evaluation_sr),
         `range_db` (default 60), `split` (the same split frequency in Hz for every key, mp3 included) and / or `match_level`.
+        modulation (not in the reference): None = off; True = every key also gets srmr, the output's speech-to-reverberation
+        modulation energy ratio (Falk, Zheng & Chan 2010; needs no target: high for clean speech, low for reverberation and for
+        stationary texture), srmr_diff, that minus the target's, mod_dist, the RMS difference in dB of the output's and the target's
+        modulation spectra (32 gammatone bands x 8 modulation bands from 4 to 128 Hz), and mod_dist_hf, the same over the bands
+        whose centre frequency is at or above the key's own cutoff (key_cutoff_hz; mp3 keys and keys with no band above the cutoff:
+        NaN) - all invariant to the output's gain (AudioMetrics.modulation_multi / modulation_batch at evaluation_sr, DESIGN.md
+        section 24); a dict = `n_bands` (3 to 64; default 32), `band` ((lo_hz, hi_hz) of the centre frequencies), `env_rate` (800 to
+        6400 Hz; default 1600), `range_db` (default 60), `kstar` (5 .. 8: a constant upper band instead of the adaptive one) and / or
+        `split` (the same split frequency in Hz for every key, mp3 included).
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -447,7 +486,7 @@ class SSR_Eval_Helper:
         # every family option is checked here, before the caller's settings are touched (the mel checks need audio_metrics)
         options = dict(lsd_split=lsd_split, stoi=stoi, waveform=waveform, mel=mel, mel_dtw=mel_dtw, quality=quality, pitch=pitch,
                        phase=phase, mrstft=mrstft, bss_sdr=bss_sdr, coherence=coherence, loudness=loudness,
-                       bandwidth=bandwidth, auditory=auditory)
+                       bandwidth=bandwidth, auditory=auditory, modulation=modulation)
         for f in _FAMILIES + _LATER_FAMILIES + _TAIL_FAMILIES:
             if options[f.option] is not None:
                 f.check(self, options[f.option])

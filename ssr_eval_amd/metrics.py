@@ -38,6 +38,7 @@ _LOUD_DIFF_NAMES = ("lufs_diff", "lra_diff", "true_peak_diff")                  
 _SPEC_NAMES = ("bw_hz", "edge_hz", "centroid_hz", "hf_db")                                # of one signal (ssr_spectrum)
 _SPEC_PAIR_NAMES = ("bw_diff", "edge_diff", "centroid_diff", "hf_diff", "ltas_dist", "ltas_max")     # estimate against target
 _NSIM_NAMES = ("nsim", "nsim_hf", "nsim_lf")                                              # the columns of ssr_auditory
+_MOD_NAMES = ("srmr", "srmr_diff", "mod_dist", "mod_dist_hf", "mod_dist_lf")              # the estimate's srmr, then ssr_modulation's pair columns
 
 
 def which_mask(which, names):
@@ -1079,6 +1080,120 @@ class AudioMetrics:
         _, _, images = B.auditory_metrics([self._loudness_signal(wav)], [], [], self.rate, n_bands, band, range_db, True, None, False, True,
                                           None, self._device)
         return images[0], np.array(fc)
+
+    # ---- modulation: does a signal move like speech?  The envelopes of §23's gammatone bands, at about env_rate Hz,
+    # through eight modulation band-passes from 4 to 128 Hz; 256 ms Hamming frames every 64 ms; the mean frame energy per (band,
+    # modulation band) is the modulation spectrum.  SRMR (Falk, Zheng & Chan 2010) is its energy below 20 Hz over that above, and it
+    # needs no target; mod_dist is the RMS difference in dB of two such spectra
+    @staticmethod
+    def _modulation_names(names):
+        """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
+        if names is None:
+            return _MOD_NAMES
+        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(k, str) and k in _MOD_NAMES for k in names):
+            raise ValueError("names must be None or a tuple of %s" % (_MOD_NAMES,))
+        return tuple(k for k in _MOD_NAMES if k in names)
+
+    @staticmethod
+    def _modulation_splits(fc, split, n):
+        """The first band whose centre frequency is at or above the split of n pairs, in [0, len(fc)]: split = None (no split: -1 for
+        every pair), one frequency in Hz for every pair, or a list of one per pair (None: -1 for that pair)."""
+        per_pair = isinstance(split, list)
+        splits = split if per_pair else [split] * n
+        if len(splits) != n:
+            raise ValueError("one split frequency per pair")
+        out = []
+        for s in splits:
+            if s is None and (per_pair or split is None):
+                out.append(-1)
+                continue
+            if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= float(s) < math.inf:
+                raise ValueError("a split frequency is a finite number >= 0 in Hz")
+            out.append(int(np.searchsorted(fc, float(s), side="left")))
+        return out
+
+    def _modulation_design(self, n_bands, band, env_rate, range_db, kstar):
+        """-> (f_c, the modulation centres in Hz, range_db as a float): every option checked, nothing queued."""
+        fc = B.modulation_design(self.rate, B.modulation_hop(self.rate, env_rate), n_bands, band, kstar)[0]
+        return fc, 4.0 * 32.0 ** (np.arange(B.MODULATION_BANDS) / (B.MODULATION_BANDS - 1.0)), B.check_modulation_range(range_db)
+
+    def srmr(self, wav, n_bands=B.AUDITORY_N_BANDS, band=None, env_rate=B.MODULATION_ENV_RATE, kstar=None, return_spectrum=False):
+        """{'srmr', 'kstar', 'c90'} of one signal at self.rate, without a target: the speech-to-reverberation modulation energy ratio
+        (Falk, Zheng & Chan 2010) - the energy of the sub-band envelopes in the four modulation bands from 4 to about 18 Hz over
+        that in the bands from about 29 Hz up to the K*-th, K* = 5 .. 8 chosen from the gammatone band c90 below which 90 % of the
+        modulation energy lies (or the constant `kstar`).  Clean, dry speech scores high; reverberation and stationary texture
+        score low.  n_bands, band: the gammatone filterbank of nsim(); env_rate: the envelope is sampled at about this rate
+        (self.rate / (self.rate // env_rate)), 800 to 6400 Hz.  return_spectrum: also 'mod_spectrum' [n_bands, 8], the mean frame
+        energy per (band, modulation band), 'centre_hz' and 'mod_hz'.  Shorter than one 256 ms frame, digitally silent, or no
+        energy above 20 Hz: NaN (kstar and c90: -1)."""
+        fc, fk, _ = self._modulation_design(n_bands, band, env_rate, B.MODULATION_RANGE_DB, kstar)
+        if not isinstance(return_spectrum, bool):
+            raise ValueError("return_spectrum must be True or False")
+        sig, _, spec = B.modulation_metrics([self._loudness_signal(wav)], [], [], self.rate, n_bands, band, env_rate, B.MODULATION_RANGE_DB,
+                                            kstar, None, return_spectrum, None, self._device)
+        whole = lambda v: -1 if math.isnan(v) else int(v)      # noqa: E731
+        d = {"srmr": float(sig[0, 0]), "kstar": whole(sig[0, 1]), "c90": whole(sig[0, 2])}
+        if return_spectrum:
+            d["mod_spectrum"], d["centre_hz"], d["mod_hz"] = np.array(spec[0]), np.array(fc), fk
+        return d
+
+    def modulation(self, est, target, split_hz=None, n_bands=B.AUDITORY_N_BANDS, band=None, env_rate=B.MODULATION_ENV_RATE,
+                   range_db=B.MODULATION_RANGE_DB, kstar=None, names=None, return_spectrum=False):
+        """{'srmr', 'srmr_diff', 'mod_dist', 'mod_dist_hf', 'mod_dist_lf'} of one (estimate, target) pair at self.rate: the estimate's
+        srmr(), that minus the target's, and the RMS difference in dB of the two modulation spectra - the estimate's scaled to the
+        target's total first, so that the value is invariant to gain, both clamped range_db below the target's largest cell - over
+        all cells, and over the gammatone bands whose centre frequency is at / above and below split_hz (NaN without split_hz or
+        where no such band exists).  n_bands, band, env_rate, kstar: as srmr().  names: None, or the result keys wanted.
+        return_spectrum: also 'mod_spectrum' and 'target_mod_spectrum' [n_bands, 8], 'centre_hz' and 'mod_hz'.  A target shorter
+        than one 256 ms frame or digitally silent, or a silent estimate: NaN."""
+        return self.modulation_batch([est], [target], split_hz, n_bands, band, env_rate, range_db, kstar, names, return_spectrum)[0]
+
+    def modulation_batch(self, ests, targets, split_hz=None, n_bands=B.AUDITORY_N_BANDS, band=None, env_rate=B.MODULATION_ENV_RATE,
+                         range_db=B.MODULATION_RANGE_DB, kstar=None, names=None, return_spectrum=False, resident=False, deferred=False):
+        """modulation() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals,
+        read in their own dtype: one ssr_modulation call per (target dtype, estimate dtype) group, split further where its workspace
+        would pass backend.MODULATION_WORKSPACE_CAP).  A target object passed for several pairs is filtered once.  split_hz: None,
+        one frequency for every pair, or a list of one per pair (None: that pair's mod_dist_hf and mod_dist_lf are NaN).
+        deferred: as evaluation_batch."""
+        fc, fk, rng_db = self._modulation_design(n_bands, band, env_rate, range_db, kstar)
+        if not isinstance(return_spectrum, bool):
+            raise ValueError("return_spectrum must be True or False")
+        keys = self._modulation_names(names)
+        n = min(len(ests), len(targets))
+        splits = self._modulation_splits(fc, split_hz, n)
+
+        def call(tgts, es, index, idx):
+            got = B.modulation_metrics(tgts, es, index, self.rate, n_bands, band, env_rate, rng_db, kstar, [splits[i] for i in idx],
+                                       return_spectrum, None, self._device, deferred=True)
+            return lambda: got() + (len(tgts), index)
+
+        def dicts(vals):
+            sig, pair, spec, n_t, index = vals
+            out = []
+            for j, row in enumerate(pair):
+                d = {k: float(v) for k, v in zip(_MOD_NAMES, (sig[n_t + j, 0],) + tuple(row)) if k in keys}
+                if return_spectrum:
+                    d["mod_spectrum"], d["target_mod_spectrum"] = np.array(spec[n_t + j]), np.array(spec[index[j]])
+                    d["centre_hz"], d["mod_hz"] = np.array(fc), np.array(fk)
+                out.append(d)
+            return out
+        for w in list(ests[:n]) + list(targets[:n]):
+            if not isinstance(w, str) and len(w.shape) != 1:
+                raise ValueError("expected a 1-D signal, got shape %s" % (tuple(w.shape),))
+        return self._pairs((call, dicts), ests[:n], targets[:n], resident, deferred, by_dtype=True, per_pair=True)
+
+    def modulation_multi(self, ests_by_key, targets, split_hz=None, n_bands=B.AUDITORY_N_BANDS, band=None, env_rate=B.MODULATION_ENV_RATE,
+                         range_db=B.MODULATION_RANGE_DB, kstar=None, names=None, return_spectrum=False, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
+        to each other in one call and the target is filtered once."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        if isinstance(split_hz, list):
+            if len(split_hz) != K:
+                raise ValueError("one split frequency per key")
+            split_hz = list(split_hz) * n
+        return _regroup(self.modulation_batch(ests, tgts, split_hz, n_bands, band, env_rate, range_db, kstar, names, return_spectrum, resident,
+                                              True), n, K, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
