@@ -9,6 +9,7 @@ from .metrics import AudioMetrics  # noqa: F401
 from .dsp import FDomainHelper  # noqa: F401
 from .lowpass import lowpass, bandpass  # noqa: F401
 from .stats import bootstrap_ci, compare_results  # noqa: F401
+from .distribution import frechet_distance, kernel_distance, distribution_distance, embed_logmel_stats  # noqa: F401
 
 __version__ = "0.1.0"
 

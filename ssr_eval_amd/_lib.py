@@ -30,6 +30,8 @@ BOOTSTRAP_UTTERANCE, BOOTSTRAP_SPEAKER, BOOTSTRAP_MAX_Q = 0, 1, 8               
 SPECTRUM_MAX_BANDS = 40                                                         # SSR_SPECTRUM_MAX_BANDS
 AUDITORY_MIN_BANDS, AUDITORY_MAX_BANDS, AUDITORY_MAX_BLOCKS = 3, 64, 65536      # SSR_AUDITORY_MIN_BANDS, _MAX_BANDS, _MAX_BLOCKS
 MODULATION_BANDS, MODULATION_MAX_BLOCKS = 8, 65536                              # SSR_MODULATION_BANDS, SSR_MODULATION_MAX_BLOCKS
+DISTRIBUTION_MAX_DIM, DISTRIBUTION_MAX_GAMMA, DISTRIBUTION_MAX_PAIR_ROWS = 1024, 8, 2048   # SSR_DISTRIBUTION_MAX_DIM, _MAX_GAMMA, _MAX_PAIR_ROWS
+DISTRIBUTION_PAIRWISE_WORKSPACE = 16640                                         # SSR_DISTRIBUTION_PAIRWISE_WORKSPACE
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -162,6 +164,14 @@ MODULATION_SIGNATURES = {
     "ssr_modulation": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _sz,
                             _vp]),
 }
+# name -> (restype, argtypes): exactly the symbols ssr_eval_amd/csrc/ssr_hip_distribution.h declares (include/ssr_hip.h includes it)
+DISTRIBUTION_SIGNATURES = {
+    "ssr_frechet_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "ssr_frechet": (_i, [_vp, _i, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ssr_kernel_distance_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "ssr_kernel_distance": (_i, [_vp, _i, _vp, _vp, _i, _i, _i64, _vp, _i, C.c_double, _vp, _vp, _sz, _vp]),
+    "ssr_pairwise_distances": (_i, [_vp, _i, _i64, _i64, _i, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
+}
 
 _lib = None
 
@@ -181,7 +191,8 @@ def load():
             "(hipcc --offload-arch=gfx950).  ssr_eval_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(LOUDNESS_SIGNATURES.items()) + \
-            list(SPECTRUM_SIGNATURES.items()) + list(AUDITORY_SIGNATURES.items()) + list(MODULATION_SIGNATURES.items()):
+            list(SPECTRUM_SIGNATURES.items()) + list(AUDITORY_SIGNATURES.items()) + list(MODULATION_SIGNATURES.items()) + \
+            list(DISTRIBUTION_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

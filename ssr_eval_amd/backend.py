@@ -1622,6 +1622,141 @@ def modulation_metrics(tgt_list, est_list, tgt_index, fs, n_bands=AUDITORY_N_BAN
         return collect if deferred else collect()
 
 
+# ---- distribution: Fréchet and kernel distance of embedding sets ---------------------------------------------------------
+DISTRIBUTION_MAX_DIM = 1024              # SSR_DISTRIBUTION_MAX_DIM
+DISTRIBUTION_MAX_GAMMA = 8               # SSR_DISTRIBUTION_MAX_GAMMA
+DISTRIBUTION_MAX_PAIR_ROWS = 2048        # SSR_DISTRIBUTION_MAX_PAIR_ROWS
+DISTRIBUTION_MAX_SWEEPS = 60             # the default bound of the Jacobi's sweep loop
+FRECHET_COLUMNS = 8                      # SSR_FRECHET_COLS: fd, |dmu|^2, tr Sigma_r, tr Sigma_e, tr_sqrt, sweeps_ref, sweeps_est, rank_ref
+KERNEL_DISTANCE_COLUMNS = 4              # SSR_KERNEL_DISTANCE_COLS: kd, mmd2, mean k(r, r), mean k(e, e)
+
+
+def check_distribution_max_sweeps(max_sweeps):
+    """max_sweeps as an int, or ValueError: a whole number in [1, 200] (the C ABI's own check)."""
+    if isinstance(max_sweeps, (bool, np.bool_)) or not isinstance(max_sweeps, (int, np.integer)) or not 1 <= max_sweeps <= 200:
+        raise ValueError("max_sweeps must be a whole number in [1, 200]")
+    return int(max_sweeps)
+
+
+def check_distribution_gammas(gammas):
+    """The kernel bandwidths as a float64 array, or ValueError: 1 to 8 finite values > 0."""
+    try:
+        if isinstance(gammas, (str, bytes)):
+            raise TypeError
+        g = np.ascontiguousarray(gammas, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("gamma must hold 1 to 8 finite values > 0")
+    if not 1 <= g.shape[0] <= DISTRIBUTION_MAX_GAMMA or not np.all(np.isfinite(g) & (g > 0.0)):
+        raise ValueError("gamma must hold 1 to 8 finite values > 0")
+    return g
+
+
+def check_distribution_scale(scale):
+    if isinstance(scale, (bool, np.bool_)) or not isinstance(scale, (int, float, np.integer, np.floating)) or not math.isfinite(scale):
+        raise ValueError("scale must be a finite number")
+    return float(scale)
+
+
+def _embedding_set(s, what):
+    """A set of embeddings as a 2-D float32 / float64 tensor (wherever it lives), or ValueError."""
+    t = s if isinstance(s, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(s))
+    if t.dim() != 2 or t.dtype not in (torch.float32, torch.float64):
+        raise ValueError("%s must be a 2-D float32 or float64 array [rows, D]" % what)
+    if not 1 <= t.shape[1] <= DISTRIBUTION_MAX_DIM:
+        raise ValueError("%s must have 1 <= D <= %d columns" % (what, DISTRIBUTION_MAX_DIM))
+    return t
+
+
+def _distribution_sets(ref, ests):
+    """The reference and the estimate sets checked -> (tensors, D); nothing touches a device."""
+    if isinstance(ests, (torch.Tensor, np.ndarray)):
+        raise ValueError("ests must be a list of sets")
+    ts = [_embedding_set(ref, "ref")] + [_embedding_set(e, "every estimate set") for e in ests]
+    if len(ts) < 2:
+        raise ValueError("at least one estimate set")
+    if any(t.shape[1] != ts[0].shape[1] for t in ts):
+        raise ValueError("every set must have the reference's D")
+    return ts, int(ts[0].shape[1])
+
+
+def _distribution_pack(ts, dev):
+    """The sets back to back in one device buffer of their widest dtype -> (data, is-float64, element offsets int64, rows int64)."""
+    dt = torch.float64 if any(t.dtype == torch.float64 for t in ts) else torch.float32
+    data = torch.cat([t.to(device=dev, dtype=dt) for t in ts], dim=0).contiguous()
+    rows = np.array([t.shape[0] for t in ts], np.int64)
+    return data, int(dt == torch.float64), (np.cumsum(rows) - rows) * int(ts[0].shape[1]), rows
+
+
+def frechet_stats(ref, ests, max_sweeps=DISTRIBUTION_MAX_SWEEPS, return_moments=False, device=None):
+    """ssr_frechet on the reference set ref [n, D] and the list of estimate sets ests (each [m_k, D]); torch tensors or
+    NumPy arrays, float32 or float64 (mixed: widened to float64), resident or host -> out [K, 8] float64 = fd, |mu_r - mu_e|^2,
+    tr Sigma_r, tr Sigma_e, tr sqrt(Sigma_r Sigma_e), sweeps_ref, sweeps_est, rank_ref; with return_moments (out, moments [1 + K, D + D D]:
+    mean and row-major covariance of every set)."""
+    ts, D = _distribution_sets(ref, ests)
+    max_sweeps = check_distribution_max_sweeps(max_sweeps)
+    require_gpu()
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else default_device()
+    K = len(ts) - 1
+    with torch.cuda.device(dev):
+        data, f64, off, rows = _distribution_pack(ts, dev)
+        out = torch.empty((K, FRECHET_COLUMNS), dtype=torch.float64, device=dev)
+        mom = torch.empty((K + 1, D + D * D), dtype=torch.float64, device=dev) if return_moments else None
+        ws_bytes = int(lib.ssr_frechet_workspace_bytes(rows.ctypes.data_as(C.c_void_p), K, D))
+        if ws_bytes == 0:
+            raise SsrHipError("sets too large for one ssr_frechet call")
+        ws = _workspace(ws_bytes, dev)
+        _lib.check(lib.ssr_frechet(_vp(data), f64, off.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p), K, D, D, max_sweeps,
+                                   _vp(out), _vp(mom), _vp(ws), ws_bytes, _stream()))
+        res = out.cpu().numpy()
+        return (res, mom.cpu().numpy()) if return_moments else res
+
+
+def kernel_sums(ref, ests, gammas, scale=1000.0, device=None):
+    """ssr_kernel_distance: the unbiased MMD^2 with the Gaussian kernels exp(-gamma |x - y|^2) of the reference set and
+    every estimate set (inputs as frechet_stats takes them; gammas: 1 to 8 values) -> [K, n_gamma, 4] float64 = kd = scale mmd2, mmd2,
+    mean k(r, r), mean k(e, e)."""
+    ts, D = _distribution_sets(ref, ests)
+    g = check_distribution_gammas(gammas)
+    scale = check_distribution_scale(scale)
+    require_gpu()
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else default_device()
+    K = len(ts) - 1
+    with torch.cuda.device(dev):
+        data, f64, off, rows = _distribution_pack(ts, dev)
+        out = torch.empty((K, len(g), KERNEL_DISTANCE_COLUMNS), dtype=torch.float64, device=dev)
+        ws_bytes = int(lib.ssr_kernel_distance_workspace_bytes(rows.ctypes.data_as(C.c_void_p), K, D, len(g)))
+        if ws_bytes == 0:
+            raise SsrHipError("sets too large for one ssr_kernel_distance call")
+        ws = _workspace(ws_bytes, dev)
+        _lib.check(lib.ssr_kernel_distance(_vp(data), f64, off.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p), K, D, D,
+                                           g.ctypes.data_as(C.c_void_p), len(g), scale, _vp(out), _vp(ws), ws_bytes, _stream()))
+        return out.cpu().numpy()
+
+
+def pairwise_distances(x, index=None, device=None, as_tensor=False):
+    """ssr_pairwise_distances: |x_i - x_j|, i < j, of the rows index (default: all; at most 2048) of the set x [rows, D] -> float64
+    [n (n - 1) / 2] in row-major order of the upper triangle, as an ndarray or (as_tensor) a device tensor."""
+    t = _embedding_set(x, "x")
+    idx = np.arange(t.shape[0], dtype=np.int64) if index is None else np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+    n = len(idx)
+    if n > DISTRIBUTION_MAX_PAIR_ROWS:
+        raise ValueError("at most %d rows" % DISTRIBUTION_MAX_PAIR_ROWS)
+    if n and (idx.min() < 0 or idx.max() >= t.shape[0]):
+        raise ValueError("index out of range")
+    require_gpu()
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else default_device()
+    with torch.cuda.device(dev):
+        data = t.to(dev).contiguous()
+        out = torch.empty(n * (n - 1) // 2, dtype=torch.float64, device=dev)
+        ws = _workspace(_lib.DISTRIBUTION_PAIRWISE_WORKSPACE, dev)
+        _lib.check(lib.ssr_pairwise_distances(_vp(data), int(t.dtype == torch.float64), 0, t.shape[0], t.shape[1], t.shape[1],
+                                              idx.ctypes.data_as(C.c_void_p), n, _vp(out), _vp(ws), _lib.DISTRIBUTION_PAIRWISE_WORKSPACE, _stream()))
+        return out if as_tensor else out.cpu().numpy()
+
+
 # ---- pitch: YIN F0 tracks, F0 RMSE, F0 correlation, GPE, VDE and FFE ------------------------------------------------------------
 PITCH_FS = 16000                 # the rate every signal is tracked at
 PITCH_HOP = 160

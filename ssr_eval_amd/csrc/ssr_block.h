@@ -38,6 +38,7 @@ static inline unsigned ssr_launder_index(unsigned i) { return i; }
     __VA_ARGS__;                                                   \
   }
 #define SSR_WPHASE SSR_PHASE
+#define SSR_PHASE_GLOBAL SSR_PHASE
 // inside a phase: dst[tid / 64] = sum of `val` over the lanes of that wave (host: tids run in ascending order)
 #define SSR_WAVE_SUM_STORE(tid, NT_, val, dst)              \
   do {                                                      \
@@ -112,6 +113,15 @@ SSR_DEV unsigned ssr_launder_index(unsigned i) { asm volatile("" : "+v"(i)); ret
     __VA_ARGS__;                                                   \
   }                                                                \
   SSR_BARRIER();
+// Phase of a body whose waves hand data to each other through GLOBAL memory (ssr_distribution.h's Jacobi passes columns from wave to
+// wave that way): the boundary is __syncthreads(), a workgroup barrier that drains the wave's outstanding global accesses and orders
+// global stores and loads of the workgroup as well as its LDS traffic.  SSR_PHASE's barrier does not.
+#define SSR_PHASE_GLOBAL(blk, regs, ...)                           \
+  {                                                                \
+    const int tid = (blk).tid; auto& R = (regs); (void)R; (void)tid; \
+    __VA_ARGS__;                                                   \
+  }                                                                \
+  __syncthreads();
 // Phase of a body whose hand-offs stay inside ONE wave (one-wave workgroups, or per-wave LDS arrays): a wave-scope ordering
 // point - it constrains the compiler and emits nothing (same-wave LDS traffic is ordered by the hardware), where SSR_PHASE's
 // workgroup fence costs an s_waitcnt lgkmcnt(0) per boundary.

@@ -23,6 +23,7 @@ from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
 from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _LOUD_DIFF_NAMES, _LOUD_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
     _MOD_NAMES, _NSIM_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _SPEC_NAMES, _SPEC_PAIR_NAMES, _WAVE_NAMES
+from .distribution import check_option as check_distribution_option, embed_waves, result_block as distribution_block
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
 
@@ -402,7 +403,7 @@ class SSR_Eval_Helper:
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
                  quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None,
-                 coherence=None, auditory=None, modulation=None, loudness=None, bandwidth=None):
+                 distribution=None, coherence=None, auditory=None, modulation=None, loudness=None, bandwidth=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -436,6 +437,14 @@ class SSR_Eval_Helper:
         512-tap FIR filter of the target as the allowed distortion - a delay or a colouring of the output costs nothing - and the
         tap of that filter's largest coefficient, the output's latency in samples (AudioMetrics.bss_sdr_multi / bss_sdr_batch at
         evaluation_sr); a dict = `taps` (1 .. 512).
+        distribution (not in the reference): None = off, the result, its JSON and the launch sequence are what they are without the
+        option; True = evaluate() adds result["distribution"] = {"settings": {...}, "dim": D, "n": files, "per_key": {key: {"fd", "kd"}}},
+        the Fréchet distance and the kernel distance (unbiased MMD^2 x 1000) between the SET of a key's outputs and the set of
+        targets (ssr_eval_amd.distribution) - corpus-level, not per file: per-file entries, each_speaker,
+        averaged and confidence are unchanged to the bit.  Each file contributes one embedding vector for its target and one per
+        key: the built-in log-mel statistics (distribution.embed_logmel_stats; fd on it is NOT comparable with published VGGish /
+        CLAP FAD figures), or a dict's `embed`: a callable (waves: list of 1-D tensors at evaluation_sr, sr) -> [len(waves), D];
+        further dict keys: `bandwidth` ("median" or the kernel's sigma), `scale`, `max_sweeps`, `metrics` (a subset of ("fd", "kd")).
         coherence (not in the reference): None = off; True = every key also gets msc / coh_sdr / coh_bw, the mean Welch-averaged
         magnitude-squared coherence of the output with the target, the power of the output that is a linear function of the target
         over the power that is not, in dB, and the width in Hz of the bins with a coherence of at least 0.5 - and msc_hf /
@@ -478,6 +487,8 @@ class SSR_Eval_Helper:
         result["confidence"] = {"settings": {...}, "averaged": {key: {metric: {"se", "lo", "hi"}}}}, the percentile bootstrap of the
         "averaged" block (ssr_eval_amd.stats.bootstrap_ci)."""
         self.bootstrap = None if bootstrap is None else bootstrap_option(bootstrap)
+        self.distribution = None if distribution is None else check_distribution_option(distribution)
+        self._last_embeddings = None
         if not isinstance(iir_exact, bool):
             raise ValueError("iir_exact must be True or False")
         self.iir_exact = iir_exact
@@ -807,6 +818,15 @@ class SSR_Eval_Helper:
                 else:
                     args, kw = f.arguments(self, all_keys)
                     queued.append(getattr(self.audio_metrics, f.batch)(all_proc, all_tgt, *args, resident=True, deferred=True, **kw))
+        # the distribution option: one embedding per target (once per file) and one per (file, key), queued behind the families
+        embedded = None
+        if self.distribution is not None and all_proc:
+            first = {}
+            for j, i in enumerate(owner):
+                first.setdefault(i, j)
+            waves = [all_tgt[first[i]] for i in sorted(first)] + list(all_proc)
+            waves = [w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w)) for w in waves]
+            embedded = (sorted(first), embed_waves(self.distribution, self.audio_metrics, waves, self.evaluationset_sr))
         self._last_processed = None
         keep = list(zip(owner, all_keys, all_proc)) if self.save_processed_result else None
 
@@ -823,6 +843,16 @@ class SSR_Eval_Helper:
                     results[i][k] = v
             if keep is not None:
                 self._last_processed = {(i, k): (y.cpu().numpy() if isinstance(y, torch.Tensor) else y) for i, k, y in keep}
+            if self.distribution is not None:
+                # per item: {"": the target's vector, key: the output's}
+                rows = [dict() for _ in items]
+                if embedded is not None:
+                    have, e = embedded
+                    for n_, i in enumerate(have):
+                        rows[i][""] = e[n_]
+                    for j, (i, k) in enumerate(zip(owner, all_keys)):
+                        rows[i][k] = e[len(have) + j]
+                self._last_embeddings = rows
             return results
         return finish if deferred else finish()
 
@@ -927,7 +957,7 @@ class SSR_Eval_Helper:
         else:
             mine = D.shard_indices(len(work), rank, world)
         paths = [os.path.join(self.test_data_root, *work[i]) for i in mine]
-        local = []
+        local, local_emb = [], []
         step = max(1, int(batch_files if batch_files is not None else self.default_batch_files()))   # files per launch sequence
         batches = pipeline_batches(paths, step)
         # the file reads of batch k+1 (straight into a page-locked arena) run under the GPU work of batch k
@@ -945,12 +975,20 @@ class SSR_Eval_Helper:
             ahead = decode_packed_async(batches[k + 1], self._device) if k + 1 < len(batches) else None
             if collect is not None:
                 local += collect()
+                local_emb += self._last_embeddings or []
             collect = queued
         if collect is not None:
             local += collect()
-        return self._assemble(work, speakers, mine, local, save_json, datetime.now())
+            local_emb += self._last_embeddings or []
+        return self._assemble(work, speakers, mine, local, save_json, datetime.now(), local_emb if self.distribution is not None else None)
 
-    def _assemble(self, work, speakers, mine, local, save_json, now):
+    def _gather_embeddings(self, local_emb, keys, mine, n_total, gather=None):
+        """The rank's embedding rows (per file: {"": target, key: output}) -> the table [n_total, (1 + len(keys)) D] every rank holds."""
+        rows = np.array([np.concatenate([r[""]] + [r[k] for k in keys]) for r in local_emb], dtype=np.float64) if local_emb and keys \
+            else np.empty((0, 0), dtype=np.float64)
+        return (gather or D.allgather_rows)(rows, mine, n_total)
+
+    def _assemble(self, work, speakers, mine, local, save_json, now, local_emb=None):
         # Key order of the reference = insertion order of preprocess() (eval.py:243-269); metric order = the four
         # AudioMetrics keys, then whatever the testee added.  A rank that owns no file (world_size > number of files) has
         # neither, so the lists are agreed on across ranks: the first rank that has results defines the order.
@@ -1006,6 +1044,10 @@ class SSR_Eval_Helper:
                                                                                       for n in ("se", "lo", "hi")))}
                         for i, k in enumerate(keys)}
             final_result["confidence"] = {"settings": dict(self.bootstrap), "averaged": conf}
+        if local_emb is not None:
+            # one more collective, only with the option on: the embedding rows travel with the file's global index; every rank then
+            # holds the same table and computes the same bits
+            final_result["distribution"] = distribution_block(self.distribution, keys, self._gather_embeddings(local_emb, keys, mine, len(work)))
         if save_json and rank == 0:
             os.makedirs("results", exist_ok=True)
             write_json(final_result, os.path.join("results", str(now.date()) + "-" + str(now.time()) + "-"

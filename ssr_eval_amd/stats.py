@@ -13,7 +13,7 @@ from . import backend as B
 
 RESAMPLE = ("utterance", "speaker")
 # what evaluate() adds to a result beside the speakers
-_AGGREGATE_KEYS = ("each_speaker", "averaged", "confidence")
+_AGGREGATE_KEYS = ("each_speaker", "averaged", "confidence", "distribution")
 
 
 def check_settings(n_boot=2000, level=0.95, seed=0, resample="utterance"):
