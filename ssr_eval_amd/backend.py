@@ -321,6 +321,18 @@ def _is_f64(a):
     return (a.dtype == torch.float64) if isinstance(a, torch.Tensor) else (getattr(a, "dtype", None) == np.float64)
 
 
+def _is_number(x):
+    """A Python or NumPy real number; a bool is none."""
+    return not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating))
+
+
+def _number_in(x, lo, hi, lo_open, hi_open, message):
+    """x as it is, or ValueError(message): a number (_is_number; NaN is outside) between lo and hi, either end open or closed."""
+    if not _is_number(x) or not (lo < float(x) if lo_open else lo <= float(x)) or not (float(x) < hi if hi_open else float(x) <= hi):
+        raise ValueError(message)
+    return x
+
+
 class Ragged:
     """A ragged batch of 1-D signals resident on the device: float32, or float64 where the reference would hold
     float64 (IIR-degraded / resampled-from-float64 estimates)."""
@@ -883,18 +895,80 @@ def _ragged_where_they_lie(arrays, dev, dtype):
 def _placed_where_they_lie(tgts, ests, idx, dev):
     """The signals as ssr_wave_metrics / ssr_quality_metrics take them - (data, is-float64 flag, offsets) per side, read in their own
     dtype (a list holding both dtypes is widened to float64) -> (target side, estimate side, target lengths, estimate lengths)."""
-    sides = []
-    for wavs in (tgts, ests):
-        f64 = any(_is_f64(w) for w in wavs)
-        data, off, lens = _ragged_where_they_lie(wavs, dev, torch.float64 if f64 else torch.float32)
-        sides.append(((data, int(f64), off), lens))
-    return sides[0][0], sides[1][0], sides[0][1], sides[1][1]
+    (tgt_side, tl), (est_side, el) = _placed_signals(tgts, dev), _placed_signals(ests, dev)
+    return tgt_side, est_side, tl, el
+
+
+def _placed_signals(wavs, dev):
+    """One list of signals as _placed_where_they_lie places a side -> ((data, is-float64 flag, offsets), lengths)."""
+    f64 = any(_is_f64(w) for w in wavs)
+    data, off, lens = _ragged_where_they_lie(wavs, dev, torch.float64 if f64 else torch.float32)
+    return (data, int(f64), off), lens
 
 
 def _placed_resampled(r, n_t):
     """The signals as ssr_stoi / ssr_f0_metrics take them - (data, offsets) per side of ONE float64 batch r that holds the n_t
     targets, then the estimates (resampled together, in one launch) -> as _placed_where_they_lie."""
     return (r.data, r.off), (r.data, r.off[n_t:]), r.lens_host[:n_t], r.lens_host[n_t:]
+
+
+def _signal_pair_index(tgt_list, est_list, tgt_index):
+    """What a call on n_tgt targets and n_est >= 0 estimates checks before it needs a device -> (targets, estimates, tgt_index as
+    int32 [n_est]), or ValueError."""
+    tgts, ests = list(tgt_list), list(est_list)
+    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
+    if idx.shape[0] != len(ests):
+        raise ValueError("one target index per estimate")
+    if len(ests) and (idx.min() < 0 or idx.max() >= len(tgts)):
+        raise ValueError("tgt_index out of range")
+    return tgts, ests, idx
+
+
+def _split_array(split, n_e, valid, message):
+    """A call's split per estimate as int32 [n_est] (None: -1, no split, for every estimate), or ValueError(message) unless it holds
+    one entry per estimate and valid(array): the bound is the family's own."""
+    sp = np.full(n_e, -1, np.int32) if split is None else np.asarray(split, dtype=np.int32).reshape(-1)
+    if sp.shape[0] != n_e or (n_e and not valid(sp)):
+        raise ValueError(message)
+    return sp
+
+
+def _gpu_call(device):
+    """-> (the library, the device of the call), or RuntimeError without a GPU: what every argument check of a call comes before."""
+    require_gpu()
+    return _lib.load(), torch.device(device) if device is not None else default_device()
+
+
+def _signal_pair_place(tgts, ests, idx, dev):
+    """The n_tgt >= 1 targets and n_est >= 0 estimates of _signal_pair_index on the device -> (target side, estimate side, target
+    lengths): as _placed_where_they_lie places them, every estimate as long as its target; without estimates the targets alone."""
+    if not ests:
+        tgt_side, tl = _placed_signals(tgts, dev)
+        return tgt_side, (None, 0, None), tl
+    tgt_side, est_side, tl, el = _placed_where_they_lie(tgts, ests, idx, dev)
+    if not np.array_equal(el, tl[idx]):
+        raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
+    return tgt_side, est_side, tl
+
+
+def _hop_blocks(tl, hop, limit):
+    """Whole blocks of `hop` samples per signal (none below two), or ValueError where a signal holds more than `limit`."""
+    blocks = np.where(tl >= 2 * hop, tl // hop, 0)
+    if blocks.max() > limit:
+        raise ValueError("a signal may hold at most %d blocks of %d samples" % (limit, hop))
+    return blocks
+
+
+def _take(t):
+    """A device result on its way to the host, as a function that returns the array: a Pending, or for an empty tensor - nothing
+    was computed - an empty array of its shape."""
+    return Pending(t) if t.numel() else (lambda: np.empty(tuple(t.shape)))
+
+
+def _collected(got, deferred):
+    """The tuple of what the functions `got` return (deferred: the function that returns it)."""
+    collect = lambda: tuple(g() for g in got)      # noqa: E731
+    return collect if deferred else collect()
 
 
 def _pair_index_metrics(tgt_list, est_list, tgt_index, n_cols, place, ws_bytes_of, entry, scalars, device, deferred):
@@ -1052,9 +1126,7 @@ def check_mrstft_resolutions(resolutions):
 
 def check_mrstft_eps(eps):
     """eps as a float, or ValueError: finite and > 0."""
-    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not (0.0 < float(eps) < math.inf):
-        raise ValueError("eps must be a finite number > 0")
-    return float(eps)
+    return float(_number_in(eps, 0.0, math.inf, True, True, "eps must be a finite number > 0"))
 
 
 def mrstft_metrics(tgt_list, est_list, tgt_index, resolutions=None, band_bins=None, eps=MRSTFT_EPS, device=None, deferred=False):
@@ -1137,9 +1209,7 @@ def check_coherence_frames(n_fft, hop):
 
 def check_coherence_threshold(thr):
     """thr as a float, or ValueError: a number in (0, 1] (the C ABI's own check)."""
-    if isinstance(thr, bool) or not isinstance(thr, (int, float, np.integer, np.floating)) or not 0.0 < float(thr) <= 1.0:
-        raise ValueError("threshold must be a number in (0, 1]")
-    return float(thr)
+    return float(_number_in(thr, 0.0, 1.0, True, False, "threshold must be a number in (0, 1]"))
 
 
 def coherence_metrics(tgt_list, est_list, tgt_index, n_fft=1024, hop=None, bands=None, thr=COHERENCE_THRESHOLD, return_spectrum=False,
@@ -1190,7 +1260,7 @@ LOUDNESS_COLUMNS = 6
 
 def check_loudness_rate(rate):
     """rate as an int, or ValueError: a whole number of Hz in LOUDNESS_RATES (the C ABI's own check)."""
-    ok = not isinstance(rate, bool) and isinstance(rate, (int, float, np.integer, np.floating)) and float(rate) == int(rate)
+    ok = _is_number(rate) and float(rate) == int(rate)
     if not ok or not LOUDNESS_RATES[0] <= int(rate) <= LOUDNESS_RATES[1]:
         raise ValueError("the loudness family needs an integer rate in [%d, %d] Hz" % LOUDNESS_RATES)
     return int(rate)
@@ -1211,15 +1281,12 @@ def loudness_metrics(sig_list, rate, return_blocks=False, device=None, deferred=
     rate = check_loudness_rate(rate)
     sigs = list(sig_list)
     n = len(sigs)
-    require_gpu()
-    lib = _lib.load()
-    dev = torch.device(device) if device is not None else default_device()
+    lib, dev = _gpu_call(device)
     with torch.cuda.device(dev):
         out = torch.empty((n, LOUDNESS_COLUMNS), dtype=torch.float64, device=dev)
         blocks, counts = None, None
         if n:
-            f64 = any(_is_f64(w) for w in sigs)
-            data, off, lens = _ragged_where_they_lie(sigs, dev, torch.float64 if f64 else torch.float32)
+            (data, f64, off), lens = _placed_signals(sigs, dev)
             counts = lens // loudness_sub_len(rate)
             if counts.max() > LOUDNESS_MAX_SUB_BLOCKS:
                 raise ValueError("a signal may hold at most %d sub-blocks of 100 ms" % LOUDNESS_MAX_SUB_BLOCKS)
@@ -1255,16 +1322,12 @@ SPECTRUM_SIG_COLUMNS, SPECTRUM_PAIR_COLUMNS = 3, 8      # SSR_SPECTRUM_SIG_COLS,
 
 def check_spectrum_rolloff(rho):
     """rho as a float, or ValueError: a number in (0, 1) (the C ABI's own check)."""
-    if isinstance(rho, bool) or not isinstance(rho, (int, float, np.integer, np.floating)) or not 0.0 < float(rho) < 1.0:
-        raise ValueError("rolloff must be a number in (0, 1)")
-    return float(rho)
+    return float(_number_in(rho, 0.0, 1.0, True, True, "rolloff must be a number in (0, 1)"))
 
 
 def check_spectrum_drop(drop_db):
     """drop_db as a float, or ValueError: a number in (0, 150] (the C ABI's own check)."""
-    if isinstance(drop_db, bool) or not isinstance(drop_db, (int, float, np.integer, np.floating)) or not 0.0 < float(drop_db) <= 150.0:
-        raise ValueError("drop_db must be a number in (0, 150]")
-    return float(drop_db)
+    return float(_number_in(drop_db, 0.0, 150.0, True, False, "drop_db must be a number in (0, 150]"))
 
 
 def spectrum_metrics(tgt_list, est_list, tgt_index, n_fft=2048, hop=None, band_bins=None, rolloff=SPECTRUM_ROLLOFF,
@@ -1288,32 +1351,16 @@ def spectrum_metrics(tgt_list, est_list, tgt_index, n_fft=2048, hop=None, band_b
     if np.any(tab[:, 0] < 0) or np.any(tab[:, 0] > tab[:, 1]) or np.any(tab[:, 1] > n_fft // 2) or np.any(tab[1:, 0] <= tab[:-1, 1]):
         raise ValueError("bands must be disjoint ascending ranges with 0 <= lo <= hi <= n_fft // 2")
     tab = np.ascontiguousarray(tab, dtype=np.int32)                      # read by the library when the call is queued
-    tgts, ests = list(tgt_list), list(est_list)
+    tgts, ests, idx = _signal_pair_index(tgt_list, est_list, tgt_index)
     n_t, n_e, nb = len(tgts), len(ests), n_fft // 2 + 1
-    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
-    if idx.shape[0] != n_e:
-        raise ValueError("one target index per estimate")
-    if n_e and (idx.min() < 0 or idx.max() >= n_t):
-        raise ValueError("tgt_index out of range")
-    sp = np.full(n_e, -1, np.int32) if split_bins is None else np.asarray(split_bins, dtype=np.int32).reshape(-1)
-    if sp.shape[0] != n_e or (n_e and sp.min() < -1):
-        raise ValueError("split_bins must hold one bin >= 0, or -1 for none, per estimate")
-    require_gpu()
-    lib = _lib.load()
-    dev = torch.device(device) if device is not None else default_device()
+    sp = _split_array(split_bins, n_e, lambda s: s.min() >= -1, "split_bins must hold one bin >= 0, or -1 for none, per estimate")
+    lib, dev = _gpu_call(device)
     with torch.cuda.device(dev):
         sig = torch.empty((n_t + n_e, SPECTRUM_SIG_COLUMNS), dtype=torch.float64, device=dev)
         pair = torch.empty((n_e, SPECTRUM_PAIR_COLUMNS), dtype=torch.float64, device=dev)
         ltas = torch.empty((n_t + n_e, nb), dtype=torch.float64, device=dev) if return_ltas else None
         if n_t:
-            if n_e:
-                tgt_side, est_side, tl, el = _placed_where_they_lie(tgts, ests, idx, dev)
-                if not np.array_equal(el, tl[idx]):
-                    raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
-            else:
-                f64 = any(_is_f64(w) for w in tgts)
-                data, off, tl = _ragged_where_they_lie(tgts, dev, torch.float64 if f64 else torch.float32)
-                tgt_side, est_side = (data, int(f64), off), (None, 0, None)
+            tgt_side, est_side, tl = _signal_pair_place(tgts, ests, idx, dev)
             lens = tl.astype(np.int32)
             B_ = tab.shape[0]
             ws_bytes = int(lib.ssr_spectrum_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p), n_e,
@@ -1323,10 +1370,7 @@ def spectrum_metrics(tgt_list, est_list, tgt_index, n_fft=2048, hop=None, band_b
             _lib.check(lib.ssr_spectrum(*_args(tgt_side), _vp(lens_h), n_t, *_args(est_side), _vp(idx_h) if n_e else None, n_e, n_fft, hop,
                                         lo, hi, rho, drop, B_, tab.ctypes.data_as(C.c_void_p), _vp(sp_h) if n_e else None, _vp(sig),
                                         _vp(pair) if n_e else None, _vp(ltas), _vp(ws), ws_bytes, _stream()))
-        take = lambda t: (Pending(t) if t.numel() else (lambda: np.empty(tuple(t.shape))))      # noqa: E731
-        got = [take(sig), take(pair)] + ([take(ltas)] if return_ltas else [])
-        collect = lambda: tuple(g() for g in got)      # noqa: E731
-        return collect if deferred else collect()
+        return _collected([_take(sig), _take(pair)] + ([_take(ltas)] if return_ltas else []), deferred)
 
 
 # ---- auditory: neurogram similarity (NSIM) of gammatone spectrograms --------------------------------------------------------------
@@ -1347,15 +1391,12 @@ def check_auditory_bands(n_bands):
 
 def check_auditory_range(range_db):
     """range_db as a float, or ValueError: a number in (0, 150] (the C ABI's own check)."""
-    if isinstance(range_db, bool) or not isinstance(range_db, (int, float, np.integer, np.floating)) or not 0.0 < float(range_db) <= 150.0:
-        raise ValueError("range_db must be a number in (0, 150]")
-    return float(range_db)
+    return float(_number_in(range_db, 0.0, 150.0, True, False, "range_db must be a number in (0, 150]"))
 
 
 def auditory_hop(fs):
     """Samples per 10 ms block at `fs`: round(fs / 100), halves up; the image's window is two of them."""
-    if isinstance(fs, bool) or not isinstance(fs, (int, float, np.integer, np.floating)) or not 50.0 <= float(fs) < math.inf:
-        raise ValueError("the auditory family needs a rate of at least 50 Hz")
+    _number_in(fs, 50.0, math.inf, False, True, "the auditory family needs a rate of at least 50 Hz")
     return int(math.floor(float(fs) / 100.0 + 0.5))
 
 
@@ -1369,8 +1410,7 @@ def gammatone_design(fs, n_bands=AUDITORY_N_BANDS, band=None):
     fs = float(fs)
     if band is None:
         band = (50.0, 0.45 * fs)
-    ok = isinstance(band, (tuple, list)) and len(band) == 2 and \
-        all(not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) for v in band)
+    ok = isinstance(band, (tuple, list)) and len(band) == 2 and all(_is_number(v) for v in band)
     if not ok or not 0.0 < float(band[0]) < float(band[1]) < fs / 2.0:
         raise ValueError("band must be None or (lo_hz, hi_hz) with 0 < lo_hz < hi_hz < fs / 2")
     scale = lambda f: 21.4 * math.log10(1.0 + 0.00437 * f)      # noqa: E731
@@ -1402,36 +1442,18 @@ def auditory_metrics(tgt_list, est_list, tgt_index, fs, n_bands=AUDITORY_N_BANDS
     if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or int(hop) < 1:
         raise ValueError("hop must be None or an integer >= 1")
     hop = int(hop)
-    tgts, ests = list(tgt_list), list(est_list)
+    tgts, ests, idx = _signal_pair_index(tgt_list, est_list, tgt_index)
     n_t, n_e = len(tgts), len(ests)
-    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
-    if idx.shape[0] != n_e:
-        raise ValueError("one target index per estimate")
-    if n_e and (idx.min() < 0 or idx.max() >= n_t):
-        raise ValueError("tgt_index out of range")
-    sp = np.full(n_e, -1, np.int32) if split_bands is None else np.asarray(split_bands, dtype=np.int32).reshape(-1)
-    if sp.shape[0] != n_e or (n_e and (sp.min() < -1 or sp.max() > C_ - 1 or np.any(sp == 0))):
-        raise ValueError("split_bands must hold -1 or a band in [1, n_bands - 1] per estimate")
-    require_gpu()
-    lib = _lib.load()
-    dev = torch.device(device) if device is not None else default_device()
+    sp = _split_array(split_bands, n_e, lambda s: s.min() >= -1 and s.max() <= C_ - 1 and not np.any(s == 0),
+                      "split_bands must hold -1 or a band in [1, n_bands - 1] per estimate")
+    lib, dev = _gpu_call(device)
     with torch.cuda.device(dev):
         pair = torch.empty((n_e, AUDITORY_PAIR_COLUMNS), dtype=torch.float64, device=dev)
         bands = torch.empty((n_e, C_), dtype=torch.float64, device=dev) if return_bands else None
         images, rows = None, np.zeros(0, np.int64)
         if n_t:
-            if n_e:
-                tgt_side, est_side, tl, el = _placed_where_they_lie(tgts, ests, idx, dev)
-                if not np.array_equal(el, tl[idx]):
-                    raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
-            else:
-                f64 = any(_is_f64(w) for w in tgts)
-                data, off, tl = _ragged_where_they_lie(tgts, dev, torch.float64 if f64 else torch.float32)
-                tgt_side, est_side = (data, int(f64), off), (None, 0, None)
-            blocks = np.where(tl >= 2 * hop, tl // hop, 0)
-            if blocks.max() > AUDITORY_MAX_BLOCKS:
-                raise ValueError("a signal may hold at most %d blocks of %d samples" % (AUDITORY_MAX_BLOCKS, hop))
-            rows = np.maximum(blocks - 1, 0).astype(np.int64)
+            tgt_side, est_side, tl = _signal_pair_place(tgts, ests, idx, dev)
+            rows = np.maximum(_hop_blocks(tl, hop, AUDITORY_MAX_BLOCKS) - 1, 0).astype(np.int64)
             rows = np.concatenate([rows, rows[idx]])
             if return_images:
                 images = torch.empty((int(rows.sum()), C_), dtype=torch.float64, device=dev)
@@ -1443,11 +1465,10 @@ def auditory_metrics(tgt_list, est_list, tgt_index, fs, n_bands=AUDITORY_N_BANDS
             _lib.check(lib.ssr_auditory(*_args(tgt_side), _vp(lens_h), n_t, *_args(est_side), _vp(idx_h) if n_e else None, n_e, hop, C_,
                                         coef.ctypes.data_as(C.c_void_p), rng_db, int(bool(match_level)), _vp(sp_h) if n_e else None,
                                         _vp(pair) if n_e else None, _vp(bands), _vp(images), _vp(ws), ws_bytes, _stream()))
-        take = lambda t: (Pending(t) if t.numel() else (lambda: np.empty(tuple(t.shape))))      # noqa: E731
-        got = [take(pair), take(bands) if return_bands else (lambda: None)]
+        got = [_take(pair), _take(bands) if return_bands else (lambda: None)]
         if return_images:
             edges = np.concatenate(([0], np.cumsum(rows))).astype(np.int64)
-            flat = take(images) if images is not None else (lambda: np.empty((0, C_)))
+            flat = _take(images) if images is not None else (lambda: np.empty((0, C_)))
 
             def cut():
                 a = flat()
@@ -1455,8 +1476,7 @@ def auditory_metrics(tgt_list, est_list, tgt_index, fs, n_bands=AUDITORY_N_BANDS
             got.append(cut)
         else:
             got.append(lambda: None)
-        collect = lambda: tuple(g() for g in got)      # noqa: E731
-        return collect if deferred else collect()
+        return _collected(got, deferred)
 
 
 # ---- modulation: SRMR and the modulation-spectrum distance on §23's filterbank ------------------------------------------------------
@@ -1474,10 +1494,7 @@ MODULATION_WORKSPACE_CAP = 1 << 30       # bytes of workspace one ssr_modulation
 
 def check_modulation_env_rate(env_rate):
     """env_rate as it is, or ValueError: a number in MODULATION_ENV_RATES (Hz)."""
-    if isinstance(env_rate, bool) or not isinstance(env_rate, (int, float, np.integer, np.floating)) or \
-            not MODULATION_ENV_RATES[0] <= float(env_rate) <= MODULATION_ENV_RATES[1]:
-        raise ValueError("env_rate must be a number in [%d, %d] Hz" % MODULATION_ENV_RATES)
-    return env_rate
+    return _number_in(env_rate, *MODULATION_ENV_RATES, False, False, "env_rate must be a number in [%d, %d] Hz" % MODULATION_ENV_RATES)
 
 
 def check_modulation_range(range_db):
@@ -1548,33 +1565,15 @@ def modulation_metrics(tgt_list, est_list, tgt_index, fs, n_bands=AUDITORY_N_BAN
     C_ = coef.shape[0]
     if not isinstance(return_spectrum, (bool, np.bool_)):
         raise ValueError("return_spectrum must be True or False")
-    tgts, ests = list(tgt_list), list(est_list)
+    tgts, ests, idx = _signal_pair_index(tgt_list, est_list, tgt_index)
     n_t, n_e = len(tgts), len(ests)
-    idx = np.asarray(tgt_index, dtype=np.int32).reshape(-1)
-    if idx.shape[0] != n_e:
-        raise ValueError("one target index per estimate")
-    if n_e and (idx.min() < 0 or idx.max() >= n_t):
-        raise ValueError("tgt_index out of range")
-    sp = np.full(n_e, -1, np.int32) if split_bands is None else np.asarray(split_bands, dtype=np.int32).reshape(-1)
-    if sp.shape[0] != n_e or (n_e and (sp.min() < -1 or sp.max() > C_)):
-        raise ValueError("split_bands must hold -1 or a band in [0, n_bands] per estimate")
-    require_gpu()
-    lib = _lib.load()
-    dev = torch.device(device) if device is not None else default_device()
+    sp = _split_array(split_bands, n_e, lambda s: s.min() >= -1 and s.max() <= C_, "split_bands must hold -1 or a band in [0, n_bands] per estimate")
+    lib, dev = _gpu_call(device)
     parts = []                                   # (target positions, estimate positions, signal, pair, spectrum) per call
     with torch.cuda.device(dev):
         if n_t:
-            if n_e:
-                tgt_side, est_side, tl, el = _placed_where_they_lie(tgts, ests, idx, dev)
-                if not np.array_equal(el, tl[idx]):
-                    raise ValueError("every estimate must be as long as its target (truncate to the common length first)")
-            else:
-                f64 = any(_is_f64(w) for w in tgts)
-                data, off, tl = _ragged_where_they_lie(tgts, dev, torch.float64 if f64 else torch.float32)
-                tgt_side, est_side = (data, int(f64), off), (None, 0, None)
-            blocks = np.where(tl >= 2 * hop, tl // hop, 0)
-            if blocks.max() > MODULATION_MAX_BLOCKS:
-                raise ValueError("a signal may hold at most %d blocks of %d samples" % (MODULATION_MAX_BLOCKS, hop))
+            tgt_side, est_side, tl = _signal_pair_place(tgts, ests, idx, dev)
+            blocks = _hop_blocks(tl, hop, MODULATION_MAX_BLOCKS)
             # whole targets with their estimates, in target order, under the cap (a target that exceeds it alone is a call of its own)
             cost = (blocks + 7) // 8 * 8 * C_ * 16 * (1 + np.bincount(idx, minlength=n_t))
             cuts, acc = [0], 0

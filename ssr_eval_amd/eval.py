@@ -66,6 +66,31 @@ def _which_option(option, value, names, entries):
     which_mask(w, names)
 
 
+# What a family's check refuses as the `split` of its option dict, beyond what its AudioMetrics._*_splits refuses (with a message of
+# its own) when the check passes the value on.  The rules differ and are behaviour: each family keeps its own.
+_SPLIT_REFUSED = {
+    "coherence": lambda s: s is None,
+    "bandwidth": lambda s: s is None or isinstance(s, (bool, str, list, tuple, dict)),
+    "auditory": lambda s: not B._is_number(s),
+    "modulation": lambda s: not B._is_number(s),
+}
+
+
+def _dict_option(option, v, names):
+    """ValueError unless `v`, the value of `option`, is True or a non-empty dict of `names` with a `split`, if any, the family takes."""
+    if v is not True and (not isinstance(v, dict) or not v or set(v) - set(names)):
+        takes = ["'%s'" % k for k in names]
+        raise ValueError("%s must be None, True or a dict of %s and / or %s" % (option, ", ".join(takes[:-1]), takes[-1]))
+    if v is not True and "split" in v and _SPLIT_REFUSED[option](v["split"]):
+        raise ValueError("split must be a frequency in Hz (leave it out to split every key at its own cutoff)")
+
+
+def _key_splits(q, keys):
+    """One split frequency per degradation key: `split` Hz of the option dict q for every key where it names one, else the key's
+    own cutoff (key_cutoff_hz; None for mp3 keys)."""
+    return [float(q["split"])] * len(keys) if "split" in q else [key_cutoff_hz(k) for k in keys]
+
+
 # A family's two functions: check(helper, value) raises ValueError for a value of the option the family does not take (it sees
 # every value but None: None is "off"), arguments(helper, degradation keys of the call) -> the (positional, keyword) arguments of
 # the family's AudioMetrics methods after the signals.  Where both need an option's defaults, *_args spells them out once.
@@ -159,9 +184,8 @@ def _mrstft_args(v):
 
 
 def _mrstft_check(h, v):
+    _dict_option("mrstft", v, ("resolutions", "band", "eps"))
     if v is not True:
-        if not isinstance(v, dict) or not v or set(v) - {"resolutions", "band", "eps"}:
-            raise ValueError("mrstft must be None, True or a dict of 'resolutions', 'band' and / or 'eps'")
         resolutions, band, eps = _mrstft_args(v)
         B.check_mrstft_eps(eps)
         AudioMetrics._mrstft_bins(h.evaluationset_sr, B.check_mrstft_resolutions(resolutions), band)
@@ -204,19 +228,14 @@ def result_key_order():
 
 
 def _coherence_args(h, v, keys):
-    """-> (n_fft, hop, band, one split frequency per degradation key, threshold): the split is `split` Hz for every key where the
-    option names one, else the key's own cutoff (key_cutoff_hz; None for mp3 keys - NaN values)."""
+    """-> (n_fft, hop, band, one split frequency per degradation key (_key_splits; None: NaN values), threshold)."""
     q = v if isinstance(v, dict) else {}
-    split = [float(q["split"])] * len(keys) if "split" in q else [key_cutoff_hz(k) for k in keys]
-    return q.get("n_fft", 1024), q.get("hop"), q.get("band"), split, q.get("threshold", B.COHERENCE_THRESHOLD)
+    return q.get("n_fft", 1024), q.get("hop"), q.get("band"), _key_splits(q, keys), q.get("threshold", B.COHERENCE_THRESHOLD)
 
 
 def _coherence_check(h, v):
+    _dict_option("coherence", v, ("n_fft", "hop", "band", "threshold", "split"))
     if v is not True:
-        if not isinstance(v, dict) or not v or set(v) - {"n_fft", "hop", "band", "threshold", "split"}:
-            raise ValueError("coherence must be None, True or a dict of 'n_fft', 'hop', 'band', 'threshold' and / or 'split'")
-        if "split" in v and v["split"] is None:
-            raise ValueError("split must be a frequency in Hz (leave it out to split every key at its own cutoff)")
         n_fft, hop, band, split, thr = _coherence_args(h, {k: o for k, o in v.items() if k != "split"}, ["k"])
         B.check_coherence_threshold(thr)
         h.audio_metrics._coh_bands(B.check_coherence_frames(n_fft, hop)[0], band, v.get("split"), 1)
@@ -241,20 +260,15 @@ def _loudness_check(h, v):
 
 
 def _bandwidth_args(h, v, keys):
-    """-> ((n_fft, hop, band, one split frequency per degradation key, rolloff, drop_db), {"names": the family's keys}): the split is
-    `split` Hz for every key where the option names one, else the key's own cutoff (key_cutoff_hz; None for mp3 keys - NaN hf_diff)."""
+    """-> ((n_fft, hop, band, one split frequency per degradation key (_key_splits; None: NaN hf_diff), rolloff, drop_db), {"names":
+    the family's keys})."""
     q = v if isinstance(v, dict) else {}
-    split = [float(q["split"])] * len(keys) if "split" in q else [key_cutoff_hz(k) for k in keys]
-    return ((q.get("n_fft", 2048), q.get("hop"), q.get("band"), split, q.get("rolloff", B.SPECTRUM_ROLLOFF), q.get("drop_db", B.SPECTRUM_DROP_DB)),
+    return ((q.get("n_fft", 2048), q.get("hop"), q.get("band"), _key_splits(q, keys), q.get("rolloff", B.SPECTRUM_ROLLOFF), q.get("drop_db", B.SPECTRUM_DROP_DB)),
             {"names": _BW_KEYS})
 
 
 def _bandwidth_check(h, v):
-    if v is not True:
-        if not isinstance(v, dict) or not v or set(v) - {"n_fft", "hop", "band", "split", "rolloff", "drop_db"}:
-            raise ValueError("bandwidth must be None, True or a dict of 'n_fft', 'hop', 'band', 'split', 'rolloff' and / or 'drop_db'")
-        if "split" in v and (v["split"] is None or isinstance(v["split"], (bool, str, list, tuple, dict))):
-            raise ValueError("split must be a frequency in Hz (leave it out to split every key at its own cutoff)")
+    _dict_option("bandwidth", v, ("n_fft", "hop", "band", "split", "rolloff", "drop_db"))
     (n_fft, hop, band, split, rho, drop), _ = _bandwidth_args(h, v, ["k"])
     n_fft, hop = B.check_coherence_frames(n_fft, hop)
     B.check_spectrum_rolloff(rho)
@@ -264,20 +278,15 @@ def _bandwidth_check(h, v):
 
 
 def _auditory_args(h, v, keys):
-    """-> ((one split frequency per degradation key, n_bands, band, range_db, match_level), {"names": the family's keys}): the split is
-    `split` Hz for every key where the option names one, else the key's own cutoff (key_cutoff_hz; None for mp3 keys - NaN nsim_hf)."""
+    """-> ((one split frequency per degradation key (_key_splits; None: NaN nsim_hf), n_bands, band, range_db, match_level), {"names":
+    the family's keys})."""
     q = v if isinstance(v, dict) else {}
-    split = [float(q["split"])] * len(keys) if "split" in q else [key_cutoff_hz(k) for k in keys]
-    return ((split, q.get("n_bands", B.AUDITORY_N_BANDS), q.get("band"), q.get("range_db", B.AUDITORY_RANGE_DB), q.get("match_level", True)),
+    return ((_key_splits(q, keys), q.get("n_bands", B.AUDITORY_N_BANDS), q.get("band"), q.get("range_db", B.AUDITORY_RANGE_DB), q.get("match_level", True)),
             {"names": _AUD_KEYS})
 
 
 def _auditory_check(h, v):
-    if v is not True:
-        if not isinstance(v, dict) or not v or set(v) - {"n_bands", "band", "range_db", "split", "match_level"}:
-            raise ValueError("auditory must be None, True or a dict of 'n_bands', 'band', 'range_db', 'split' and / or 'match_level'")
-        if "split" in v and (isinstance(v["split"], bool) or not isinstance(v["split"], (int, float, np.integer, np.floating))):
-            raise ValueError("split must be a frequency in Hz (leave it out to split every key at its own cutoff)")
+    _dict_option("auditory", v, ("n_bands", "band", "range_db", "split", "match_level"))
     (split, n_bands, band, range_db, match), _ = _auditory_args(h, v, ["k"])
     fc, _ = B.gammatone_design(h.evaluationset_sr, n_bands, band)
     B.check_auditory_range(range_db)
@@ -287,23 +296,17 @@ def _auditory_check(h, v):
 
 
 def _modulation_args(h, v, keys):
-    """-> ((one split frequency per degradation key, n_bands, band, env_rate, range_db, kstar), {"names": the family's keys}): the split
-    is `split` Hz for every key where the option names one, else the key's own cutoff (key_cutoff_hz; None for mp3 keys - NaN
-    mod_dist_hf)."""
+    """-> ((one split frequency per degradation key (_key_splits; None: NaN mod_dist_hf), n_bands, band, env_rate, range_db, kstar),
+    {"names": the family's keys})."""
     q = v if isinstance(v, dict) else {}
-    split = [float(q["split"])] * len(keys) if "split" in q else [key_cutoff_hz(k) for k in keys]
-    return ((split, q.get("n_bands", B.AUDITORY_N_BANDS), q.get("band"), q.get("env_rate", B.MODULATION_ENV_RATE),
+    return ((_key_splits(q, keys), q.get("n_bands", B.AUDITORY_N_BANDS), q.get("band"), q.get("env_rate", B.MODULATION_ENV_RATE),
              q.get("range_db", B.MODULATION_RANGE_DB), q.get("kstar")), {"names": _MOD_KEYS})
 
 
 def _modulation_check(h, v):
-    if v is not True:
-        if not isinstance(v, dict) or not v or set(v) - {"n_bands", "band", "env_rate", "range_db", "kstar", "split"}:
-            raise ValueError("modulation must be None, True or a dict of 'n_bands', 'band', 'env_rate', 'range_db', 'kstar' and / or 'split'")
-        if "split" in v and (isinstance(v["split"], bool) or not isinstance(v["split"], (int, float, np.integer, np.floating))):
-            raise ValueError("split must be a frequency in Hz (leave it out to split every key at its own cutoff)")
-        if "kstar" in v and v["kstar"] is None:
-            raise ValueError("kstar must be an integer in [5, 8] (leave it out for the adaptive table)")
+    _dict_option("modulation", v, ("n_bands", "band", "env_rate", "range_db", "kstar", "split"))
+    if v is not True and "kstar" in v and v["kstar"] is None:
+        raise ValueError("kstar must be an integer in [5, 8] (leave it out for the adaptive table)")
     (split, n_bands, band, env_rate, range_db, kstar), _ = _modulation_args(h, v, ["k"])
     fc, _, _ = h.audio_metrics._modulation_design(n_bands, band, env_rate, range_db, kstar)
     h.audio_metrics._modulation_splits(fc, split, 1)

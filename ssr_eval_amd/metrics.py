@@ -93,6 +93,52 @@ def _shared_targets(targets):
     return tgts, index
 
 
+def _names_asked(names, allowed):
+    """The result keys asked for, in result order, or ValueError: None = all of `allowed`, or a non-empty tuple / list of them."""
+    if names is None:
+        return allowed
+    if not isinstance(names, (tuple, list)) or not names or not all(isinstance(k, str) and k in allowed for k in names):
+        raise ValueError("names must be None or a tuple of %s" % (allowed,))
+    return tuple(k for k in allowed if k in names)
+
+
+def _split_indices(split, n, to_index):
+    """The split index of n pairs: split = None (no split: -1 for every pair), one frequency in Hz for every pair, or a list of one
+    per pair (None: -1 for that pair).  to_index(the frequency as a float) is the family's own mapping."""
+    if split is None:
+        return [-1] * n
+    splits = split if isinstance(split, list) else [split] * n
+    if len(splits) != n:
+        raise ValueError("one split frequency per pair")
+    message = "a split frequency is a finite number >= 0 in Hz"
+    return [-1 if s is None else to_index(float(B._number_in(s, 0.0, math.inf, False, True, message))) for s in splits]
+
+
+def _tile_key_splits(split_hz, K, n):
+    """The split of a *_multi call for its n * K item-major pairs: a list holds one frequency per key and is tiled n times; None
+    or one frequency is for every pair as it is."""
+    if not isinstance(split_hz, list):
+        return split_hz
+    if len(split_hz) != K:
+        raise ValueError("one split frequency per key")
+    return list(split_hz) * n
+
+
+def _check_1d(signals):
+    """ValueError for a signal in memory that is not 1-D (a path is read later)."""
+    for w in signals:
+        if not isinstance(w, str) and len(w.shape) != 1:
+            raise ValueError("expected a 1-D signal, got shape %s" % (tuple(w.shape),))
+
+
+def _group_by_dtype(signals):
+    """The positions of the float32 and of the float64 signals, the group met first in front: one library call per dtype."""
+    groups = {}
+    for i, w in enumerate(signals):
+        groups.setdefault(bool(B._is_f64(w)), []).append(i)
+    return list(groups.values())
+
+
 class AudioMetrics:
     def __init__(self, rate, *, precision="f64", device=None, n_fft=None, hop_length=None):
         self.rate = rate
@@ -505,7 +551,7 @@ class AudioMetrics:
     def _pitch_range(fmin, fmax):
         """(fmin, fmax) in Hz as floats, or ValueError (40 <= fmin < fmax <= 1000, at least three lags)."""
         for v in (fmin, fmax):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            if not B._is_number(v):
                 raise ValueError("fmin and fmax must be numbers (Hz)")
         return B.check_pitch_range(fmin, fmax)
 
@@ -554,8 +600,7 @@ class AudioMetrics:
         [0, n_fft // 2]; ValueError where that leaves no bin."""
         if band is None:
             return None
-        ok = isinstance(band, (tuple, list)) and len(band) == 2 and all(
-            not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v) for v in band)
+        ok = isinstance(band, (tuple, list)) and len(band) == 2 and all(B._is_number(v) and np.isfinite(v) for v in band)
         if not ok:
             raise ValueError("band must be None or (lo_hz, hi_hz)")
         lo, hi = (fractions.Fraction(float(v)) * n_fft / fractions.Fraction(float(rate)) for v in band)
@@ -680,20 +725,11 @@ class AudioMetrics:
         lo, hi = self._phase_bins(self.rate, n_fft, band) or (0, n_fft // 2)
         if split is None:
             return [[(lo, hi)]] * n
-        per_pair = isinstance(split, list)
-        splits = split if per_pair else [split] * n
-        if len(splits) != n:
-            raise ValueError("one split frequency per pair")
-        rows = []
-        for s in splits:
-            if s is None and per_pair:
-                rows.append([(lo, hi), (1, 0)])
-                continue
-            if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= float(s) < math.inf:
-                raise ValueError("a split frequency is a finite number >= 0 in Hz")
-            k = math.ceil(fractions.Fraction(float(s)) * n_fft / fractions.Fraction(float(self.rate)))
-            rows.append([(lo, hi), (k, hi) if k <= hi else (1, 0)])
-        return rows
+        return [[(lo, hi), (k, hi) if 0 <= k <= hi else (1, 0)] for k in _split_indices(split, n, self._ceil_bin(n_fft))]
+
+    def _ceil_bin(self, n_fft):
+        """-> the function f in Hz -> ceil(f n_fft / rate), in exact arithmetic: the first bin at or above f."""
+        return lambda f: math.ceil(fractions.Fraction(f) * n_fft / fractions.Fraction(float(self.rate)))
 
     def _coh_dicts(self, n_fft, split, spectrum):
         """(rows [n, n_bands, 3], spectra [n, n_fft / 2 + 1] or None) -> one dict per pair."""
@@ -747,10 +783,7 @@ class AudioMetrics:
         dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
         to each other in one call."""
         ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
-        if isinstance(split_hz, list):
-            if len(split_hz) != K:
-                raise ValueError("one split frequency per key")
-            split_hz = list(split_hz) * n
+        split_hz = _tile_key_splits(split_hz, K, n)
         family = self._coh_family(n_fft, hop, band, split_hz, threshold, return_spectrum, n * K)
         return _regroup(self._pairs(family, ests, tgts, resident, True, by_dtype=True, per_pair=True), n, K, deferred)
 
@@ -760,19 +793,13 @@ class AudioMetrics:
     @staticmethod
     def _loudness_names(names, with_target):
         """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
-        allowed = _LOUD_NAMES + (_LOUD_DIFF_NAMES if with_target else ())
-        if names is None:
-            return allowed
-        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(k, str) and k in allowed for k in names):
-            raise ValueError("names must be None or a tuple of %s" % (allowed,))
-        return tuple(k for k in allowed if k in names)
+        return _names_asked(names, _LOUD_NAMES + (_LOUD_DIFF_NAMES if with_target else ()))
 
     def _loudness_signal(self, wav):
         if isinstance(wav, str):
             from .io import load_audio
             wav = load_audio(wav, self.rate)
-        if len(wav.shape) != 1:
-            raise ValueError("expected a 1-D signal, got shape %s" % (tuple(wav.shape),))
+        _check_1d([wav])
         return wav
 
     def loudness(self, est, target=None, return_blocks=False):
@@ -801,11 +828,8 @@ class AudioMetrics:
             sigs, tgts, index = [self._loudness_signal(e) for e in ests], [], []
         n_e = len(sigs)
         every = sigs + tgts
-        groups = {}
-        for i, w in enumerate(every):
-            groups.setdefault(bool(B._is_f64(w)), []).append(i)
         pending = [(idx, B.loudness_metrics([every[i] for i in idx], rate, return_blocks, self._device, deferred=True))
-                   for idx in groups.values()]
+                   for idx in _group_by_dtype(every)]
 
         def finish():
             rows, blocks = np.empty((len(every), len(_LOUD_NAMES))), [None] * len(every)
@@ -844,12 +868,7 @@ class AudioMetrics:
     @staticmethod
     def _bandwidth_names(names, with_target):
         """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
-        allowed = _SPEC_NAMES + (_SPEC_PAIR_NAMES if with_target else ())
-        if names is None:
-            return allowed
-        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(k, str) and k in allowed for k in names):
-            raise ValueError("names must be None or a tuple of %s" % (allowed,))
-        return tuple(k for k in allowed if k in names)
+        return _names_asked(names, _SPEC_NAMES + (_SPEC_PAIR_NAMES if with_target else ()))
 
     @staticmethod
     def _ltas_bands(rate, n_fft, band):
@@ -881,19 +900,7 @@ class AudioMetrics:
         pair, or a list of one per pair (None: no split for that pair, -1)."""
         if split is None:
             return None
-        per_pair = isinstance(split, list)
-        splits = split if per_pair else [split] * n
-        if len(splits) != n:
-            raise ValueError("one split frequency per pair")
-        bins = []
-        for s in splits:
-            if s is None and per_pair:
-                bins.append(-1)
-                continue
-            if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= float(s) < math.inf:
-                raise ValueError("a split frequency is a finite number >= 0 in Hz")
-            bins.append(min(math.ceil(fractions.Fraction(float(s)) * n_fft / fractions.Fraction(float(self.rate))), n_fft // 2 + 1))
-        return bins
+        return [min(k, n_fft // 2 + 1) for k in _split_indices(split, n, self._ceil_bin(n_fft))]
 
     def bandwidth(self, est, target=None, n_fft=2048, hop=None, band=None, split_hz=None, rolloff=B.SPECTRUM_ROLLOFF,
                   drop_db=B.SPECTRUM_DROP_DB, names=None, return_ltas=False):
@@ -942,11 +949,8 @@ class AudioMetrics:
 
         if not with_t and splits is None:          # signals alone: they are the call's targets, there is no estimate
             sigs = [self._loudness_signal(e) for e in ests]
-            groups = {}
-            for i, w in enumerate(sigs):
-                groups.setdefault(bool(B._is_f64(w)), []).append(i)
             pending = [(idx, B.spectrum_metrics([sigs[i] for i in idx], [], [], n_fft, hop, bins, rho, drop, table, None, return_ltas,
-                                                self._device, deferred=True)) for idx in groups.values()]
+                                                self._device, deferred=True)) for idx in _group_by_dtype(sigs)]
 
             def finish():
                 out = [None] * len(sigs)
@@ -978,10 +982,7 @@ class AudioMetrics:
         dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
         to each other in one call and the target is transformed once."""
         ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
-        if isinstance(split_hz, list):
-            if len(split_hz) != K:
-                raise ValueError("one split frequency per key")
-            split_hz = list(split_hz) * n
+        split_hz = _tile_key_splits(split_hz, K, n)
         return _regroup(self.bandwidth_batch(ests, tgts, n_fft, hop, band, split_hz, rolloff, drop_db, names, return_ltas, resident, True),
                         n, K, deferred)
 
@@ -991,29 +992,13 @@ class AudioMetrics:
     @staticmethod
     def _nsim_names(names):
         """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
-        if names is None:
-            return _NSIM_NAMES
-        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(k, str) and k in _NSIM_NAMES for k in names):
-            raise ValueError("names must be None or a tuple of %s" % (_NSIM_NAMES,))
-        return tuple(k for k in _NSIM_NAMES if k in names)
+        return _names_asked(names, _NSIM_NAMES)
 
     @staticmethod
     def _nsim_splits(fc, split, n):
         """The first interior band at or above the split of n pairs (len(fc) - 1: the split lies above every interior band): split = None
         (no split: -1 for every pair), one frequency in Hz for every pair, or a list of one per pair (None: -1 for that pair)."""
-        per_pair = isinstance(split, list)
-        splits = split if per_pair else [split] * n
-        if len(splits) != n:
-            raise ValueError("one split frequency per pair")
-        out = []
-        for s in splits:
-            if s is None and (per_pair or split is None):
-                out.append(-1)
-                continue
-            if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= float(s) < math.inf:
-                raise ValueError("a split frequency is a finite number >= 0 in Hz")
-            out.append(1 + int(np.searchsorted(fc[1:-1], float(s), side="left")))
-        return out
+        return _split_indices(split, n, lambda f: 1 + int(np.searchsorted(fc[1:-1], f, side="left")))
 
     def nsim(self, est, target, split_hz=None, n_bands=B.AUDITORY_N_BANDS, band=None, range_db=B.AUDITORY_RANGE_DB, match_level=True,
              return_bands=False):
@@ -1054,9 +1039,7 @@ class AudioMetrics:
                     d["fvnsim"], d["centre_hz"] = np.array(bands[j]), np.array(fc)
                 out.append(d)
             return out
-        for w in list(ests[:n]) + list(targets[:n]):
-            if not isinstance(w, str) and len(w.shape) != 1:
-                raise ValueError("expected a 1-D signal, got shape %s" % (tuple(w.shape),))
+        _check_1d(list(ests[:n]) + list(targets[:n]))
         return self._pairs((call, dicts), ests[:n], targets[:n], resident, deferred, by_dtype=True, per_pair=True)
 
     def nsim_multi(self, ests_by_key, targets, split_hz=None, n_bands=B.AUDITORY_N_BANDS, band=None, range_db=B.AUDITORY_RANGE_DB,
@@ -1065,10 +1048,7 @@ class AudioMetrics:
         dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
         to each other in one call and the target is filtered once."""
         ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
-        if isinstance(split_hz, list):
-            if len(split_hz) != K:
-                raise ValueError("one split frequency per key")
-            split_hz = list(split_hz) * n
+        split_hz = _tile_key_splits(split_hz, K, n)
         return _regroup(self.nsim_batch(ests, tgts, split_hz, n_bands, band, range_db, match_level, return_bands, names, resident, True),
                         n, K, deferred)
 
@@ -1088,29 +1068,13 @@ class AudioMetrics:
     @staticmethod
     def _modulation_names(names):
         """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
-        if names is None:
-            return _MOD_NAMES
-        if not isinstance(names, (tuple, list)) or not names or not all(isinstance(k, str) and k in _MOD_NAMES for k in names):
-            raise ValueError("names must be None or a tuple of %s" % (_MOD_NAMES,))
-        return tuple(k for k in _MOD_NAMES if k in names)
+        return _names_asked(names, _MOD_NAMES)
 
     @staticmethod
     def _modulation_splits(fc, split, n):
         """The first band whose centre frequency is at or above the split of n pairs, in [0, len(fc)]: split = None (no split: -1 for
         every pair), one frequency in Hz for every pair, or a list of one per pair (None: -1 for that pair)."""
-        per_pair = isinstance(split, list)
-        splits = split if per_pair else [split] * n
-        if len(splits) != n:
-            raise ValueError("one split frequency per pair")
-        out = []
-        for s in splits:
-            if s is None and (per_pair or split is None):
-                out.append(-1)
-                continue
-            if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= float(s) < math.inf:
-                raise ValueError("a split frequency is a finite number >= 0 in Hz")
-            out.append(int(np.searchsorted(fc, float(s), side="left")))
-        return out
+        return _split_indices(split, n, lambda f: int(np.searchsorted(fc, f, side="left")))
 
     def _modulation_design(self, n_bands, band, env_rate, range_db, kstar):
         """-> (f_c, the modulation centres in Hz, range_db as a float): every option checked, nothing queued."""
@@ -1177,9 +1141,7 @@ class AudioMetrics:
                     d["centre_hz"], d["mod_hz"] = np.array(fc), np.array(fk)
                 out.append(d)
             return out
-        for w in list(ests[:n]) + list(targets[:n]):
-            if not isinstance(w, str) and len(w.shape) != 1:
-                raise ValueError("expected a 1-D signal, got shape %s" % (tuple(w.shape),))
+        _check_1d(list(ests[:n]) + list(targets[:n]))
         return self._pairs((call, dicts), ests[:n], targets[:n], resident, deferred, by_dtype=True, per_pair=True)
 
     def modulation_multi(self, ests_by_key, targets, split_hz=None, n_bands=B.AUDITORY_N_BANDS, band=None, env_rate=B.MODULATION_ENV_RATE,
@@ -1188,10 +1150,7 @@ class AudioMetrics:
         dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
         to each other in one call and the target is filtered once."""
         ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
-        if isinstance(split_hz, list):
-            if len(split_hz) != K:
-                raise ValueError("one split frequency per key")
-            split_hz = list(split_hz) * n
+        split_hz = _tile_key_splits(split_hz, K, n)
         return _regroup(self.modulation_batch(ests, tgts, split_hz, n_bands, band, env_rate, range_db, kstar, names, return_spectrum, resident,
                                               True), n, K, deferred)
 
