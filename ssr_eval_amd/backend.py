@@ -1621,6 +1621,93 @@ def modulation_metrics(tgt_list, est_list, tgt_index, fs, n_bands=AUDITORY_N_BAN
         return collect if deferred else collect()
 
 
+# ---- csii: the coherence speech intelligibility index and the fitted three-level I3 on §20's spectra -----------------
+CSII_CENTRES = (150.0, 250.0, 350.0, 450.0, 570.0, 700.0, 840.0, 1000.0, 1170.0, 1370.0, 1600.0, 1850.0, 2150.0, 2500.0, 2900.0, 3400.0,
+                4000.0, 4800.0, 5800.0, 7000.0, 8500.0)         # Hz: the critical bands of ANSI S3.5-1997
+CSII_IMPORTANCE = (0.0103, 0.0261, 0.0419) + (0.0577,) * 14 + (0.0460, 0.0343, 0.0226, 0.0110)        # their band importance, sum 1
+CSII_COLUMNS = _lib.CSII_COLUMNS         # SSR_CSII_COLUMNS: the nine values, then the segments in the four sets
+CSII_SETS = 4                            # all, low, mid, high
+_CSII_WEIGHTS = {}                       # (rate, n_fft, band, device index) -> the device copy of csii_design's W
+
+
+def csii_default_nfft(fs):
+    """The segment length at rate fs: the smallest of PHASE_N_FFTS that holds 16 ms, 2048 where none does (256 at 16 kHz, 1024 at
+    44.1 and 48 kHz).  ValueError unless fs is a number above 300 Hz (the lowest critical band centre lies at 150 Hz)."""
+    _number_in(fs, 300.0, math.inf, True, True, "the csii family needs a rate above 300 Hz")
+    return next((n for n in PHASE_N_FFTS if n >= 0.016 * float(fs)), PHASE_N_FFTS[-1])
+
+
+def check_csii_frames(fs, n_fft, hop):
+    """(n_fft, hop) as ints (n_fft None: csii_default_nfft(fs); hop None: n_fft // 2), or ValueError: §20's framing."""
+    return check_coherence_frames(csii_default_nfft(fs) if n_fft is None else n_fft, hop)
+
+
+def csii_design(fs, n_fft, band=None):
+    """The critical-band stage at rate fs on n_fft-point segments -> (f_c [n_bands] in Hz, importance [n_bands] float64
+    with sum 1, W [n_bands, n_fft // 2 + 1] float64): the bands of ANSI S3.5-1997 with f_c <= fs / 2 (17 at 8 kHz, 20 at 16 kHz, all 21
+    from 17 kHz) - inside band = (lo_hz, hi_hz),
+    both ends included, if one is given -, their importance renormalised, and the rounded-exponential weights W_j[k] = (1 + p g)
+    exp(-p g) with g = |k fs / n_fft - f_c| / f_c and p = 4 f_c / ERB(f_c), ERB = 24.7 (4.37 f_c / 1000 + 1); W_j[0] = 0.
+    ValueError unless n_fft is one of PHASE_N_FFTS and at least one band is left."""
+    csii_default_nfft(fs)
+    n_fft, _ = check_coherence_frames(n_fft, None)
+    fs = float(fs)
+    ok = band is None or (isinstance(band, (tuple, list)) and len(band) == 2 and all(_is_number(v) for v in band) and
+                          0.0 <= float(band[0]) <= float(band[1]))
+    keep = [j for j, f in enumerate(CSII_CENTRES) if f <= fs / 2.0 and (band is None or float(band[0]) <= f <= float(band[1]))] if ok else []
+    if not keep:
+        raise ValueError("band must be None or (lo_hz, hi_hz) with 0 <= lo_hz <= hi_hz and a critical-band centre up to fs / 2 inside it")
+    fc = np.array([CSII_CENTRES[j] for j in keep], np.float64)
+    imp = np.array([CSII_IMPORTANCE[j] for j in keep], np.float64)
+    imp = imp / imp.sum()
+    p = 4.0 * fc / (24.7 * (4.37 * fc / 1000.0 + 1.0))
+    g = np.abs(np.arange(n_fft // 2 + 1, dtype=np.float64)[None, :] * (fs / n_fft) - fc[:, None]) / fc[:, None]
+    W = (1.0 + p[:, None] * g) * np.exp(-p[:, None] * g)
+    W[:, 0] = 0.0
+    return fc, np.ascontiguousarray(imp), np.ascontiguousarray(W)
+
+
+def csii_metrics(tgt_list, est_list, tgt_index, fs, n_fft=None, hop=None, band=None, split_bands=None, return_bands=False, device=None,
+                 deferred=False):
+    """The coherence speech intelligibility index of estimate e against target tgt_index[e] (ssr_csii): waveforms at rate
+    fs (float32 or float64, each estimate as long as its target; a list holding both dtypes is widened to float64) -> (rows [n_est,
+    13] float64: csii over all segments, csii_low, csii_mid, csii_high, i3, the value above the split of the four sets in that
+    order, then the segments in the four sets; bands [n_est, 4, n_bands]: the band values T_j of every set, or None without
+    return_bands).  n_fft: None = csii_default_nfft(fs), or 256, 512, 1024 or 2048; hop: None = n_fft // 2; band: None or (lo_hz,
+    hi_hz), the critical-band centres kept; split_bands: None, or per estimate the first band of its upper part in [0, n_bands]
+    (n_bands: none above; -1: no split).  A set of fewer than two segments and a digitally silent target: NaN.  The workspace holds
+    128 (n_fft / 2 + 1) bytes per chunk of 32 segments of every pair.  Device views of one buffer are read where they lie.
+    deferred: a function that returns the tuple."""
+    n_fft, hop = check_csii_frames(fs, n_fft, hop)
+    _, imp, W = csii_design(fs, n_fft, band)
+    J = imp.shape[0]
+    if not isinstance(return_bands, (bool, np.bool_)):
+        raise ValueError("return_bands must be True or False")
+    tgts, ests, idx = _signal_pair_index(tgt_list, est_list, tgt_index)
+    n_t, n_e = len(tgts), len(ests)
+    sp = _split_array(split_bands, n_e, lambda s: s.min() >= -1 and s.max() <= J, "split_bands must hold -1 or a band in [0, n_bands] per estimate")
+    lib, dev = _gpu_call(device)
+    with torch.cuda.device(dev):
+        rows = torch.empty((n_e, CSII_COLUMNS), dtype=torch.float64, device=dev)
+        bands = torch.empty((n_e, CSII_SETS, J), dtype=torch.float64, device=dev) if return_bands else None
+        if n_e:
+            tgt_side, est_side, tl = _signal_pair_place(tgts, ests, idx, dev)
+            lens = tl.astype(np.int32)
+            ws_bytes = int(lib.ssr_csii_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p), n_e, n_fft, hop, J))
+            ws = _workspace(ws_bytes, dev)
+            lens_h, idx_h, sp_h = _host_i32(lens, dev), _host_i32(idx, dev), _host_i32(sp, dev)
+            # the weights stay on the device for the life of the process, one table (at most 172 KB) per (rate, n_fft, band, device);
+            # the importance is read by the library out of page-locked memory, like the three int32 arrays: no copy waits for the stream
+            key = (float(fs), n_fft, None if band is None else (float(band[0]), float(band[1])), torch.cuda.current_device())
+            w_dev = _CSII_WEIGHTS.get(key)
+            if w_dev is None:
+                w_dev = _CSII_WEIGHTS[key] = _h2d(W, dev)
+            imp_h = _DescRing.get(torch.cuda.current_device()).stage(imp, dev)
+            _lib.check(lib.ssr_csii(*_args(tgt_side), _vp(lens_h), n_t, *_args(est_side), _vp(idx_h), n_e, n_fft, hop, J, _vp(w_dev),
+                                    _vp(imp_h), _vp(sp_h), _vp(rows), _vp(bands), _vp(ws), ws_bytes, _stream()))
+        return _collected([_take(rows), _take(bands) if return_bands else (lambda: None)], deferred)
+
+
 # ---- distribution: Fréchet and kernel distance of embedding sets (DESIGN §25) ---------------------------------------------------------
 DISTRIBUTION_MAX_DIM = 1024              # SSR_DISTRIBUTION_MAX_DIM
 DISTRIBUTION_MAX_GAMMA = 8               # SSR_DISTRIBUTION_MAX_GAMMA

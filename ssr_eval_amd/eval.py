@@ -21,7 +21,7 @@ import torch
 from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
-from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _LOUD_DIFF_NAMES, _LOUD_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
+from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _CSII_NAMES, _LOUD_DIFF_NAMES, _LOUD_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
     _MOD_NAMES, _NSIM_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _SPEC_NAMES, _SPEC_PAIR_NAMES, _WAVE_NAMES
 from .distribution import check_option as check_distribution_option, embed_waves, result_block as distribution_block
 from .stats import bootstrap_ci, bootstrap_option
@@ -47,6 +47,9 @@ _AUD_KEYS = _NSIM_NAMES[:2]
 # of the modulation family a key's result keeps the output's SRMR, its difference to the target's and the modulation-spectrum
 # distance over all bands and over the bands above the key's cutoff
 _MOD_KEYS = _MOD_NAMES[:4]
+# of the csii family a key's result keeps the index over all segments, over the mid-level ones, the fitted I3 and the index over the
+# critical bands at or above the key's cutoff
+_CSII_KEYS = (_CSII_NAMES[0], _CSII_NAMES[2], _CSII_NAMES[4], _CSII_NAMES[5])
 
 
 def _option_dict(value):
@@ -73,6 +76,7 @@ _SPLIT_REFUSED = {
     "bandwidth": lambda s: s is None or isinstance(s, (bool, str, list, tuple, dict)),
     "auditory": lambda s: not B._is_number(s),
     "modulation": lambda s: not B._is_number(s),
+    "csii": lambda s: not B._is_number(s),
 }
 
 
@@ -312,9 +316,9 @@ def _modulation_check(h, v):
     h.audio_metrics._modulation_splits(fc, split, 1)
 
 
-# The open end of the registry: queued after the two tuples above, its keys behind theirs.  A new family's row goes in BEFORE the
-# `auditory` row, behind the last row in front of it: the tests of the auditory family pin its two keys as the end of
-# full_key_order(), those of the families before it only that each comes after its predecessor.
+# The third tuple of the registry: queued after the two tuples above, its keys behind theirs.  It is closed - the tests of its
+# families pin its four rows, and those of the auditory family its two keys as the end of full_key_order(); a new family's row goes
+# into _NEWER_FAMILIES below.
 _TAIL_FAMILIES = (
     _Family("loudness", "loudness_multi", "loudness_batch", _LOUD_KEYS, _loudness_check, lambda h, keys: ((), {"names": _LOUD_KEYS}), False),
     _Family("bandwidth", "bandwidth_multi", "bandwidth_batch", _BW_KEYS, _bandwidth_check,
@@ -328,6 +332,34 @@ _TAIL_FAMILIES = (
 def full_key_order():
     """all_key_order() and the keys of the tail families behind it: the order a result lists its metrics in."""
     return all_key_order() + tuple(k for f in _TAIL_FAMILIES for k in f.keys)
+
+
+def _csii_args(h, v, keys):
+    """-> ((one split frequency per degradation key (_key_splits; None: NaN csii_hf), n_fft, hop, band), {"names": the family's keys})."""
+    q = v if isinstance(v, dict) else {}
+    return (_key_splits(q, keys), q.get("n_fft"), q.get("hop"), q.get("band")), {"names": _CSII_KEYS}
+
+
+def _csii_check(h, v):
+    _dict_option("csii", v, ("n_fft", "hop", "band", "split"))
+    if v is not True and "n_fft" in v and v["n_fft"] is None:
+        raise ValueError("n_fft must be one of %s (leave it out for 16 ms segments)" % (B.PHASE_N_FFTS,))
+    (split, n_fft, hop, band), _ = _csii_args(h, v, ["k"])
+    _, _, fc = h.audio_metrics._csii_design(n_fft, hop, band)
+    h.audio_metrics._csii_splits(fc, split, 1)
+
+
+# The open end of the registry: the families added after _TAIL_FAMILIES was pinned, queued after it, their keys behind its keys.  A
+# new family's row goes at the end.
+_NEWER_FAMILIES = (
+    _Family("csii", "csii_multi", "csii_batch", _CSII_KEYS, _csii_check, lambda h, keys: _csii_args(h, h.csii, keys), True),
+)
+_ALL_FAMILIES = _FAMILIES + _LATER_FAMILIES + _TAIL_FAMILIES + _NEWER_FAMILIES
+
+
+def every_key_order():
+    """full_key_order() and the keys of the newer families behind it: the order a result lists its metrics in."""
+    return full_key_order() + tuple(k for f in _NEWER_FAMILIES for k in f.keys)
 
 
 def key_cutoff_hz(key):
@@ -406,7 +438,7 @@ class SSR_Eval_Helper:
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
                  quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None,
-                 distribution=None, coherence=None, auditory=None, modulation=None, loudness=None, bandwidth=None):
+                 distribution=None, coherence=None, csii=None, auditory=None, modulation=None, loudness=None, bandwidth=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -482,6 +514,14 @@ class SSR_Eval_Helper:
         section 24); a dict = `n_bands` (3 to 64; default 32), `band` ((lo_hz, hi_hz) of the centre frequencies), `env_rate` (800 to
         6400 Hz; default 1600), `range_db` (default 60), `kstar` (5 .. 8: a constant upper band instead of the adaptive one) and / or
         `split` (the same split frequency in Hz for every key, mp3 included).
+        csii (not in the reference): None = off; True = every key also gets csii, the coherence speech intelligibility index of the
+        output against the target (Kates & Arehart 2005: the coherence signal-to-distortion ratio per critical band up to 8.5 kHz,
+        weighted with the band importance of ANSI S3.5-1997; 1 = the output is a linear function of the target), csii_mid, the same
+        over the target's mid-level segments, i3, the intelligibility fitted to the low- and mid-level values, and csii_hf, csii
+        over the bands whose centre is at or above the key's own cutoff (key_cutoff_hz; mp3 keys and keys with no band above the
+        cutoff: NaN) - all invariant to the output's gain (AudioMetrics.csii_multi / csii_batch at evaluation_sr, DESIGN.md section
+        26); a dict = `n_fft` (256, 512, 1024 or 2048; default 16 ms), `hop` (default n_fft // 2), `band` ((lo_hz, hi_hz) of the band
+        centres kept) and / or `split` (the same split frequency in Hz for every key, mp3 included).
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -500,8 +540,8 @@ class SSR_Eval_Helper:
         # every family option is checked here, before the caller's settings are touched (the mel checks need audio_metrics)
         options = dict(lsd_split=lsd_split, stoi=stoi, waveform=waveform, mel=mel, mel_dtw=mel_dtw, quality=quality, pitch=pitch,
                        phase=phase, mrstft=mrstft, bss_sdr=bss_sdr, coherence=coherence, loudness=loudness,
-                       bandwidth=bandwidth, auditory=auditory, modulation=modulation)
-        for f in _FAMILIES + _LATER_FAMILIES + _TAIL_FAMILIES:
+                       bandwidth=bandwidth, auditory=auditory, modulation=modulation, csii=csii)
+        for f in _ALL_FAMILIES:
             if options[f.option] is not None:
                 f.check(self, options[f.option])
             setattr(self, f.option, options[f.option])
@@ -810,7 +850,7 @@ class SSR_Eval_Helper:
         queued = []
         if all_proc:
             same_keys = multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items)))
-            for f in _FAMILIES + _LATER_FAMILIES + _TAIL_FAMILIES:
+            for f in _ALL_FAMILIES:
                 if getattr(self, f.option) is None:
                     continue
                 if multi and (same_keys or not f.per_key):
@@ -1007,7 +1047,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = full_key_order()
+        order_keys = every_key_order()
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

@@ -39,6 +39,9 @@ _SPEC_NAMES = ("bw_hz", "edge_hz", "centroid_hz", "hf_db")                      
 _SPEC_PAIR_NAMES = ("bw_diff", "edge_diff", "centroid_diff", "hf_diff", "ltas_dist", "ltas_max")     # estimate against target
 _NSIM_NAMES = ("nsim", "nsim_hf", "nsim_lf")                                              # the columns of ssr_auditory
 _MOD_NAMES = ("srmr", "srmr_diff", "mod_dist", "mod_dist_hf", "mod_dist_lf")              # the estimate's srmr, then ssr_modulation's pair columns
+_CSII_NAMES = ("csii", "csii_low", "csii_mid", "csii_high", "i3", "csii_hf", "csii_mid_hf")      # columns 0 .. 5 and 7 of ssr_csii
+_CSII_COLUMNS = (0, 1, 2, 3, 4, 5, 7)
+_CSII_COUNT_NAMES = ("n_segments", "n_low", "n_mid", "n_high")                            # columns 9 .. 12
 
 
 def which_mask(which, names):
@@ -1153,6 +1156,78 @@ class AudioMetrics:
         split_hz = _tile_key_splits(split_hz, K, n)
         return _regroup(self.modulation_batch(ests, tgts, split_hz, n_bands, band, env_rate, range_db, kstar, names, return_spectrum, resident,
                                               True), n, K, deferred)
+
+    # ---- csii: how much of the estimate would a listener understand?  The coherence speech intelligibility index of
+    # Kates & Arehart (2005): §20's magnitude-squared coherence as a signal-to-distortion ratio per critical band up to 8.5 kHz,
+    # weighted with the band importance of ANSI S3.5-1997, taken separately over the target's high-, mid- and low-level segments (the
+    # low-level ones carry the consonants), and the fitted three-level index I3
+    @staticmethod
+    def _csii_names(names):
+        """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
+        return _names_asked(names, _CSII_NAMES)
+
+    @staticmethod
+    def _csii_splits(fc, split, n):
+        """The first band whose centre frequency is at or above the split of n pairs, in [0, len(fc)]: split = None (no split: -1 for
+        every pair), one frequency in Hz for every pair, or a list of one per pair (None: -1 for that pair)."""
+        return _split_indices(split, n, lambda f: int(np.searchsorted(fc, f, side="left")))
+
+    def _csii_design(self, n_fft, hop, band):
+        """-> (n_fft, hop, f_c): every option checked, nothing queued."""
+        n_fft, hop = B.check_csii_frames(self.rate, n_fft, hop)
+        return n_fft, hop, B.csii_design(self.rate, n_fft, band)[0]
+
+    def csii(self, est, target, split_hz=None, n_fft=None, hop=None, band=None, names=None, return_bands=False, return_counts=False):
+        """{'csii', 'csii_low', 'csii_mid', 'csii_high', 'i3', 'csii_hf', 'csii_mid_hf'} of one (estimate, target) pair at self.rate:
+        the coherence speech intelligibility index over all segments and over the target's low- (-30 .. -10 dB re its overall level),
+        mid- (-10 .. 0 dB) and high-level (>= 0 dB) segments, each in [0, 1] with 1 for an estimate that is a linear function of the
+        target; i3 = 1 / (1 + exp(-(-3.47 + 1.84 csii_low + 9.99 csii_mid))), the fitted intelligibility; csii_hf / csii_mid_hf: csii
+        and csii_mid over the critical bands whose centre is at or above split_hz (NaN without split_hz or where no such band
+        exists).  Invariant to the estimate's gain.  n_fft: None = 16 ms (backend.csii_default_nfft), or 256, 512, 1024 or 2048;
+        hop: None = n_fft // 2; band: None or (lo_hz, hi_hz), the band centres kept; names: None, or the result keys wanted.
+        return_bands: also 'band_values' [4, n_bands], the band values of the sets all, low, mid, high, and 'centre_hz';
+        return_counts: also 'n_segments', 'n_low', 'n_mid', 'n_high'.  A set of fewer than two segments and a digitally silent
+        target: NaN (i3: NaN where csii_low or csii_mid is)."""
+        return self.csii_batch([est], [target], split_hz, n_fft, hop, band, names, return_bands, return_counts)[0]
+
+    def csii_batch(self, ests, targets, split_hz=None, n_fft=None, hop=None, band=None, names=None, return_bands=False, return_counts=False,
+                   resident=False, deferred=False):
+        """csii() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals, read
+        in their own dtype: one ssr_csii call per (target dtype, estimate dtype) group).  A target object passed for several pairs is
+        classified once.  split_hz: None, one frequency for every pair, or a list of one per pair (None: that pair's two _hf values
+        are NaN).  deferred: as evaluation_batch."""
+        n_fft, hop, fc = self._csii_design(n_fft, hop, band)
+        if not isinstance(return_bands, bool) or not isinstance(return_counts, bool):
+            raise ValueError("return_bands and return_counts must be True or False")
+        keys = self._csii_names(names)
+        n = min(len(ests), len(targets))
+        splits = self._csii_splits(fc, split_hz, n)
+
+        def call(tgts, es, index, idx):
+            return B.csii_metrics(tgts, es, index, self.rate, n_fft, hop, band, [splits[i] for i in idx], return_bands, self._device, deferred=True)
+
+        def dicts(vals):
+            rows, bands = vals
+            out = []
+            for j, row in enumerate(rows):
+                d = {k: float(row[c]) for k, c in zip(_CSII_NAMES, _CSII_COLUMNS) if k in keys}
+                if return_bands:
+                    d["band_values"], d["centre_hz"] = np.array(bands[j]), np.array(fc)
+                if return_counts:
+                    d.update({k: int(row[9 + c]) for c, k in enumerate(_CSII_COUNT_NAMES)})
+                out.append(d)
+            return out
+        _check_1d(list(ests[:n]) + list(targets[:n]))
+        return self._pairs((call, dicts), ests[:n], targets[:n], resident, deferred, by_dtype=True, per_pair=True)
+
+    def csii_multi(self, ests_by_key, targets, split_hz=None, n_fft=None, hop=None, band=None, names=None, return_bands=False,
+                   return_counts=False, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
+        to each other in one call and the target is classified once."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        split_hz = _tile_key_splits(split_hz, K, n)
+        return _regroup(self.csii_batch(ests, tgts, split_hz, n_fft, hop, band, names, return_bands, return_counts, resident, True), n, K, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
