@@ -4,11 +4,12 @@
 // Why: the 256-thread engine of ssr_stft.h runs a frame on four waves in lock step - eight s_barrier per frame (14 % of
 // the kernel, measured), three LDS exchanges, and four waves that all stall together.  Here a frame belongs to one wave:
 //   * 64 lanes x 32 points.  The first pass is a radix-32 DFT done entirely IN the lane's registers (4 x 8 with
-//     compile-time twiddles), so the transform is 32 x 8 x 8 = three passes and only TWO exchanges through LDS;
+//     compile-time twiddles), so the transform is 32 x 8 x 8 = three passes and only TWO exchanges through LDS; k_stft_wave
+//     folds the window into its first radix-4 layer and the inner twiddles into its radix-8 butterflies (ssr_dft32_win);
 //   * exchanges are ordered by the hardware (the DS operations of one wave execute in order), so a "phase boundary" is a
 //     compiler-only wave-scope fence: no s_barrier, no s_waitcnt between a wave's writes and its reads;
-//   * what a lane needs every frame is loop-invariant and stays in registers: its 16 window values
-//     (w[m + N/2] = 1/2 - w[m]) and the 3 twiddles of the second pass (t, t^2, t^4 of t = w^(8 (l mod 32)), which does not
+//   * what a lane needs every frame is loop-invariant: its 16 window values (w[m + N/2] = 1/2 - w[m]; k_stft_wave forms them
+//     from two per-lane constants, ssr_window_from_lane) and the 3 twiddles of the second pass (t, t^2, t^4 of t = w^(8 (l mod 32)), which does not
 //     depend on the butterfly); the first pass needs none.  Only the third pass loads 3 table twiddles per butterfly.
 //     Both radix-8 passes run the twiddles INSIDE the butterfly (ssr_bfly8_tw: three layers of fused radix-2 butterflies);
 //   * the per-frame LSD reduction is a wave shuffle, the silent-frame vote a ballot.
@@ -25,7 +26,8 @@
 // (SSR_WPHASE / SSR_WAVE_SYNC: ssr_block.h)
 
 constexpr int SSR_W_N = 2048, SSR_W_L = 64, SSR_W_P = 32;     // points, lanes, points per lane
-constexpr int SSR_W_TWP = 7 * 32 + 12 * 64;                   // lane-ordered twiddle copies behind the table (= SSR_WAVE_TWP)
+constexpr int SSR_W_WCS_OFF = 7 * 32 + 12 * 64;               // lane-ordered twiddle copies behind the table, then the 64 window constants
+constexpr int SSR_W_TWP = SSR_W_WCS_OFF + 64;                 // (= SSR_WAVE_WCS_OFF, SSR_WAVE_TWP of ssr_tables.h: tu_stft.inc asserts it)
 SSR_DEV int ssr_wpad(int i) { return i + (i >> 5); }            // lane stride 32 -> 33 doubles: conflict-free ds_*_b64
 constexpr int SSR_W_PN = SSR_W_N + (SSR_W_N >> 5) + 1;
 
@@ -85,6 +87,73 @@ template <typename T, int NZ = 32> SSR_DEV void ssr_dft32(cx<T>* v) {
   }
   SSR_UNROLL for (int k1 = 0; k1 < 4; ++k1) ssr_bfly8(v + 8 * k1);
 }
+
+// Radix-2 butterfly with the COMPILE-TIME twiddle W = W32^M on the second input:  a, b  <-  a + W b,  a - W b.
+// W = -i (M = 8, the only trivial one among the exponents in use) is plain additions, selected on the exponent: an fma with a literal
+// 0 or 1 does not fold without fast-math; every other exponent is ssr_bfly2_tw with literal operands.
+template <int M, typename T> SSR_DEV void ssr_bfly2_w32(cx<T>& a, cx<T>& b) {
+  static_assert(M > 0 && M < 16, "the exponents of ssr_bfly8_w32<1..3> are 1..15 (ssr_w32 holds 0..21)");
+  if constexpr (M == 8) { const cx<T> r = cmul_negi(b); const cx<T> p = cadd(a, r); b = csub(a, r); a = p; }
+  else ssr_bfly2_tw(a, b, ssr_w32<T>(M));
+}
+// ssr_bfly8_tw (ssr_fft.h) with the compile-time base twiddle t = W32^K1:  t^4, t^2, -i t^2, t, -i t, s = t W8, -i s
+template <int K1, typename T> SSR_DEV void ssr_bfly8_w32(cx<T>* v) {
+  cx<T> a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3], b0 = v[4], b1 = v[5], b2 = v[6], b3 = v[7];
+  ssr_bfly2_w32<4 * K1>(a0, b0);
+  ssr_bfly2_w32<4 * K1>(a1, b1);
+  ssr_bfly2_w32<4 * K1>(a2, b2);
+  ssr_bfly2_w32<4 * K1>(a3, b3);
+  ssr_bfly2_w32<2 * K1>(a0, a2);          // c0, d0
+  ssr_bfly2_w32<2 * K1>(a1, a3);          // c1, d1
+  ssr_bfly2_w32<2 * K1 + 8>(b0, b2);      // e0, f0
+  ssr_bfly2_w32<2 * K1 + 8>(b1, b3);      // e1, f1
+  ssr_bfly2_w32<K1>(a0, a1);              // X0, X4
+  ssr_bfly2_w32<K1 + 8>(a2, a3);          // X2, X6
+  ssr_bfly2_w32<K1 + 4>(b0, b1);          // X1, X5
+  ssr_bfly2_w32<K1 + 12>(b2, b3);         // X3, X7
+  v[0] = a0; v[1] = b0; v[2] = a2; v[3] = b2; v[4] = a1; v[5] = b1; v[6] = a3; v[7] = b3;
+}
+// Lane l's 16 half-window values 0.5 hann[l + 64 r] = 1/4 - 1/4 cos(a_l + 2 pi r / 32) = 1/4 - (CA cos_r - SA sin_r), r < 16, from
+// cs = (CA, SA) = (cos, sin)(a_l) / 4, a_l = 2 pi l / N (ssr_tables.h, long double) and the compile-time (cos_r, sin_r): two fused
+// multiply-adds each, within 3 ulp of 1/4 of the exact value (two roundings below 1/2, the roundings of CA, SA, cos_r, sin_r; the
+// table's values are within 1/2 ulp of THEIR size).  k_stft_wave computes them every frame instead of loading them: 16 vector-memory
+// instructions per frame pair less on the CU-shared address unit, 30 FP64 instructions more on the SIMD's own pipe.
+template <typename T> SSR_DEV void ssr_window_from_lane(T* wl, cx<T> cs) {
+  SSR_UNROLL for (int r = 0; r < SSR_W_P / 2; ++r) {
+    const cx<T> e = ssr_w32<T>(r);                     // (cos_r, -sin_r)
+    if (r == 0) wl[r] = (T)0.25 - cs.x;
+    else if (r == 8) wl[r] = (T)0.25 + cs.y;
+    else wl[r] = ssr_fma(-cs.y, e.y, ssr_fma(-cs.x, e.x, (T)0.25));
+  }
+}
+// ssr_dft32 of the WINDOWED packed frame v[r] = (pa[r] + i pb[r]) w[r], w[r] = wl[r] (r < 16), 1/2 - wl[r - 16] (r >= 16), with the
+// window folded into the first radix-4 layer (t0 +- t2 = fma(+-x2, w2, x0 w0): 4 multiplies + 4 fused multiply-adds where the
+// separate window pass costs 8 multiplies + 4 additions) and the inner twiddles W32^(n2 k1) folded into the radix-8 butterflies
+// (ssr_bfly8_w32; k1 = 0 has none: ssr_bfly8).  The same register order as ssr_dft32 on exit.
+// Two halves, so that a caller can issue work between them: once the first layer is done pa / pb / wl are dead (k_stft_wave requests
+// the next pass's table values there).
+template <typename T> SSR_DEV void ssr_dft32_win_layer1(cx<T>* v, const float* pa, const float* pb, const T* wl) {
+  SSR_UNROLL for (int n2 = 0; n2 < 8; ++n2) {
+    const T w0 = wl[n2], w1 = wl[8 + n2], w2 = (T)0.5 - w0, w3 = (T)0.5 - w1;              // w[m + N/2] = 1/2 - w[m]
+    const cx<T> x2 = {(T)pa[16 + n2], (T)pb[16 + n2]}, x3 = {(T)pa[24 + n2], (T)pb[24 + n2]};
+    const cx<T> t0 = {(T)pa[n2] * w0, (T)pb[n2] * w0}, t1 = {(T)pa[8 + n2] * w1, (T)pb[8 + n2] * w1};
+    const cx<T> b0 = {ssr_fma(x2.x, w2, t0.x), ssr_fma(x2.y, w2, t0.y)};
+    const cx<T> b1 = {ssr_fma(-x2.x, w2, t0.x), ssr_fma(-x2.y, w2, t0.y)};
+    const cx<T> b2 = {ssr_fma(x3.x, w3, t1.x), ssr_fma(x3.y, w3, t1.y)};
+    const cx<T> b3 = cmul_negi(cx<T>{ssr_fma(-x3.x, w3, t1.x), ssr_fma(-x3.y, w3, t1.y)});
+    v[n2] = cadd(b0, b2); v[8 + n2] = cadd(b1, b3); v[16 + n2] = csub(b0, b2); v[24 + n2] = csub(b1, b3);
+  }
+}
+template <typename T> SSR_DEV void ssr_dft32_win_rest(cx<T>* v) {
+  ssr_bfly8(v);
+  ssr_bfly8_w32<1>(v + 8);
+  ssr_bfly8_w32<2>(v + 16);
+  ssr_bfly8_w32<3>(v + 24);
+}
+template <typename T> SSR_DEV void ssr_dft32_win(cx<T>* v, const float* pa, const float* pb, const T* wl) {
+  ssr_dft32_win_layer1(v, pa, pb, wl);
+  ssr_dft32_win_rest(v);
+}
 // frequency held by register rho after ssr_dft32
 SSR_DEV constexpr int ssr_dft32_freq(int rho) { return (rho >> 3) + 4 * (rho & 7); }
 
@@ -95,11 +164,11 @@ template <typename T, bool SUMS> struct SsrWaveRegs {
   cx<T> v[SSR_W_P];          // the lane's 32 points
   T tx[SSR_W_P];             // SPLIT exchange: real parts read back while the imaginary parts are still to be written
   float pa[SSR_W_P], pb[SSR_W_P];   // samples of the NEXT frame, requested one frame ahead
-  T wl[SSR_W_P / 2];         // 0.5 * hann[tid + 64 r], r < 16 of the next frame: requested at the TOP of the epilogue, ahead of
-                             // the magnitude stores (behind them in the in-order memory counter every frame would wait for
-                             // the stores' acknowledgements)
-  cx<T> tw1[3];              // t, t^2, t^4 of t = w^(8 (tid mod 32)): requested while the first exchange is in flight
-  cx<T> tw2[12];             // w^j, w^2j, w^4j of the four third-pass butterflies: requested while the second one is
+  cx<T> wcs;                 // (cos, sin)(2 pi tid / N) / 4, loaded once per chunk: the lane's window values come from it (ssr_window_from_lane)
+  cx<T> tw1[3];              // t, t^2, t^4 of t = w^(8 (tid mod 32)): requested while the first exchange is in flight (k_stft_wave: in
+                             // pass 0, behind its first layer)
+  cx<T> tw2[12];             // w^j, w^2j, w^4j of the four third-pass butterflies: requested while the second one is (k_stft_wave: at
+                             // the top of pass 1)
   double lsd_total;          // lane 0: sum over the chunk's frames of the per-frame LSD
 };
 
@@ -212,14 +281,24 @@ SSR_DEV int ssr_w_rd_paired(const SsrWavePBase& B, int i) {
 #define SSR_W_LOAD_TW2 { const unsigned l_ = SSR_UIDX(tid & 63); \
                          SSR_UNROLL for (int i = 0; i < 12; ++i) R.tw2[i] = VT.at(l_ + (SSR_W_N + 224 + 64 * i)); }
 #define SSR_W_FFT_TAIL(blk, BLK0, regs, L, EXTRA2)                                                                        \
-  SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, SSR_W_EXCHANGE(blk, regs, L, st1, ssr_w_off_st1, ld8, ssr_w_off_ld8, SSR_W_LOAD_TW2 EXTRA2))
+  SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, SSR_W_LOAD_TW1, , SSR_W_EXCHANGE(blk, regs, L, st1, ssr_w_off_st1, ld8, ssr_w_off_ld8, SSR_W_LOAD_TW2 EXTRA2))
 #define SSR_W_FFT_TAIL_PAIRED(blk, BLK0, regs, L)                                                                         \
-  SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, SSR_W_EXCHANGE_G(blk, regs, L, st1, ssr_w_off_st1, ssr_wave_pbases, SSR_W_RIDX_PAIRED, SSR_W_LOAD_TW2_PAIRED))
-#define SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, EXCH2)                                                                   \
+  SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, SSR_W_LOAD_TW1, , SSR_W_EXCHANGE_G(blk, regs, L, st1, ssr_w_off_st1, ssr_wave_pbases, SSR_W_RIDX_PAIRED, SSR_W_LOAD_TW2_PAIRED))
+// The paired tail with both table requests A WHOLE PASS ahead of their waits (k_stft_wave): R.tw1 is requested by the CALLER's pass 0,
+// once its first layer has consumed the prefetched samples (64 registers free), R.tw2 at the top of pass 1 (the 64
+// registers of R.tx are dead from the end of the first exchange to the second one's first read).  Requested inside the exchanges
+// (SSR_W_FFT_TAIL_PAIRED) the values are awaited some 65 instructions - nearly all of them DS operations - after they were asked for.
+#define SSR_W_FFT_TAIL_PAIRED_EARLY(blk, BLK0, regs, L)                                                                   \
+  SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, , SSR_SCHED_BARRIER(); SSR_W_LOAD_TW2_PAIRED; SSR_SCHED_BARRIER(),                \
+                    SSR_W_EXCHANGE_G(blk, regs, L, st1, ssr_w_off_st1, ssr_wave_pbases, SSR_W_RIDX_PAIRED, ))
+// LOAD1: the request of R.tw1, issued in the first exchange (empty: the caller has requested it); EARLY2: statements at the top of
+// pass 1 (the request of R.tw2, where EXCH2 does not make it)
+#define SSR_W_FFT_TAIL_X(blk, BLK0, regs, L, LOAD1, EARLY2, EXCH2)                                                    \
   blk = BLK0; ssr_launder(blk);                                                                                       \
-  SSR_W_EXCHANGE(blk, regs, L, st0, ssr_w_off_st0, ld8, ssr_w_off_ld8, SSR_W_LOAD_TW1);                               \
+  SSR_W_EXCHANGE(blk, regs, L, st0, ssr_w_off_st0, ld8, ssr_w_off_ld8, LOAD1);                                        \
   /* pass 1: four radix-8 butterflies, base twiddle t = w^(8 (j mod 32)) - the same for every butterfly of the lane */\
   SSR_WPHASE(blk, regs, {                                                                                             \
+    EARLY2;                                                                                                           \
     const cx<T> s1_ = ssr_tw_w8(R.tw1[0]);                                                                            \
     SSR_UNROLL for (int b = 0; b < 4; ++b) ssr_bfly8_tw(R.v + 8 * b, R.tw1[0], R.tw1[1], R.tw1[2], s1_);              \
   });                                                                                                                 \
@@ -292,7 +371,6 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
   const int mask = SUMS ? p.metric_mask : (p.metric_mask & SSR_M_LSD);
   const bool want_lsd = mask & SSR_M_LSD;
   const SsrView<float> va(sa, n), vb(sb, n);
-  const SsrView<T> vw(p.window, N);
   const SsrView<cx<T>> vt(p.tw, N + SSR_W_TWP);
 
   double* lsum = reinterpret_cast<double*>(lds_base + ssr_stft_wave_sums_offset<T, SPLIT>());   // [6][64], SUMS only
@@ -303,31 +381,35 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
     if (tid == 0) L.sc1[0] = 0.0;
     if (u0 < u1) {
       ssr_wave_prefetch<T>(p, R, tid, va, vb, u0, n, n_frames);
-      SSR_UNROLL for (int r = 0; r < SSR_W_P / 2; ++r) R.wl[r] = vw.at(SSR_UIDX(tid + 64 * r));
+      R.wcs = vt.at(SSR_UIDX(tid) + (SSR_W_N + SSR_W_WCS_OFF));
     }
     SSR_VMEM_DRAIN();
   });
 
   BLK blk0 = blk;
   for (int u = u0, it = 0; u < u1; u += S, ++it) {
-    // The lane's table values (window, twiddles) and addresses are loop-invariant, and 128 + 64 registers of data and
+    // The lane's table values (twiddles) and addresses are loop-invariant, and 128 + 64 registers of data and
     // prefetched samples leave no room to keep them: with the lane index opaque the optimiser cannot hoist them out of the
     // loop (it would, and then shuffle some 250 values through the accumulator registers every frame).  Table values are
-    // re-requested from L1 / L2 a phase before they are needed; LDS slots are four per-lane bases plus immediates.
+    // re-requested from L1 / L2 a pass before they are needed; LDS slots are four per-lane bases plus immediates.
     blk = blk0; ssr_launder(blk);
+#define VT vt
     // ---- pass 0: window, radix-32 DFT in registers (Stockham pass with stride 1: no twiddle).  Lane 0 also closes the
     // previous frame's LSD.
     SSR_WPHASE(blk, regs, {
       ssr_wave_flags(R, tid, L.nz, it & 1);            // silent-frame votes of this unit, read by its epilogue
-      SSR_UNROLL for (int r = 0; r < SSR_W_P; ++r) {
-        const T w = (r < SSR_W_P / 2) ? R.wl[r] : (T)0.5 - R.wl[r - SSR_W_P / 2];       // w[m + N/2] = 1/2 - w[m]
-        R.v[r] = {(T)R.pa[r] * w, (T)R.pb[r] * w};
-      }
-      ssr_dft32(R.v);
+      // (lane 0's branch first: behind the transform it splits the phase, and the first layer sinks below the table request)
       if (want_lsd && it > 0 && tid == 0) R.lsd_total += sqrt(L.sc1[0] / (double)F);
+      T wl[SSR_W_P / 2];
+      ssr_touch(R.wcs.x); ssr_touch(R.wcs.y);          // a product of this point: hoisted out of the loop the 64 window values spill
+      ssr_window_from_lane(wl, R.wcs);
+      ssr_dft32_win_layer1(R.v, R.pa, R.pb, wl);
+      SSR_SCHED_BARRIER();                             // pa / pb are dead: pass 1's twiddles, a whole pass ahead of their wait
+      SSR_W_LOAD_TW1;
+      SSR_SCHED_BARRIER();
+      ssr_dft32_win_rest(R.v);
     });
-#define VT vt
-    SSR_W_FFT_TAIL_PAIRED(blk, blk0, regs, L);
+    SSR_W_FFT_TAIL_PAIRED_EARLY(blk, blk0, regs, L);
 #undef VT
     // register 8 b + q holds Z[j_b + 256 q], j = tid, 64 + tid, 192 - tid, 256 - tid (lane 0: 0, 64, 192, 128) - every
     // partner Z[2048 - k] of the lane's bins is in the lane's own registers (see SSR_W_FFT_TAIL_PAIRED).
@@ -343,7 +425,7 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
       // The two signals are requested at different times: 64 + 16 requests at once stop the wave at the 64th until the oldest
       // ones have returned, i.e. expose the latency they are here to hide.
       // All 128 data registers are live here, and a quarter of them is released per butterfly group - the first
-      // signal is requested after group 0, the second after group 1, the window (the shortest way: L1 / L2) after group 2
+      // signal is requested after group 0, the second after group 1
       SSR_SCHED_BARRIER();
       double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       const int par = it & 1;
@@ -376,7 +458,7 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
       // the mask is the variant's full set - no zero forcing, no per-bin test of the mask, and the float32 arithmetic of a
       // bin pair runs as packed instructions (ssr_pair_bins2_fast).  The wave-uniform choice is made ONCE per frame, outside
       // the loop: taken per bin it split the epilogue into 48 basic blocks with two scalar branches each.
-      constexpr int PF1 = SUMS ? 1 : 0;    // the butterfly group after which the first signal is requested (then the second, then the window)
+      constexpr int PF1 = SUMS ? 1 : 0;    // the butterfly group after which the first signal is requested (then the second)
       auto bins = [&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
         SSR_UNROLL for (int b = 0; b < 4; ++b) SSR_UNROLL for (int q0 = 0; q0 < 4; q0 += G) {
@@ -417,11 +499,6 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
           if (b == PF1 + 1 && q0 + G == 4) {
             SSR_SCHED_BARRIER();
             ssr_wave_prefetch<T, 2>(p, R, tid, va, vb, u + S, n, n_frames);
-            SSR_SCHED_BARRIER();
-          }
-          if (b == PF1 + 2 && q0 + G == 4) {
-            SSR_SCHED_BARRIER();
-            SSR_UNROLL for (int r = 0; r < SSR_W_P / 2; ++r) R.wl[r] = vw.at(SSR_UIDX(tid + 64 * r));
             SSR_SCHED_BARRIER();
           }
         }

@@ -58,7 +58,8 @@ inline SsrEngine ssr_pick_wave_engine(int n_fft) {
   return w;
 }
 
-constexpr int SSR_WAVE_N = 2048, SSR_WAVE_TWP = 7 * 32 + 12 * 64;   // wave engines: transform length, lane-ordered twiddle copies
+// wave engines: transform length; lane-ordered twiddle copies and k_stft_wave's 64 window constants behind the table
+constexpr int SSR_WAVE_N = 2048, SSR_WAVE_WCS_OFF = 7 * 32 + 12 * 64, SSR_WAVE_TWP = SSR_WAVE_WCS_OFF + 64;
 constexpr int SSR_WAVE24_N = 1536, SSR_WAVE24_TWP = 2 * 9 * 64;     // the 24-points-per-lane variant (ssr_fft24.h)
 
 template <typename T> struct SsrTables {
@@ -153,6 +154,12 @@ template <typename T> bool ssr_build_tables_for(int n_fft, SsrEngine eng, SsrTab
     for (int b = 0; b < 4; ++b)
       for (int k = 0; k < 3; ++k)
         for (int l = 0; l < 64; ++l) t.tw[N + 224 + 64 * (3 * b + k) + l] = t.tw[(l + 64 * b) << k];
+    //   [N + SSR_WAVE_WCS_OFF + l]    = (cos, sin)(2 pi l / N) / 4, l < 64: lane l of k_stft_wave forms its half-window values from it,
+    //                                   0.5 hann[l + 64 r] = 1/4 - (CA cos_r - SA sin_r) with the compile-time angles 2 pi r / 32
+    for (int l = 0; l < 64; ++l) {
+      const long double ang = 2.0L * SSR_PI_L * l / N;
+      t.tw[N + SSR_WAVE_WCS_OFF + l] = {(T)(0.25L * cosl(ang)), (T)(0.25L * sinl(ang))};
+    }
   }
   if (t.eng.bluestein) {
     // inner (Bluestein) length q: n_fft itself, or n_fft / R under a radix-R outer step

@@ -12,7 +12,7 @@
 #include "ssr_stft_r3_rot.h"
 
 typedef SSR_TU_T TT;
-static_assert(SSR_W_N == SSR_WAVE_N && SSR_W_TWP == SSR_WAVE_TWP, "ssr_tables.h appends what ssr_stft_wave.h reads");
+static_assert(SSR_W_N == SSR_WAVE_N && SSR_W_TWP == SSR_WAVE_TWP && SSR_W_WCS_OFF == SSR_WAVE_WCS_OFF, "ssr_tables.h appends what ssr_stft_wave.h reads");
 static_assert(SSR_W24_N == SSR_WAVE24_N && SSR_W24_TWP == SSR_WAVE24_TWP, "ssr_tables.h appends what ssr_fft24.h reads");
 
 // Minimum waves per SIMD asked of the register allocator.  The 2048-point direct kernel without running

@@ -1,9 +1,11 @@
 // Developer micro-benchmark (gfx950): the ceiling of a kernel with k_stft_wave's FP64 instruction mix and LDS exchange pattern and
 // NO global memory.  One "unit" = what the hot loop of k_stft_wave<double, false, true, true> issues per frame
 // pair (static count of its loop body, tools/isa_stats.py - the transform blocks and the both-frames-loud epilogue, with the radix-8
-// passes as fused twiddled radix-2 butterflies, profiles/fft_fma_notes.md section 1: 326 v_add_f64, 84 v_mul_f64, 700 v_fma(c)_f64,
-// 64 v_cvt_f64_f32, 80 ds_write2_b64, 64 ds_read2_b64, four LDS exchanges; before the fused passes: 700 / 234 / 300):
-// here 328 + 84 + 700 + 64 FP64 instructions on 32 independent registers
+// passes as fused twiddled radix-2 butterflies, the window and the inner twiddles of the in-register radix-32 pass folded into fused
+// multiply-adds and the window values formed by two fused multiply-adds each, profiles/stft_pass0_notes.md section 1: 204 v_add_f64,
+// 44 v_mul_f64, 864 v_fma(c)_f64, 64 v_cvt_f64_f32, 80 ds_write2_b64, 64 ds_read2_b64, four LDS exchanges; before the windowed pass:
+// 326 / 84 / 700, before the fused passes: 700 / 234 / 300):
+// here 204 + 44 + 864 + 64 FP64 instructions on 32 independent registers
 // (no dependent pair closer than 32 instructions: ideal ILP) in four phases, each followed by 20 ds_write2_b64, a wait, 16
 // ds_read2_b64 and a wait - one wave per workgroup with its own LDS slice, as in the kernel.  Prints units/s for 1, 2 and 3 waves
 // per SIMD over the whole chip, the FP64 instruction rate per SIMD, and the sustained clock; second part: the issue rate of
@@ -32,10 +34,11 @@ template <bool WITH_LDS, int MODE = 0> __global__ __launch_bounds__(64) void k_m
 #pragma unroll
       for (int g = 0; g < 31; ++g) {
 #pragma unroll
-        for (int k = 0; k < 2 + (g < 20); ++k) asm volatile("v_add_f64 %0, %0, %1" : "+v"(x[(g * 10 + k) & 31]) : "v"(c0));
-        if (g < 21) asm volatile("v_mul_f64 %0, %0, %1" : "+v"(x[(g * 10 + 3) & 31]) : "v"(c1));
+        for (int k = 0; k < 1 + (g < 20); ++k) asm volatile("v_add_f64 %0, %0, %1" : "+v"(x[(g * 10 + k) & 31]) : "v"(c0));
+        if (g < 11) asm volatile("v_mul_f64 %0, %0, %1" : "+v"(x[(g * 10 + 3) & 31]) : "v"(c1));
 #pragma unroll
-        for (int k = 4; k < 9 + (g < 20); ++k) asm volatile("v_fma_f64 %0, %0, %1, %2" : "+v"(x[(g * 10 + k) & 31]) : "v"(c1), "v"(c0));
+        for (int k = 4; k < 10; ++k) asm volatile("v_fma_f64 %0, %0, %1, %2" : "+v"(x[(g * 10 + k) & 31]) : "v"(c1), "v"(c0));
+        if (g < 30) asm volatile("v_fma_f64 %0, %0, %1, %2" : "+v"(x[(g * 10 + 2) & 31]) : "v"(c1), "v"(c0));   // slot 2: free since the additions shrank
       }
 #pragma unroll
       for (int k = 0; k < 16; ++k) asm volatile("v_cvt_f64_f32 %0, %1" : "=v"(x[(ph * 16 + k) & 31]) : "v"(f[k & 3]));
@@ -121,7 +124,7 @@ int main() {
   unsigned long long* d;
   (void)hipMalloc(&d, 1 << 22);
   static unsigned long long h[1 << 18];
-  const int units = 2000, per_unit_f64 = 4 * ((31 * 2 + 20) + 21 + (31 * 5 + 20) + 16);      // 1176
+  const int units = 2000, per_unit_f64 = 4 * ((31 + 20) + 11 + (31 * 6 + 30) + 16);          // 1176
   for (int with_lds = 1; with_lds >= 0; --with_lds)
     for (int wps = 1; wps <= 3; ++wps) {
       const int blocks = 256 * 4 * wps;
