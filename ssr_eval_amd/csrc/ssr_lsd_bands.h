@@ -16,8 +16,14 @@
 // Registers: KG * NB float64 accumulators + KG running sums + KG frame totals.  NB = 2 (the LF / HF split, 12 VGPRs of
 // accumulators at KG = 3) and NB = SSR_MAX_BANDS (48 at KG = 3) are separate instantiations, so the common split does not pay the
 // occupancy of eight.  Device code only.
+//
+// Summation order.  The frame totals of an image are added in quanta of SSR_LSD_BANDS_Q rows that start at multiples of Q - rows in
+// row order inside a quantum, the quanta in order at the end - and a wave's run of rows is a whole number of quanta.  How many rows
+// a wave takes depends on the batch (its longest image and its size); the quanta do not, so an image has the same bits in any batch.
 #pragma once
 #include "ssr_stft.h"
+
+#define SSR_LSD_BANDS_Q 8                  // rows of a summation quantum
 
 struct SsrLsdBandsParams {
   const float* x;              // estimate images: key k of item i at x + k * x_plane + x_row[i] * pitch
@@ -27,8 +33,9 @@ struct SsrLsdBandsParams {
   const int32_t* n_rows;       // [n_items]
   const int32_t* edges;        // [n_keys * n_items][n_bands + 1], image v = k * n_items + i
   int64_t x_plane;
-  int F, pitch, n_bands, n_items, rows_per_chunk, n_chunks;
-  double* part;                // [n_keys * n_items][n_chunks][n_bands]: sum over the chunk's rows of the band's frame LSD
+  int F, pitch, n_bands, n_items, rows_per_chunk, n_chunks;       // rows_per_chunk: a multiple of SSR_LSD_BANDS_Q
+  int n_quanta;                // n_chunks * rows_per_chunk / SSR_LSD_BANDS_Q: quantum slots per image
+  double* part;                // [n_keys * n_items][n_quanta][n_bands]: sum over the quantum's rows of the band's frame LSD
 };
 
 // adds `v` to acc[b] (b in [0, NB): a lane-varying index) through a select chain; any other b drops it
@@ -131,26 +138,34 @@ __device__ __forceinline__ void ssr_lsd_bands_body(const SsrLsdBandsParams& p, i
         }
       }
     }
-  }
+    if ((t + 1) % SSR_LSD_BANDS_Q == 0 || t + 1 == t1) {   // the quantum ends (t0 is a multiple of Q; wave-uniform)
+      const int q = t / SSR_LSD_BANDS_Q;                   // < n_quanta: t < n_chunks * rows_per_chunk
 #pragma unroll
-  for (int g = 0; g < KG; ++g)
-    if (lane < nb) p.part[(((int64_t)(key0 + g) * p.n_items + item) * p.n_chunks + chunk) * nb + lane] = ft[g];
+      for (int g = 0; g < KG; ++g) {
+        if (lane < nb) p.part[(((int64_t)(key0 + g) * p.n_items + item) * p.n_quanta + q) * nb + lane] = ft[g];
+        ft[g] = 0.0;
+      }
+    }
+  }
 }
 
 struct SsrLsdBandsFinalizeParams {
   const double* part;          // as SsrLsdBandsParams::part
   const int32_t* n_rows;       // [n_items]
-  int n_chunks, n_bands, n_items, n_keys;
+  int n_quanta, n_bands, n_items, n_keys;
   double* out;                 // [n_items][n_keys][n_bands]
 };
 
-// one thread per (image, band): the chunk totals in chunk order, divided by T
+// one thread per (image, band): the totals of the image's own quanta in order, divided by T
 __device__ __forceinline__ void ssr_lsd_bands_finalize(const SsrLsdBandsFinalizeParams& p, int64_t idx) {
   const int nb = p.n_bands;
   const int64_t v = idx / nb;
   const int band = (int)(idx % nb);
   const int key = (int)(v / p.n_items), item = (int)(v % p.n_items);
+  const int T = p.n_rows[item];
+  int nq = (T + SSR_LSD_BANDS_Q - 1) / SSR_LSD_BANDS_Q;     // the slots the image's rows wrote
+  if (nq > p.n_quanta) nq = p.n_quanta;
   double s = 0.0;
-  for (int c = 0; c < p.n_chunks; ++c) s += p.part[(v * p.n_chunks + c) * nb + band];
-  p.out[((int64_t)item * p.n_keys + key) * nb + band] = s / (double)p.n_rows[item];
+  for (int q = 0; q < nq; ++q) s += p.part[(v * p.n_quanta + q) * nb + band];
+  p.out[((int64_t)item * p.n_keys + key) * nb + band] = s / (double)T;
 }

@@ -1,6 +1,10 @@
 // What the per-pair waveform metric families share (ssr_stoi.h, ssr_wave_metrics.h, ssr_quality.h, ssr_pitch.h, ssr_phase.h,
-// ssr_mrstft.h, ssr_bss.h, ssr_coherence.h, ssr_spectrum.h, ssr_auditory.h): estimate e is scored against target tgt_index[e], consecutive pairs that name one target form a run, and every
-// grid is a prefix sum of per-item counts (tiles, frames, chunks) that a workgroup finds its item in.  Compiles on the device
+// ssr_mrstft.h, ssr_bss.h, ssr_coherence.h, ssr_spectrum.h, ssr_auditory.h, ssr_loudness.h, ssr_modulation.h, ssr_csii.h): estimate e
+// is scored against target tgt_index[e], consecutive pairs that name one target form a run, and every
+// grid is a prefix sum of per-item counts (tiles, frames, chunks) that a workgroup finds its item in.  ssr_run_geometry_body builds
+// the prefixes of wave, quality, bss, coherence, spectrum (over its n_tgt + n_est signals) and csii; stoi, pitch, phase, mrstft,
+// auditory, loudness (signals, no pairs) and modulation (through ssr_auditory.h) build their own and share ssr_prefix_find.
+// Compiles on the device
 // and under SSR_HOST_EMU (tests/emu/*_emu.cpp).  A new family uses these and re-implements none of them; what stays its own is
 // its count function, its *Params struct (taken by value by its kernels: no common base) and its kernel bodies.
 #pragma once

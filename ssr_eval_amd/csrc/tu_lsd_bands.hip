@@ -34,9 +34,15 @@ static void launch_bands_kg(const SsrLsdBandsParams& p, bool vec, dim3 grid, hip
 }
 
 // the reduction + the finalisation; `edges_dev` already on the device, n_keys * n_items images
+// rows of a wave: ssr_wave_rows_per_wg's, rounded up to whole summation quanta
+static int band_rows_per_chunk(int max_rows, int64_t groups) {
+  return ssr_ceil_div(ssr_wave_rows_per_wg(max_rows, groups), SSR_LSD_BANDS_Q) * SSR_LSD_BANDS_Q;
+}
+
 static int launch_bands(SsrLsdBandsParams p, int n_keys, int kg, int max_rows, const int32_t* n_rows, double* out, hipStream_t s) {
-  p.rows_per_chunk = ssr_wave_rows_per_wg(max_rows, (int64_t)p.n_items * (n_keys / kg));
+  p.rows_per_chunk = band_rows_per_chunk(max_rows, (int64_t)p.n_items * (n_keys / kg));
   p.n_chunks = ssr_ceil_div(max_rows, p.rows_per_chunk);
+  p.n_quanta = p.n_chunks * (p.rows_per_chunk / SSR_LSD_BANDS_Q);
   const bool vec = ssr_images_vec16(p.x, p.y, p.pitch, p.x_plane);
   const dim3 grid((unsigned)((int64_t)(n_keys / kg) * p.n_items * p.n_chunks));
   const bool two = p.n_bands <= 2;        // the LF / HF split: 2 accumulators per key instead of SSR_MAX_BANDS
@@ -49,7 +55,7 @@ static int launch_bands(SsrLsdBandsParams p, int n_keys, int kg, int max_rows, c
     default: launch_bands_kg<1, SSR_MAX_BANDS>(p, vec, grid, s); break;
   }
   HIP_TRY(hipGetLastError());
-  SsrLsdBandsFinalizeParams f{p.part, n_rows, p.n_chunks, p.n_bands, p.n_items, n_keys, out};
+  SsrLsdBandsFinalizeParams f{p.part, n_rows, p.n_quanta, p.n_bands, p.n_items, n_keys, out};
   const int64_t n = (int64_t)n_keys * p.n_items * p.n_bands;
   hipLaunchKernelGGL(k_lsd_bands_finalize, dim3((unsigned)ssr_ceil_div(n, 256)), dim3(256), 0, s, f, n);
   HIP_TRY(hipGetLastError());
@@ -57,8 +63,9 @@ static int launch_bands(SsrLsdBandsParams p, int n_keys, int kg, int max_rows, c
 }
 
 static size_t part_bytes(int64_t n_images, int max_rows, int n_bands, int64_t groups) {
-  const int n_chunks = ssr_ceil_div(max_rows, ssr_wave_rows_per_wg(max_rows, groups));
-  return ssr_align256((size_t)n_images * n_chunks * n_bands * sizeof(double));
+  const int rows = band_rows_per_chunk(max_rows, groups);
+  const int n_quanta = ssr_ceil_div(max_rows, rows) * (rows / SSR_LSD_BANDS_Q);
+  return ssr_align256((size_t)n_images * n_quanta * n_bands * sizeof(double));
 }
 static size_t edges_bytes(int64_t n_images, int n_bands) { return ssr_align256((size_t)n_images * (n_bands + 1) * sizeof(int32_t)); }
 
@@ -84,7 +91,7 @@ extern "C" int ssr_spectrogram_lsd_bands(const float* est_sp, const int64_t* est
   hipStream_t s = (hipStream_t)stream;
   int32_t* e_dev = (int32_t*)(ws + pb);
   HIP_TRY(hipMemcpyAsync(e_dev, edges, (size_t)n_images * (n_bands + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  SsrLsdBandsParams p{est_sp, tgt_sp, est_frame_off, tgt_frame_off, n_rows, e_dev, 0, n_bins, n_bins, n_bands, n_images, 0, 0,
+  SsrLsdBandsParams p{est_sp, tgt_sp, est_frame_off, tgt_frame_off, n_rows, e_dev, 0, n_bins, n_bins, n_bands, n_images, 0, 0, 0,
                       (double*)ws};
   return launch_bands(p, 1, 1, max_rows, n_rows, out, s);
 }
@@ -138,7 +145,7 @@ static int pair_lsd_bands_impl(const ssr_plan* pl, const float* est, const doubl
   if (int rc = ssr_pair_images(pl, {len, frame_off, n_items, w.g}, est, est64, est_off, tgt, tgt_off, n_keys, w.im, ws, s)) return rc;
   SsrLsdBandsParams p{(float*)(ws + w.im.off_est), (float*)(ws + w.im.off_tgt), frame_off, frame_off, rows, e_dev,
                       (int64_t)(w.im.plane / sizeof(float)), pl->n_bins,
-                      ssr_mag_pitch(pl->n_bins), n_bands, n_items, 0, 0, (double*)(ws + w.off_part)};
+                      ssr_mag_pitch(pl->n_bins), n_bands, n_items, 0, 0, 0, (double*)(ws + w.off_part)};
   return launch_bands(p, n_keys, w.kg, max_T, rows, out, s);
 }
 
