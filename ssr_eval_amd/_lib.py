@@ -33,6 +33,7 @@ MODULATION_BANDS, MODULATION_MAX_BLOCKS = 8, 65536                              
 DISTRIBUTION_MAX_DIM, DISTRIBUTION_MAX_GAMMA, DISTRIBUTION_MAX_PAIR_ROWS = 1024, 8, 2048   # SSR_DISTRIBUTION_MAX_DIM, _MAX_GAMMA, _MAX_PAIR_ROWS
 DISTRIBUTION_PAIRWISE_WORKSPACE = 16640                                         # SSR_DISTRIBUTION_PAIRWISE_WORKSPACE
 CSII_BANDS, CSII_COLUMNS = 21, 13                                               # SSR_CSII_BANDS, SSR_CSII_COLUMNS
+ALIGN_MAX_LAG, ALIGN_COLUMNS = 4096, 4                                          # SSR_ALIGN_MAX_LAG, SSR_ALIGN_COLUMNS
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -179,6 +180,11 @@ CSII_SIGNATURES = {
     "ssr_csii_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i, _i]),
     "ssr_csii": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
+# name -> (restype, argtypes): exactly the symbols ssr_eval_amd/csrc/ssr_hip_align.h declares (include/ssr_hip.h includes it)
+ALIGN_SIGNATURES = {
+    "ssr_align_workspace_bytes": (_sz, [_vp, _i, _vp, _vp, _i, _i]),
+    "ssr_align": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
 
 _lib = None
 
@@ -199,7 +205,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(LOUDNESS_SIGNATURES.items()) + \
             list(SPECTRUM_SIGNATURES.items()) + list(AUDITORY_SIGNATURES.items()) + list(MODULATION_SIGNATURES.items()) + \
-            list(DISTRIBUTION_SIGNATURES.items()) + list(CSII_SIGNATURES.items()):
+            list(DISTRIBUTION_SIGNATURES.items()) + list(CSII_SIGNATURES.items()) + list(ALIGN_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -1708,6 +1708,90 @@ def csii_metrics(tgt_list, est_list, tgt_index, fs, n_fft=None, hop=None, band=N
         return _collected([_take(rows), _take(bands) if return_bands else (lambda: None)], deferred)
 
 
+# ---- delay estimation and compensation: a stage in front of the metrics ----------------------------------------------------
+ALIGN_MAX_LAG = _lib.ALIGN_MAX_LAG       # SSR_ALIGN_MAX_LAG
+ALIGN_LAG = 1024                         # the default search range in samples, either way
+ALIGN_COLUMNS = _lib.ALIGN_COLUMNS       # SSR_ALIGN_COLUMNS: delay, frac, corr, edge
+
+
+def check_align_lag(max_lag):
+    """max_lag as an int, or ValueError: an integer in [1, 4096] (the C ABI's own check)."""
+    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 1 <= int(max_lag) <= ALIGN_MAX_LAG:
+        raise ValueError("max_lag must be an integer in [1, %d]" % ALIGN_MAX_LAG)
+    return int(max_lag)
+
+
+def check_align_subsample(subsample):
+    """subsample as a bool, or ValueError."""
+    if not isinstance(subsample, (bool, np.bool_)):
+        raise ValueError("subsample must be True or False")
+    return bool(subsample)
+
+
+def align(tgt_list, est_list, tgt_index, max_lag=ALIGN_LAG, subsample=False, return_corr=False, device=None, deferred=False, shift=True):
+    """The delay of estimate e against target tgt_index[e] and the estimate with that delay taken out (ssr_align):
+    waveforms (float32 or float64; an estimate need NOT be as long as its target; targets of both dtypes are widened to float64,
+    estimates of both dtypes go through one call per dtype) -> (rows [n_est, 4] float64: delay d* in samples (positive: the estimate
+    is late), the parabola's sub-sample estimate frac in [-0.5, 0.5], the normalised correlation at d*, edge = 1 where |d*| = max_lag;
+    shifted: a list of n_est DEVICE tensors in each estimate's dtype and length, z[t] = y[t + d*] with zero fill - with subsample and
+    frac != 0 through a 33-tap windowed sinc at d* + frac -, views of one buffer per dtype that stay in HBM (None with shift=False);
+    c [n_est, 2 max_lag + 1], lag -max_lag first, or None without return_corr).  A silent or empty signal on either side, and a
+    correlation that is nowhere positive: delay 0, frac 0, edge 0, corr NaN, the estimate unchanged.  The delay found reaches the
+    shift through device memory: nothing waits on the host.  Device views of one buffer are read where they lie.  deferred: rows
+    and c are functions that return the arrays."""
+    L, subsample = check_align_lag(max_lag), check_align_subsample(subsample)
+    if not isinstance(return_corr, (bool, np.bool_)) or not isinstance(shift, (bool, np.bool_)):
+        raise ValueError("return_corr and shift must be True or False")
+    tgts, ests, idx = _signal_pair_index(tgt_list, est_list, tgt_index)
+    n_e = len(ests)
+    lib, dev = _gpu_call(device)
+    groups = {}
+    for e, w in enumerate(ests):
+        groups.setdefault(bool(_is_f64(w)), []).append(e)
+    shifted = [None] * n_e if shift else None
+    got = []
+    with torch.cuda.device(dev):
+        for f64, members in groups.items():
+            used = sorted({int(idx[e]) for e in members})
+            where = {t: j for j, t in enumerate(used)}
+            sub_idx = np.array([where[int(idx[e])] for e in members], dtype=np.int32)
+            tgt_side, est_side, tl, el = _placed_where_they_lie([tgts[t] for t in used], [ests[e] for e in members], sub_idx, dev)
+            n_t, n_g = len(used), len(members)
+            rows = torch.empty((n_g, ALIGN_COLUMNS), dtype=torch.float64, device=dev)
+            c = torch.empty((n_g, 2 * L + 1), dtype=torch.float64, device=dev) if return_corr else None
+            out, out_off = None, None
+            if shift:
+                out = torch.empty(int(el.sum()), dtype=torch.float64 if f64 else torch.float32, device=dev)
+                out_off = _h2d(_offsets(el), dev)
+                edges = np.concatenate(([0], np.cumsum(el))).astype(np.int64)
+                for j, e in enumerate(members):
+                    shifted[e] = out[edges[j]:edges[j + 1]]
+            lens, elens = tl.astype(np.int32), el.astype(np.int32)
+            as_p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+            ws_bytes = int(lib.ssr_align_workspace_bytes(as_p(lens), n_t, as_p(elens), as_p(sub_idx), n_g, L))
+            ws = _workspace(ws_bytes, dev)
+            lens_h, elens_h, idx_h = _host_i32(lens, dev), _host_i32(elens, dev), _host_i32(sub_idx, dev)
+            _lib.check(lib.ssr_align(*_args(tgt_side), _vp(lens_h), n_t, *_args(est_side), _vp(elens_h), _vp(idx_h), n_g, L, int(subsample),
+                                     _vp(rows), _vp(out) if out is not None and out.numel() else None, _vp(out_off), _vp(c), _vp(ws),
+                                     ws_bytes, _stream()))
+            got.append((members, _take(rows), _take(c) if return_corr else None))
+
+    def collect_rows():
+        full = np.empty((n_e, ALIGN_COLUMNS))
+        for members, r, _ in got:
+            full[members] = r()
+        return full
+
+    def collect_corr():
+        full = np.empty((n_e, 2 * L + 1))
+        for members, _, c in got:
+            full[members] = c()
+        return full
+    if deferred:
+        return collect_rows, shifted, (collect_corr if return_corr else None)
+    return collect_rows(), shifted, (collect_corr() if return_corr else None)
+
+
 # ---- distribution: Fréchet and kernel distance of embedding sets (DESIGN §25) ---------------------------------------------------------
 DISTRIBUTION_MAX_DIM = 1024              # SSR_DISTRIBUTION_MAX_DIM
 DISTRIBUTION_MAX_GAMMA = 8               # SSR_DISTRIBUTION_MAX_GAMMA

@@ -362,6 +362,20 @@ def every_key_order():
     return full_key_order() + tuple(k for f in _NEWER_FAMILIES for k in f.keys)
 
 
+# The delay stage of SSR_Eval_Helper(align=...) is no registry family: it runs in front of the metrics and changes what they see.  What
+# it adds to a key's result sits behind the families' keys: the delay taken out, in samples at evaluation_sr, and the normalised
+# correlation at that delay.
+ALIGN_KEYS = ("delay", "align_corr")
+
+
+def _align_option(v):
+    """(max_lag, subsample) of the `align` option, or ValueError: True, or a non-empty dict of 'max_lag' and / or 'subsample'."""
+    if v is not True and (not isinstance(v, dict) or not v or set(v) - {"max_lag", "subsample"}):
+        raise ValueError("align must be None, True or a dict of 'max_lag' and / or 'subsample'")
+    q = v if isinstance(v, dict) else {}
+    return B.check_align_lag(q.get("max_lag", B.ALIGN_LAG)), B.check_align_subsample(q.get("subsample", False))
+
+
 def key_cutoff_hz(key):
     """Cutoff in Hz of a degradation key: the integer after the tag, floor-divided by 2 - what preprocess passed to lowpass()
     (proc_bw_8000_4_44100 -> 4000, proc_fft_44099_44100 -> 22049: the sr - 1 quirk).  proc_mp3_* carries none: None."""
@@ -438,7 +452,7 @@ class SSR_Eval_Helper:
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
                  quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None,
-                 distribution=None, coherence=None, csii=None, auditory=None, modulation=None, loudness=None, bandwidth=None):
+                 distribution=None, coherence=None, align=None, csii=None, auditory=None, modulation=None, loudness=None, bandwidth=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -522,6 +536,14 @@ class SSR_Eval_Helper:
         cutoff: NaN) - all invariant to the output's gain (AudioMetrics.csii_multi / csii_batch at evaluation_sr, DESIGN.md section
         26); a dict = `n_fft` (256, 512, 1024 or 2048; default 16 ms), `hop` (default n_fft // 2), `band` ((lo_hz, hi_hz) of the band
         centres kept) and / or `split` (the same split frequency in Hz for every key, mp3 included).
+        align (not in the reference): None = off, the result, its JSON and the launch sequence are what they are without the option;
+        True = the delay of every output against its target is searched within 1024 samples either way and taken out before any
+        metric sees the output (AudioMetrics.align_batch at evaluation_sr, after the resampling): the shift
+        is a copy by whole samples, zero-filled at the edge the output is moved away from, the target is never cropped, and every
+        key also gets delay, the delay taken out in samples (positive: the output was late), and align_corr, the normalised
+        cross-correlation at that delay (NaN for digital silence: nothing is shifted); a dict = `max_lag` (1 .. 4096 samples) and /
+        or `subsample` (True: the shift is by the whole samples plus the parabola's sub-sample estimate, through a 33-tap windowed
+        sinc, and delay holds both).  save_processed_result keeps the aligned output.
         iir_exact (not in the reference): True = the setting_lowpass_filtering keys come from the kernel that is bit-identical to
         scipy.signal.sosfiltfilt; False = from the segment-parallel kernel (backend.sosfiltfilt_multi(exact=False): the same filter
         within 1e-10 of each signal's peak, not SciPy's bits; measured times: DESIGN.md section 14).
@@ -530,6 +552,8 @@ class SSR_Eval_Helper:
         result["confidence"] = {"settings": {...}, "averaged": {key: {metric: {"se", "lo", "hi"}}}}, the percentile bootstrap of the
         "averaged" block (ssr_eval_amd.stats.bootstrap_ci)."""
         self.bootstrap = None if bootstrap is None else bootstrap_option(bootstrap)
+        self.align = align
+        self._align = None if align is None else _align_option(align)
         self.distribution = None if distribution is None else check_distribution_option(distribution)
         self._last_embeddings = None
         if not isinstance(iir_exact, bool):
@@ -831,6 +855,11 @@ class SSR_Eval_Helper:
                     ys = B.resample_poly([all_proc[i] for i in idx], self.evaluationset_sr, self.model_output_sr, self._device)
                     for i, y in zip(idx, ys):
                         all_proc[i] = y                             # stays in HBM: the metric stage is the only consumer
+        # the delay stage: the outputs are replaced by their compensated copies (device views of one buffer per dtype, one call per
+        # dtype); the delays stay on the device until the batch's values are collected
+        delays = None
+        if self._align is not None and all_proc:
+            all_proc, delays = self.audio_metrics.align_batch(all_proc, all_tgt, *self._align, resident=True, deferred=True)
         values, K, multi = None, 0, False
         if all_proc:
             counts = collections.Counter(owner)
@@ -881,6 +910,10 @@ class SSR_Eval_Helper:
                 for flat in queued:
                     for v, x in zip(vals, flat()):
                         v.update(x)
+                if delays is not None:
+                    for v, d in zip(vals, delays()):
+                        v[ALIGN_KEYS[0]] = d["delay"] + (d["delay_frac"] if self._align[1] else 0.0)
+                        v[ALIGN_KEYS[1]] = d["align_corr"]
                 for i, k, v, e in zip(owner, all_keys, vals, all_extra):
                     v.update(e)                                 # the testee's extra metrics last, as the reference's update
                     results[i][k] = v
@@ -1047,7 +1080,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = every_key_order()
+        order_keys = every_key_order() + ALIGN_KEYS
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

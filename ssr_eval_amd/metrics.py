@@ -41,6 +41,7 @@ _NSIM_NAMES = ("nsim", "nsim_hf", "nsim_lf")                                    
 _MOD_NAMES = ("srmr", "srmr_diff", "mod_dist", "mod_dist_hf", "mod_dist_lf")              # the estimate's srmr, then ssr_modulation's pair columns
 _CSII_NAMES = ("csii", "csii_low", "csii_mid", "csii_high", "i3", "csii_hf", "csii_mid_hf")      # columns 0 .. 5 and 7 of ssr_csii
 _CSII_COLUMNS = (0, 1, 2, 3, 4, 5, 7)
+_ALIGN_NAMES = ("delay", "delay_frac", "align_corr", "align_edge")                        # the columns of ssr_align
 _CSII_COUNT_NAMES = ("n_segments", "n_low", "n_mid", "n_high")                            # columns 9 .. 12
 
 
@@ -1228,6 +1229,52 @@ class AudioMetrics:
         ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
         split_hz = _tile_key_splits(split_hz, K, n)
         return _regroup(self.csii_batch(ests, tgts, split_hz, n_fft, hop, band, names, return_bands, return_counts, resident, True), n, K, deferred)
+
+    # ---- delay estimation and compensation (not in the reference): a stage in front of the metrics, no metric family.
+    # The estimate's delay against the target within +- max_lag samples by a float64 cross-correlation, and the estimate with that
+    # delay taken out (zero-filled at the edge it is shifted away from); the two signals need not be equally long
+    @staticmethod
+    def _align_dicts(rows):
+        return [{_ALIGN_NAMES[0]: float(r[0]), _ALIGN_NAMES[1]: float(r[1]), _ALIGN_NAMES[2]: float(r[2]), _ALIGN_NAMES[3]: float(r[3])} for r in rows]
+
+    def align(self, est, target, max_lag=B.ALIGN_LAG, subsample=False):
+        """-> (the estimate with its delay against `target` taken out, an ndarray of the estimate's dtype and length; {'delay': d*
+        in samples, positive where the estimate is late, 'delay_frac': the parabola's sub-sample estimate in [-0.5, 0.5],
+        'align_corr': the normalised correlation at d*, 'align_edge': 1.0 where |d*| = max_lag}).  subsample: the shift is by d* +
+        delay_frac through a 33-tap windowed sinc; otherwise by d*, a copy.  Digital silence on either side: delay 0, NaN
+        align_corr, the estimate as it is."""
+        aligned, dicts = self.align_batch([est], [target], max_lag, subsample)
+        return aligned[0], dicts[0]
+
+    def delay(self, est, target, max_lag=B.ALIGN_LAG):
+        """The dict of align() alone: nothing is shifted."""
+        _check_1d([est, target])
+        tgts, index = _shared_targets([target])
+        rows, _, _ = B.align(tgts, [est], index, max_lag, False, False, self._device, shift=False)
+        return self._align_dicts(rows)[0]
+
+    def align_batch(self, ests, targets, max_lag=B.ALIGN_LAG, subsample=False, resident=False, deferred=False):
+        """align() for lists of pairs in one ssr_align call per estimate dtype -> (the aligned estimates, the dicts).  A target object
+        passed for several pairs appears once in the call.  resident: the aligned estimates stay device tensors, views of one buffer
+        per dtype (otherwise ndarrays).  deferred: the dicts are a function that returns them; nothing waits for the delays - the
+        shift reads them from device memory."""
+        n = min(len(ests), len(targets))
+        ests, targets = list(ests[:n]), list(targets[:n])
+        _check_1d(ests + targets)
+        tgts, index = _shared_targets(targets)
+        rows, shifted, _ = B.align(tgts, ests, index, max_lag, subsample, False, self._device, deferred=True)
+        if not resident:
+            shifted = [z.cpu().numpy() for z in shifted]
+        dicts = lambda: self._align_dicts(rows())      # noqa: E731
+        return shifted, (dicts if deferred else dicts())
+
+    def align_multi(self, ests_by_key, targets, max_lag=B.ALIGN_LAG, subsample=False, resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> (K lists of n
+        aligned estimates, n lists of K dicts).  Only the estimates are shifted; a target is named once for its K estimates and is
+        never cropped."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        shifted, dicts = self.align_batch(ests, tgts, max_lag, subsample, resident, True)
+        return [[shifted[i * K + k] for i in range(n)] for k in range(K)], _regroup(dicts, n, K, deferred)
 
     # ---- mel-spectrogram distances (not in the reference; DESIGN §11): on this rate's magnitude image, NVSR's 128-band HTK mel
     # front end by default.  **mel: n_mels, f_min, f_max, norm, mel_scale (torchaudio's melscale_fbanks), n_cep (mcd).
