@@ -170,6 +170,10 @@ template <typename T, bool SUMS> struct SsrWaveRegs {
   cx<T> tw2[12];             // w^j, w^2j, w^4j of the four third-pass butterflies: requested while the second one is (k_stft_wave: at
                              // the top of pass 1)
   double lsd_total;          // lane 0: sum over the chunk's frames of the per-frame LSD
+  // STASH (ssr_stft_wave_body): frame `it` of a chunk belongs to lane it & 63, which holds what lane 0 used to finish frame by
+  // frame until the next flush - the frame's wave sum of LSD terms without the Nyquist bin's, and the frame's Z[1024]
+  double lsd_frame;
+  cx<T> nyq;
 };
 
 template <typename T, bool SPLIT> struct SsrWaveLds {
@@ -344,9 +348,69 @@ template <typename REGS> SSR_DEV void ssr_wave_flags(REGS& R, int tid, int* nz, 
   SSR_WAVE_ANY_STORE(tid, orb != 0u, nz + 2 + par);
 }
 
+// ---- one-lane work taken out of the frame loop (STASH): lane 0's value for every lane, and wave sums that land in a register.
+// Device: v_readfirstlane / a DPP sum handed to every lane by v_readlane (ssr_wave_sum_dpp).  Host emulation: the lanes of a phase run one after
+// the other in ascending order, so lane 0 leaves its value in `slot` for the others, and a wave sum is complete only when the
+// phase is over - it goes through LDS scratch and lands in a phase of its own (SSR_W_SUM_LAND; nothing on the device).
+#ifdef SSR_HOST_EMU
+template <typename V> SSR_DEV V ssr_wave_first(int tid, V v, V& slot) { if ((tid & 63) == 0) slot = v; return slot; }
+// SSR_W_SUM(tid, val, sc, lane_ok, dst, OP), inside a phase, then SSR_W_SUM_LAND(blk, regs, cond, sc, lane_ok, dst, OP) right behind that
+// phase with the same last four arguments: in the lanes where `lane_ok` holds, `dst OP (sum of val over the wave)` - OP is = or +=.
+// The device does it in SSR_W_SUM and SSR_W_SUM_LAND is empty; the host sums into sc[0] in SSR_W_SUM and applies OP in SSR_W_SUM_LAND
+// (where `cond` is the condition under which SSR_W_SUM was reached).
+#define SSR_W_SUM(tid, val, sc, lane_ok, dst, OP) SSR_WAVE_SUM_STORE(tid, 64, val, sc)
+#define SSR_W_SUM_LAND(blk, regs, cond, sc, lane_ok, dst, OP) SSR_WPHASE(blk, regs, if ((cond) && (lane_ok)) dst OP (sc)[0])
+#else
+SSR_DEV float ssr_wave_first(int, float v, float&) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+SSR_DEV double ssr_wave_first(int, double v, double&) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+// The wave sum by data-parallel-primitive moves instead of ssr_wave_sum's six ds_bpermute round trips (each a dependent LDS access at
+// the very end of a frame, with nothing left to cover it): an inclusive scan inside each row of 16 lanes (row_shr 1, 2, 4, 8, lanes
+// without a source read 0), then lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast:15), then lane 31 into rows 2 and 3
+// (row_bcast:31) - lane 63 holds the sum, and v_readlane hands it to every lane.  Two 32-bit moves and one addition per step.
+template <int CTRL, int ROWS> SSR_DEV double ssr_wave_dpp(double v) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, ROWS, 0xf, true);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, ROWS, 0xf, true);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+SSR_DEV double ssr_wave_sum_dpp(double v) {
+  v += ssr_wave_dpp<0x111, 0xf>(v);
+  v += ssr_wave_dpp<0x112, 0xf>(v);
+  v += ssr_wave_dpp<0x114, 0xf>(v);
+  v += ssr_wave_dpp<0x118, 0xf>(v);
+  v += ssr_wave_dpp<0x142, 0xa>(v);
+  v += ssr_wave_dpp<0x143, 0xc>(v);
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, 63);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), 63);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+#define SSR_W_SUM(tid, val, sc, lane_ok, dst, OP) do { const double s_ = ssr_wave_sum_dpp(val); if (lane_ok) dst OP s_; } while (0)
+#define SSR_W_SUM_LAND(blk, regs, cond, sc, lane_ok, dst, OP)
+#endif
+
+// log10(0 / e^2 + 1e-12)^2: the LSD term of a bin whose target magnitude is exactly 0 (log10 of float32 1e-12 is -12 to 2e-9)
+constexpr double SSR_W_LSD_OF_ZERO = 144.0;
+
 // grid = n_items * n_chunks workgroups of ONE wave; PAIR mode, direct 2048-point engine, float32 signals.
 // MAG: 1 / 0 = magnitude rows are / are not written (p.out_kind == SSR_OUT_MAG known at compile time), -1 = decided at run time.
-template <typename T, bool SUMS, bool SPLIT, int MAG = -1, typename BLK>
+// STASH: what only lane 0 did in every frame - the float64 division and square root that close the previous frame's LSD, and the
+// Nyquist bin Z[1024] with its two stores under a lane condition - is done once per 64 frames by all lanes at once.  Frame `it`
+// belongs to lane it & 63: a frame leaves its wave sum of LSD terms (R.lsd_frame) and lane 0's register 4 (R.nyq) with its owner,
+// and the FLUSH behind every block of 64 frames (and behind a chunk's last, shorter block) evaluates the 64 Nyquist bins, closes
+// the 64 frames' LSD and stores column 1024 of the 64 rows, wave-uniformly.  The frame's LSD sum receives its Nyquist term last,
+// and frame values are added by wave reduction: results move at round-off level, magnitude rows not at all.
+// STASH = false is the frame-by-frame code (the host tests compare the two).  The float64 variants with running sums keep it: they
+// stand at 256 VGPRs, and the stash's six more spill (7 and 13 registers, 32 and 48 B of scratch).
+template <typename T, bool SUMS> constexpr bool ssr_stft_wave_stash() { return !(SUMS && sizeof(T) == 8); }
+template <typename T, bool SUMS, bool SPLIT, int MAG = -1, bool STASH = ssr_stft_wave_stash<T, SUMS>(), typename BLK>
 SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk, int item, char* lds_base) {
   constexpr int N = SSR_W_N, F = N / 2 + 1;
   // (the magnitude rows staged through LDS and stored as 16-byte writes instead - 136 -> 112 vector-memory instructions per frame
@@ -377,6 +441,7 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
   SSR_REGS(Regs, regs, blk);
   SSR_WPHASE(blk, regs, {
     R.lsd_total = 0.0;
+    R.lsd_frame = 0.0; R.nyq = {(T)0, (T)0};
     if constexpr (SUMS) for (int q = 0; q < 6; ++q) lsum[64 * q + tid] = 0.0;
     if (tid == 0) L.sc1[0] = 0.0;
     if (u0 < u1) {
@@ -387,129 +452,186 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
   });
 
   BLK blk0 = blk;
-  for (int u = u0, it = 0; u < u1; u += S, ++it) {
-    // The lane's table values (twiddles) and addresses are loop-invariant, and 128 + 64 registers of data and
-    // prefetched samples leave no room to keep them: with the lane index opaque the optimiser cannot hoist them out of the
-    // loop (it would, and then shuffle some 250 values through the accumulator registers every frame).  Table values are
-    // re-requested from L1 / L2 a pass before they are needed; LDS slots are four per-lane bases plus immediates.
-    blk = blk0; ssr_launder(blk);
+  const int64_t OP = p.out_pitch ? p.out_pitch : F;      // floats between output rows
+  // STASH: blocks of 64 frames (units ub, ub + S, ... < ue; the chunk's frames it0 ...), a flush behind each.  Otherwise one block.
+  for (int ub = u0, it0 = 0; ub < u1; it0 += 64) {
+    const int ue = (STASH && ub + 64 * S < u1) ? ub + 64 * S : u1;
+    // (only the host emulation's ssr_wave_first uses it: lane 0's register 4 on its way to the frame's owner)
+    [[maybe_unused]] cx<T> nyq0 = {(T)0, (T)0};
+    for (int u = ub, it = it0; u < ue; u += S, ++it) {
+      // The lane's table values (twiddles) and addresses are loop-invariant, and 128 + 64 registers of data and
+      // prefetched samples leave no room to keep them: with the lane index opaque the optimiser cannot hoist them out of the
+      // loop (it would, and then shuffle some 250 values through the accumulator registers every frame).  Table values are
+      // re-requested from L1 / L2 a pass before they are needed; LDS slots are four per-lane bases plus immediates.
+      blk = blk0; ssr_launder(blk);
 #define VT vt
-    // ---- pass 0: window, radix-32 DFT in registers (Stockham pass with stride 1: no twiddle).  Lane 0 also closes the
-    // previous frame's LSD.
-    SSR_WPHASE(blk, regs, {
-      ssr_wave_flags(R, tid, L.nz, it & 1);            // silent-frame votes of this unit, read by its epilogue
-      // (lane 0's branch first: behind the transform it splits the phase, and the first layer sinks below the table request)
-      if (want_lsd && it > 0 && tid == 0) R.lsd_total += sqrt(L.sc1[0] / (double)F);
-      T wl[SSR_W_P / 2];
-      ssr_touch(R.wcs.x); ssr_touch(R.wcs.y);          // a product of this point: hoisted out of the loop the 64 window values spill
-      ssr_window_from_lane(wl, R.wcs);
-      ssr_dft32_win_layer1(R.v, R.pa, R.pb, wl);
-      SSR_SCHED_BARRIER();                             // pa / pb are dead: pass 1's twiddles, a whole pass ahead of their wait
-      SSR_W_LOAD_TW1;
-      SSR_SCHED_BARRIER();
-      ssr_dft32_win_rest(R.v);
-    });
-    SSR_W_FFT_TAIL_PAIRED_EARLY(blk, blk0, regs, L);
+      // ---- pass 0: window, radix-32 DFT in registers (Stockham pass with stride 1: no twiddle).  Without STASH lane 0 also closes the
+      // previous frame's LSD.
+      SSR_WPHASE(blk, regs, {
+        ssr_wave_flags(R, tid, L.nz, it & 1);            // silent-frame votes of this unit, read by its epilogue
+        // (lane 0's branch first: behind the transform it splits the phase, and the first layer sinks below the table request)
+        if constexpr (!STASH) { if (want_lsd && it > 0 && tid == 0) R.lsd_total += sqrt(L.sc1[0] / (double)F); }
+        T wl[SSR_W_P / 2];
+        ssr_touch(R.wcs.x); ssr_touch(R.wcs.y);          // a product of this point: hoisted out of the loop the 64 window values spill
+        ssr_window_from_lane(wl, R.wcs);
+        ssr_dft32_win_layer1(R.v, R.pa, R.pb, wl);
+        SSR_SCHED_BARRIER();                             // pa / pb are dead: pass 1's twiddles, a whole pass ahead of their wait
+        SSR_W_LOAD_TW1;
+        SSR_SCHED_BARRIER();
+        ssr_dft32_win_rest(R.v);
+      });
+      SSR_W_FFT_TAIL_PAIRED_EARLY(blk, blk0, regs, L);
 #undef VT
-    // register 8 b + q holds Z[j_b + 256 q], j = tid, 64 + tid, 192 - tid, 256 - tid (lane 0: 0, 64, 192, 128) - every
-    // partner Z[2048 - k] of the lane's bins is in the lane's own registers (see SSR_W_FFT_TAIL_PAIRED).
+      // register 8 b + q holds Z[j_b + 256 q], j = tid, 64 + tid, 192 - tid, 256 - tid (lane 0: 0, 64, 192, 128) - every
+      // partner Z[2048 - k] of the lane's bins is in the lane's own registers (see SSR_W_FFT_TAIL_PAIRED).
 
-    // ---- epilogue: four groups of four bins (partner values in, magnitudes out per group: few registers live at once)
-    blk = blk0; ssr_launder(blk);
-    const int64_t OP = p.out_pitch ? p.out_pitch : F;      // floats between output rows
-    float* ra0 = p.out_a ? p.out_a + (row0 + u) * OP : nullptr;   // wave-uniform row pointers
-    float* rb0 = p.out_b ? p.out_b + (row0 + u) * OP : nullptr;
-    SSR_WPHASE(blk, regs, {
-      // UNCONDITIONAL (the last frame of a chunk re-requests a clamped, valid frame that nobody consumes): under a condition
-      // the previous contents of the 64 + 32 registers would stay live through all three passes for the path not taken.
-      // The two signals are requested at different times: 64 + 16 requests at once stop the wave at the 64th until the oldest
-      // ones have returned, i.e. expose the latency they are here to hide.
-      // All 128 data registers are live here, and a quarter of them is released per butterfly group - the first
-      // signal is requested after group 0, the second after group 1
-      SSR_SCHED_BARRIER();
-      double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      const int par = it & 1;
-      const bool a_nz = L.nonzero(0, par), b_nz = L.nonzero(1, par);
-      const bool both = a_nz && b_nz;                             // wave-uniform: the common case carries no selects
-      const bool store = MAG < 0 ? p.out_kind == SSR_OUT_MAG : MAG != 0;
-      // the two magnitude rows as buffer views: scalar row base + one lane offset + an immediate per bin (a plain pointer
-      // costs a 64-bit vector add per store)
-      const SsrRwView<float> wa(ra0, store ? F : 0), wb(rb0, (store && rb0 != nullptr) ? F : 0);   // out_b == null: the target rows
-      // are not written (ssr_pair_metrics_multi: they exist already) - the stores fall to the buffer range check
-      // byte offset of bin j_b + 256 q in a magnitude row: lane part + immediate
-      const int lane4 = 4 * tid, lane4_2 = 4 * (192 - tid), lane4_3 = 4 * ssr_wave_pj3(tid);
-      auto bin_off = [&](int b, int q) -> int {
-        return (b == 0 ? lane4 : b == 1 ? lane4 + 256 : b == 2 ? lane4_2 : lane4_3) + 1024 * q;
-      };
-      // Lane 0's butterflies 0 and 128 pair with THEMSELVES (q <-> 8 - q, bin 0 and the Nyquist bin with themselves; q <-> 7 - q):
-      // its upper halves are rotated once into the registers the general rule (3 - b, 7 - q) reads.  Register 4 - the Nyquist bin
-      // Z[1024], which pairs with itself - is taken right after group 0 (32 data registers are free by then), and only then
-      // receives its rotated value.
-      cx<T> rot4 = {(T)0, (T)0};
-      if (tid == 0) {
-        rot4 = R.v[28];
-        const cx<T> t29 = R.v[29], t30 = R.v[30], t31 = R.v[31];
-        R.v[31] = R.v[0]; R.v[30] = R.v[7]; R.v[29] = R.v[6]; R.v[28] = R.v[5];
-        R.v[7] = t31; R.v[6] = t30; R.v[5] = t29;
-      }
-      constexpr int G = 2;                                        // bins in flight (the partners are in registers - there is no
-                                                                  // LDS latency to cover)
-      // The sixteen bins, two at a time.  FAST (a compile-time fact inside each copy of the loop): both frames hold signal and
-      // the mask is the variant's full set - no zero forcing, no per-bin test of the mask, and the float32 arithmetic of a
-      // bin pair runs as packed instructions (ssr_pair_bins2_fast).  The wave-uniform choice is made ONCE per frame, outside
-      // the loop: taken per bin it split the epilogue into 48 basic blocks with two scalar branches each.
-      constexpr int PF1 = SUMS ? 1 : 0;    // the butterfly group after which the first signal is requested (then the second)
-      auto bins = [&](auto fast_tag) {
-        constexpr bool FAST = decltype(fast_tag)::value;
-        SSR_UNROLL for (int b = 0; b < 4; ++b) SSR_UNROLL for (int q0 = 0; q0 < 4; q0 += G) {
-          cx<T> zn[G];
-          SSR_UNROLL for (int q = 0; q < G; ++q) zn[q] = R.v[8 * (3 - b) + 7 - (q0 + q)];   // Z[2048 - k] out of butterfly 256 - j
-          SSR_UNROLL for (int q = 0; q < G; q += 2) {
-            const cx<T> zk0 = R.v[8 * b + q0 + q], zk1 = R.v[8 * b + q0 + q + 1];
-            f2 e, t;
-            if constexpr (FAST) {
-              ssr_pair_bins2_fast<T, SUMS>(acc, zk0, zn[q], zk1, zn[q + 1], e, t);
-            } else {
-              float e0, t0, e1, t1;
-              ssr_pair_bin<T, 0, true>(mask, acc, zk0, zn[q], a_nz, b_nz, e0, t0);
-              ssr_pair_bin<T, 0, true>(mask, acc, zk1, zn[q + 1], a_nz, b_nz, e1, t1);
-              e = f2_make(e0, e1); t = f2_make(t0, t1);
-            }
-            if (store) {
-              wa.st_raw(bin_off(b, q0 + q), e.x);
-              wa.st_raw(bin_off(b, q0 + q + 1), e.y);
-              wb.st_raw(bin_off(b, q0 + q), t.x);
-              wb.st_raw(bin_off(b, q0 + q + 1), t.y);
-            }
-          }
-          if (b == 0 && q0 + G == 4) {
-            if (tid == 0) {                                           // the Nyquist bin, then register 4's rotated value
-              const cx<T> zq = R.v[4];
-              float e, t;
-              ssr_pair_bin<T, 0, true>(mask, acc, zq, zq, a_nz, b_nz, e, t);
-              if (store) { wa.st_raw(4 * (N / 2), e); wb.st_raw(4 * (N / 2), t); }
-              R.v[4] = rot4;
-            }
-          }
-          if (b == PF1 && q0 + G == 4) {
-            SSR_SCHED_BARRIER();
-            ssr_wave_prefetch<T, 1>(p, R, tid, va, vb, u + S, n, n_frames);
-            SSR_SCHED_BARRIER();
-          }
-          if (b == PF1 + 1 && q0 + G == 4) {
-            SSR_SCHED_BARRIER();
-            ssr_wave_prefetch<T, 2>(p, R, tid, va, vb, u + S, n, n_frames);
-            SSR_SCHED_BARRIER();
-          }
+      // ---- epilogue: four groups of four bins (partner values in, magnitudes out per group: few registers live at once)
+      blk = blk0; ssr_launder(blk);
+      float* ra0 = p.out_a ? p.out_a + (row0 + u) * OP : nullptr;   // wave-uniform row pointers
+      float* rb0 = p.out_b ? p.out_b + (row0 + u) * OP : nullptr;
+      SSR_WPHASE(blk, regs, {
+        // UNCONDITIONAL (the last frame of a chunk re-requests a clamped, valid frame that nobody consumes): under a condition
+        // the previous contents of the 64 + 32 registers would stay live through all three passes for the path not taken.
+        // The two signals are requested at different times: 64 + 16 requests at once stop the wave at the 64th until the oldest
+        // ones have returned, i.e. expose the latency they are here to hide.
+        // All 128 data registers are live here, and a quarter of them is released per butterfly group - the first
+        // signal is requested after group 0, the second after group 1
+        SSR_SCHED_BARRIER();
+        double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        const int par = it & 1;
+        const bool a_nz = L.nonzero(0, par), b_nz = L.nonzero(1, par);
+        const bool both = a_nz && b_nz;                             // wave-uniform: the common case carries no selects
+        // A silent target frame: every LSD term is log10(0 / e^2 + 1e-12)^2 = SSR_W_LSD_OF_ZERO exactly, as the reference and the
+        // block engine have it.  It is added as that constant (wave-uniform, general path only) instead of 1,025 times the float32
+        // logarithm sequence's value for 1e-12, whose one rounding error (about 1 ulp) nothing would average out.
+        const int gmask = b_nz ? mask : (mask & ~SSR_M_LSD);
+        const double lsd_silent = (want_lsd && !b_nz) ? SSR_W_LSD_OF_ZERO : 0.0;
+        const bool store = MAG < 0 ? p.out_kind == SSR_OUT_MAG : MAG != 0;
+        // the two magnitude rows as buffer views: scalar row base + one lane offset + an immediate per bin (a plain pointer
+        // costs a 64-bit vector add per store)
+        const SsrRwView<float> wa(ra0, store ? F : 0), wb(rb0, (store && rb0 != nullptr) ? F : 0);   // out_b == null: the target rows
+        // are not written (ssr_pair_metrics_multi: they exist already) - the stores fall to the buffer range check
+        // byte offset of bin j_b + 256 q in a magnitude row: lane part + immediate
+        const int lane4 = 4 * tid, lane4_2 = 4 * (192 - tid), lane4_3 = 4 * ssr_wave_pj3(tid);
+        auto bin_off = [&](int b, int q) -> int {
+          return (b == 0 ? lane4 : b == 1 ? lane4 + 256 : b == 2 ? lane4_2 : lane4_3) + 1024 * q;
+        };
+        // Lane 0's butterflies 0 and 128 pair with THEMSELVES (q <-> 8 - q, bin 0 and the Nyquist bin with themselves; q <-> 7 - q):
+        // its upper halves are rotated once into the registers the general rule (3 - b, 7 - q) reads.  Register 4 - the Nyquist bin
+        // Z[1024], which pairs with itself - is taken right after group 0 (32 data registers are free by then), and only then
+        // receives its rotated value.
+        cx<T> rot4 = {(T)0, (T)0};
+        if (tid == 0) {
+          rot4 = R.v[28];
+          const cx<T> t29 = R.v[29], t30 = R.v[30], t31 = R.v[31];
+          R.v[31] = R.v[0]; R.v[30] = R.v[7]; R.v[29] = R.v[6]; R.v[28] = R.v[5];
+          R.v[7] = t31; R.v[6] = t30; R.v[5] = t29;
         }
-      };
-      constexpr int FULL = SUMS ? (SSR_M_LSD | SSR_M_LOG_SISPEC | SSR_M_SISPEC) : SSR_M_LSD;
-      if (both && (mask & 7) == FULL) bins(SsrTrue{});
-      else bins(SsrFalse{});
-      if (want_lsd) SSR_WAVE_SUM_STORE(tid, 64, acc[0], L.sc1);
-      if constexpr (SUMS)
-        for (int q = 0; q < 6; ++q) SSR_LDS_ACCUM(lsum + 64 * q + tid, acc[1 + q]);
-    });
+        constexpr int G = 2;                                        // bins in flight (the partners are in registers - there is no
+                                                                    // LDS latency to cover)
+        // The sixteen bins, two at a time.  FAST (a compile-time fact inside each copy of the loop): both frames hold signal and
+        // the mask is the variant's full set - no zero forcing, no per-bin test of the mask, and the float32 arithmetic of a
+        // bin pair runs as packed instructions (ssr_pair_bins2_fast).  The wave-uniform choice is made ONCE per frame, outside
+        // the loop: taken per bin it split the epilogue into 48 basic blocks with two scalar branches each.
+        constexpr int PF1 = SUMS ? 1 : 0;    // the butterfly group after which the first signal is requested (then the second)
+        auto bins = [&](auto fast_tag) {
+          constexpr bool FAST = decltype(fast_tag)::value;
+          SSR_UNROLL for (int b = 0; b < 4; ++b) SSR_UNROLL for (int q0 = 0; q0 < 4; q0 += G) {
+            cx<T> zn[G];
+            SSR_UNROLL for (int q = 0; q < G; ++q) zn[q] = R.v[8 * (3 - b) + 7 - (q0 + q)];   // Z[2048 - k] out of butterfly 256 - j
+            SSR_UNROLL for (int q = 0; q < G; q += 2) {
+              const cx<T> zk0 = R.v[8 * b + q0 + q], zk1 = R.v[8 * b + q0 + q + 1];
+              f2 e, t;
+              if constexpr (FAST) {
+                ssr_pair_bins2_fast<T, SUMS>(acc, zk0, zn[q], zk1, zn[q + 1], e, t);
+              } else {
+                float e0, t0, e1, t1;
+                ssr_pair_bin<T, 0, true>(gmask, acc, zk0, zn[q], a_nz, b_nz, e0, t0);
+                acc[0] += lsd_silent;
+                ssr_pair_bin<T, 0, true>(gmask, acc, zk1, zn[q + 1], a_nz, b_nz, e1, t1);
+                acc[0] += lsd_silent;
+                e = f2_make(e0, e1); t = f2_make(t0, t1);
+              }
+              if (store) {
+                wa.st_raw(bin_off(b, q0 + q), e.x);
+                wa.st_raw(bin_off(b, q0 + q + 1), e.y);
+                wb.st_raw(bin_off(b, q0 + q), t.x);
+                wb.st_raw(bin_off(b, q0 + q + 1), t.y);
+              }
+            }
+            if (b == 0 && q0 + G == 4) {
+              if constexpr (STASH) {                                    // the Nyquist bin to the frame's owner, a silent frame's
+                // part forced to zero (for this bin ar = 2 zq.x, ai = 0, br = 2 zq.y, bi = 0: what ssr_pair_bin's forcing gives); then
+                // register 4's rotated value
+                cx<T> zq = {ssr_wave_first(tid, R.v[4].x, nyq0.x), ssr_wave_first(tid, R.v[4].y, nyq0.y)};
+                if (!a_nz) zq.x = (T)0;
+                if (!b_nz) zq.y = (T)0;
+                if (tid == (it & 63)) R.nyq = zq;
+                if (tid == 0) R.v[4] = rot4;
+              } else
+              if (tid == 0) {                                           // the Nyquist bin, then register 4's rotated value
+                const cx<T> zq = R.v[4];
+                float e, t;
+                double an[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                ssr_pair_bin<T, 0, true>(mask, an, zq, zq, a_nz, b_nz, e, t);
+                if (want_lsd && t == 0.0f) an[0] = SSR_W_LSD_OF_ZERO;       // (the flush's rule: a target magnitude of exactly 0)
+                for (int i = 0; i < 7; ++i) acc[i] += an[i];
+                if (store) { wa.st_raw(4 * (N / 2), e); wb.st_raw(4 * (N / 2), t); }
+                R.v[4] = rot4;
+              }
+            }
+            if (b == PF1 && q0 + G == 4) {
+              SSR_SCHED_BARRIER();
+              ssr_wave_prefetch<T, 1>(p, R, tid, va, vb, u + S, n, n_frames);
+              SSR_SCHED_BARRIER();
+            }
+            if (b == PF1 + 1 && q0 + G == 4) {
+              SSR_SCHED_BARRIER();
+              ssr_wave_prefetch<T, 2>(p, R, tid, va, vb, u + S, n, n_frames);
+              SSR_SCHED_BARRIER();
+            }
+          }
+        };
+        constexpr int FULL = SUMS ? (SSR_M_LSD | SSR_M_LOG_SISPEC | SSR_M_SISPEC) : SSR_M_LSD;
+        if (both && (mask & 7) == FULL) bins(SsrTrue{});
+        else bins(SsrFalse{});
+        if constexpr (STASH) { if (want_lsd) SSR_W_SUM(tid, acc[0], L.sc1, tid == (it & 63), R.lsd_frame, =); }
+        else if (want_lsd) SSR_WAVE_SUM_STORE(tid, 64, acc[0], L.sc1);
+        if constexpr (SUMS)
+          for (int q = 0; q < 6; ++q) SSR_LDS_ACCUM(lsum + 64 * q + tid, acc[1 + q]);
+      });
+      if constexpr (STASH) { SSR_W_SUM_LAND(blk, regs, want_lsd, L.sc1, tid == (it & 63), R.lsd_frame, =); }
+    }
+    // ---- flush (STASH): lane l finishes frame it0 + l of the block - its Nyquist bin, its LSD, column 1024 of its two rows.  One view
+    // over the block's rows with a per-lane row offset; lanes past the block's last frame are selected out - their zero stash is not a
+    // zero term (a zero bin's LSD term is log10(1e-12)^2 = 144): they add 0.0 and store at offset -1, which the range check drops, as it
+    // drops every target store when out_b is null.  (Byte offsets are 32-bit: 63 S rows of a row pitch far below 2^20 floats.)
+    if constexpr (STASH) {
+      const int nf = (ue - ub + S - 1) / S;                  // frames in the stash, 1 .. 64
+      float* fa = p.out_a ? p.out_a + (row0 + ub) * OP : nullptr;
+      float* fb = p.out_b ? p.out_b + (row0 + ub) * OP : nullptr;
+      const int64_t span = (int64_t)(nf - 1) * S * OP + F;   // floats from the first row's start to the last row's end
+      blk = blk0; ssr_launder(blk);
+      SSR_WPHASE(blk, regs, {
+        const bool store = MAG < 0 ? p.out_kind == SSR_OUT_MAG : MAG != 0;
+        const SsrRwView<float> wa(fa, store ? span : 0), wb(fb, (store && fb != nullptr) ? span : 0);
+        const bool mine = tid < nf;
+        double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        float e, t;
+        ssr_pair_bin<T, 0, true>(mask, acc, R.nyq, R.nyq, true, true, e, t);
+        if (want_lsd && t == 0.0f) acc[0] = SSR_W_LSD_OF_ZERO;     // a silent target frame (its stash is zero): the exact term, see the epilogue
+        const int off = mine ? 4 * (tid * S * (int)OP + N / 2) : -1;
+        wa.st_raw(off, e); wb.st_raw(off, t);
+        if constexpr (SUMS)
+          for (int q = 0; q < 6; ++q) SSR_LDS_ACCUM(lsum + 64 * q + tid, mine ? acc[1 + q] : 0.0);
+        // (the division stays: 1.0 / F is not exact)
+        const double r = (want_lsd && mine) ? sqrt((R.lsd_frame + acc[0]) / (double)F) : 0.0;
+        SSR_W_SUM(tid, r, L.sc1, tid == 0, R.lsd_total, +=);
+        R.lsd_frame = 0.0; R.nyq = {(T)0, (T)0};
+      });
+      SSR_W_SUM_LAND(blk, regs, true, L.sc1, tid == 0, R.lsd_total, +=);
+    }
+    ub = ue;
   }
 
   if (part == nullptr) return;
@@ -524,7 +646,7 @@ SSR_BODY void ssr_stft_wave_body(const SsrStftParams<T>& p, BLK& blk, int chunk,
   }
   SSR_WPHASE(blk, regs, if (tid == 0) {
     double lsd = R.lsd_total;
-    if (want_lsd && u1 > u0) lsd += sqrt(L.sc1[0] / (double)F);
+    if constexpr (!STASH) { if (want_lsd && u1 > u0) lsd += sqrt(L.sc1[0] / (double)F); }
     part[0] = lsd;
     part[7] = 0.0;
   });
