@@ -799,6 +799,7 @@ int ssr_allreduce_sums(double* buf, int n, void* comm, void* stream);
 #include "../ssr_eval_amd/csrc/ssr_hip_modulation.h"
 #include "../ssr_eval_amd/csrc/ssr_hip_distribution.h"
 #include "../ssr_eval_amd/csrc/ssr_hip_align.h"
+#include "../ssr_eval_amd/csrc/ssr_hip_nmr.h"
 #include "../ssr_eval_amd/csrc/ssr_hip_csii.h"
 
 #ifdef __cplusplus

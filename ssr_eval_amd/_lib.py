@@ -34,6 +34,7 @@ DISTRIBUTION_MAX_DIM, DISTRIBUTION_MAX_GAMMA, DISTRIBUTION_MAX_PAIR_ROWS = 1024,
 DISTRIBUTION_PAIRWISE_WORKSPACE = 16640                                         # SSR_DISTRIBUTION_PAIRWISE_WORKSPACE
 CSII_BANDS, CSII_COLUMNS = 21, 13                                               # SSR_CSII_BANDS, SSR_CSII_COLUMNS
 ALIGN_MAX_LAG, ALIGN_COLUMNS = 4096, 4                                          # SSR_ALIGN_MAX_LAG, SSR_ALIGN_COLUMNS
+NMR_BANDS, NMR_COLUMNS, NMR_TABLE = 128, 6, 8                                   # SSR_NMR_BANDS, SSR_NMR_COLUMNS, SSR_NMR_TABLE
 
 _vp, _i, _i64, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
 
@@ -185,6 +186,11 @@ ALIGN_SIGNATURES = {
     "ssr_align_workspace_bytes": (_sz, [_vp, _i, _vp, _vp, _i, _i]),
     "ssr_align": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
+# name -> (restype, argtypes): exactly the symbols ssr_eval_amd/csrc/ssr_hip_nmr.h declares (include/ssr_hip.h includes it)
+NMR_SIGNATURES = {
+    "ssr_nmr_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i]),
+    "ssr_nmr": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
 
 _lib = None
 
@@ -205,7 +211,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(LOUDNESS_SIGNATURES.items()) + \
             list(SPECTRUM_SIGNATURES.items()) + list(AUDITORY_SIGNATURES.items()) + list(MODULATION_SIGNATURES.items()) + \
-            list(DISTRIBUTION_SIGNATURES.items()) + list(CSII_SIGNATURES.items()) + list(ALIGN_SIGNATURES.items()):
+            list(DISTRIBUTION_SIGNATURES.items()) + list(CSII_SIGNATURES.items()) + list(ALIGN_SIGNATURES.items()) + list(NMR_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

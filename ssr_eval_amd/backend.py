@@ -1708,6 +1708,121 @@ def csii_metrics(tgt_list, est_list, tgt_index, fs, n_fft=None, hop=None, band=N
         return _collected([_take(rows), _take(bands) if return_bands else (lambda: None)], deferred)
 
 
+# ---- nmr: the noise-to-mask ratio on the FFT ear model of BS.1387, restated ---------------------------------------------
+NMR_COLUMNS = _lib.NMR_COLUMNS           # SSR_NMR_COLUMNS: nmr, nmr_seg, rdf, nmr_hf, nmr_lf, frames
+NMR_LEVEL_DB = 92.0                      # the level of a full-scale sine in dB SPL
+NMR_DZ = 0.25                            # band width in Bark
+_NMR_DESIGNS = {}                        # (rate, n_fft, level_db) -> nmr_design's dict
+_NMR_WEIGHTS = {}                        # (rate, n_fft, level_db, device index) -> the device copy of its weights
+
+
+def nmr_default_nfft(fs):
+    """The frame length at rate fs: the smallest of PHASE_N_FFTS that holds 32 ms, 2048 where none does (256 at 8 kHz, 512 at 16 kHz,
+    1024 at 24 and 32 kHz, 2048 at 44.1 and 48 kHz).  ValueError unless fs is a number from 8 to 192 kHz."""
+    _number_in(fs, 8000.0, 192000.0, False, False, "the nmr family needs a rate from 8000 to 192000 Hz")
+    return next((n for n in PHASE_N_FFTS if n >= 0.032 * float(fs)), PHASE_N_FFTS[-1])
+
+
+def check_nmr_options(fs, n_fft, level_db):
+    """(n_fft as an int - None: nmr_default_nfft(fs) -, level_db as a float), or ValueError."""
+    default = nmr_default_nfft(fs)
+    n_fft, _ = check_coherence_frames(default if n_fft is None else n_fft, None)
+    _number_in(level_db, 0.0, 200.0, False, False, "level_db must be a number in [0, 200]")
+    return n_fft, float(level_db)
+
+
+def nmr_design(fs, n_fft=None, level_db=NMR_LEVEL_DB):
+    """Every table of DESIGN §28 at rate fs for n_fft-point frames, cached per (fs, n_fft, level_db) -> a dict: 'n_fft', 'fc' [Nc] the
+    band centres in Hz, 'weights' [n_fft // 2 + 1] = G W2 (level and ear weighting), 'bins' [Nc, 2] int32 = (k_lo, k_hi), 'table' [Nc,
+    8] = (u_lo, u_hi, Ein, c_up, ad, 1 / Bs, a, mgain) - the arrays ssr_nmr takes - and 'mask_db' [Nc], the offset m_i."""
+    n_fft, level_db = check_nmr_options(fs, n_fft, level_db)
+    fs = float(fs)
+    key = (fs, n_fft, level_db)
+    d = _NMR_DESIGNS.get(key)
+    if d is not None:
+        return d
+    N, nb = n_fft, n_fft // 2 + 1
+    k = np.arange(nb, dtype=np.float64)
+    f = k[1:] * (fs / N) / 1000.0
+    w = np.zeros(nb)
+    w[1:] = 10.0 ** ((-2.184 * f ** -0.8 + 6.5 * np.exp(-0.6 * (f - 3.3) ** 2) - 0.001 * f ** 3.6) / 10.0)
+    w *= 10.0 ** (level_db / 10.0) / (N / 4.0) ** 2
+    zl, zu = 7.0 * math.asinh(80.0 / 650.0), 7.0 * math.asinh(min(18000.0, 0.45 * fs) / 650.0)
+    Nc = int(math.ceil((zu - zl) / NMR_DZ))
+    lo = zl + NMR_DZ * np.arange(Nc)
+    hi = np.minimum(lo + NMR_DZ, zu)
+    fl, fu, fc = 650.0 * np.sinh(lo / 7.0), 650.0 * np.sinh(hi / 7.0), 650.0 * np.sinh(0.5 * (lo + hi) / 7.0)
+    width = fs / N
+    # bin k occupies [(k - 1/2), (k + 1/2)] width: a band's first and last bin and the share of each that lies inside the band
+    k_lo = np.floor(fl / width + 0.5).astype(np.int64)
+    k_hi = np.minimum(np.ceil(fu / width - 0.5).astype(np.int64), nb - 1)
+    k_hi = np.maximum(k_hi, k_lo)
+    share = lambda kk, i: max(min((kk + 0.5) * width, fu[i]) - max((kk - 0.5) * width, fl[i]), 0.0) / width      # noqa: E731
+    u_lo = np.array([share(k_lo[i], i) for i in range(Nc)])
+    u_hi = np.array([share(k_hi[i], i) for i in range(Nc)])
+    table = np.zeros((Nc, 8))
+    table[:, 0], table[:, 1] = u_lo, u_hi
+    table[:, 2] = 10.0 ** (0.1456 * (fc / 1000.0) ** -0.8)
+    table[:, 3] = -24.0 - 230.0 / fc
+    rd = 10.0 ** (-2.7 * NMR_DZ)
+    table[:, 4] = np.concatenate(([0.0], np.cumsum(rd ** np.arange(1, Nc))))
+    # Bs: the spreading of Eb = 1 in every band, in the definition's direct form
+    i_, l_ = np.arange(Nc)[:, None], np.arange(Nc)[None, :]
+    S = np.where(i_ >= l_, 10.0 ** (table[:, 3][None, :] * (i_ - l_) * NMR_DZ / 10.0), 10.0 ** (-2.7 * (l_ - i_) * NMR_DZ))
+    S = S / S.sum(axis=0, keepdims=True)
+    table[:, 5] = 1.0 / ((S ** 0.4).sum(axis=1) ** 2.5)
+    table[:, 6] = np.exp(-((N // 2) / fs) / (0.008 + (100.0 / fc) * 0.022))
+    m_db = np.where(np.arange(Nc) <= 12.0 / NMR_DZ, 3.0, 0.25 * np.arange(Nc) * NMR_DZ)
+    table[:, 7] = 10.0 ** (-m_db / 10.0)
+    d = {"n_fft": N, "level_db": level_db, "fc": fc, "weights": np.ascontiguousarray(w),
+         "bins": np.ascontiguousarray(np.stack([k_lo, k_hi], axis=1).astype(np.int32)), "table": np.ascontiguousarray(table), "mask_db": m_db}
+    _NMR_DESIGNS[key] = d
+    return d
+
+
+def nmr_metrics(tgt_list, est_list, tgt_index, fs, n_fft=None, level_db=NMR_LEVEL_DB, split_bands=None, return_bands=False,
+                return_mask=False, device=None, deferred=False):
+    """The noise-to-mask ratio of estimate e against target tgt_index[e] (ssr_nmr): waveforms at rate fs (float32 or
+    float64, each estimate as long as its target; a list holding both dtypes is widened to float64) -> (rows [n_est, 6] float64: nmr,
+    nmr_seg, rdf, nmr_hf, nmr_lf, frames; bands [n_est, Nc]: mean_t R per band, or None without return_bands; mask [the frames of all
+    targets, Nc]: the masking threshold M of every target, frame after frame in target order, or None without return_mask).  n_fft:
+    None = nmr_default_nfft(fs), or 256, 512, 1024 or 2048 (hop n_fft / 2); split_bands: None, or per estimate the first band of its
+    upper part in [0, Nc] (-1: no split).  The workspace holds 8 Nc bytes per frame of every target and 8 (Nc + 2) bytes per chunk of
+    32 frames of every pair.  Device views of one buffer are read where they lie.  deferred: a function that returns the tuple."""
+    d = nmr_design(fs, n_fft, level_db)
+    n_fft, J = d["n_fft"], d["fc"].shape[0]
+    if not isinstance(return_bands, (bool, np.bool_)) or not isinstance(return_mask, (bool, np.bool_)):
+        raise ValueError("return_bands and return_mask must be True or False")
+    tgts, ests, idx = _signal_pair_index(tgt_list, est_list, tgt_index)
+    n_t, n_e = len(tgts), len(ests)
+    sp = _split_array(split_bands, n_e, lambda s: s.min() >= -1 and s.max() <= J, "split_bands must hold -1 or a band in [0, n_bands] per estimate")
+    lib, dev = _gpu_call(device)
+    with torch.cuda.device(dev):
+        rows = torch.empty((n_e, NMR_COLUMNS), dtype=torch.float64, device=dev)
+        bands = torch.empty((n_e, J), dtype=torch.float64, device=dev) if return_bands else None
+        mask = None
+        if n_e:
+            tgt_side, est_side, tl = _signal_pair_place(tgts, ests, idx, dev)
+            lens = tl.astype(np.int32)
+            frames = int(np.where(lens >= n_fft, 1 + (lens - n_fft) // (n_fft // 2), 0).sum())
+            mask = torch.empty((frames, J), dtype=torch.float64, device=dev) if return_mask else None
+            ws_bytes = int(lib.ssr_nmr_workspace_bytes(lens.ctypes.data_as(C.c_void_p), n_t, idx.ctypes.data_as(C.c_void_p), n_e, n_fft, J))
+            ws = _workspace(ws_bytes, dev)
+            lens_h, idx_h, sp_h, bins_h = _host_i32(lens, dev), _host_i32(idx, dev), _host_i32(sp, dev), _host_i32(d["bins"], dev)
+            # the weights stay on the device for the life of the process, one table (at most 8 KB) per (rate, n_fft, level, device); the
+            # band table is read by the library out of page-locked memory, like the int32 arrays: no copy waits for the stream
+            key = (float(fs), n_fft, d["level_db"], torch.cuda.current_device())
+            w_dev = _NMR_WEIGHTS.get(key)
+            if w_dev is None:
+                w_dev = _NMR_WEIGHTS[key] = _h2d(d["weights"], dev)
+            tab_h = _DescRing.get(torch.cuda.current_device()).stage(d["table"], dev)
+            _lib.check(lib.ssr_nmr(*_args(tgt_side), _vp(lens_h), n_t, *_args(est_side), _vp(idx_h), n_e, n_fft, J, _vp(w_dev), _vp(bins_h),
+                                   _vp(tab_h), _vp(sp_h), _vp(rows), _vp(bands), _vp(mask), _vp(ws), ws_bytes, _stream()))
+        elif return_mask:
+            mask = torch.empty((0, J), dtype=torch.float64, device=dev)
+        return _collected([_take(rows), _take(bands) if return_bands else (lambda: None), _take(mask) if return_mask else (lambda: None)], deferred)
+
+
 # ---- delay estimation and compensation: a stage in front of the metrics (DESIGN §27) ----------------------------------------------------
 ALIGN_MAX_LAG = _lib.ALIGN_MAX_LAG       # SSR_ALIGN_MAX_LAG
 ALIGN_LAG = 1024                         # the default search range in samples, either way

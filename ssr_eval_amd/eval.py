@@ -22,7 +22,7 @@ from . import backend as B
 from . import dist as D
 from .lowpass import lowpass, lowpass_batch, lowpass_iir_multi, stft_hard_lowpass_multi
 from .metrics import AudioMetrics, which_mask, _BSS_NAMES, _COH_HF_NAMES, _COH_NAMES, _CSII_NAMES, _LOUD_DIFF_NAMES, _LOUD_NAMES, _MEL_DTW_NAMES, _MEL_NAMES, _MRSTFT_NAMES, \
-    _MOD_NAMES, _NSIM_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _SPEC_NAMES, _SPEC_PAIR_NAMES, _WAVE_NAMES
+    _MOD_NAMES, _NMR_NAMES, _NSIM_NAMES, _PHASE_NAMES, _PITCH_NAMES, _QUALITY_NAMES, _SPEC_NAMES, _SPEC_PAIR_NAMES, _WAVE_NAMES
 from .distribution import check_option as check_distribution_option, embed_waves, result_block as distribution_block
 from .stats import bootstrap_ci, bootstrap_option
 from .utils import dict_mean, write_json
@@ -50,6 +50,9 @@ _MOD_KEYS = _MOD_NAMES[:4]
 # of the csii family a key's result keeps the index over all segments, over the mid-level ones, the fitted I3 and the index over the
 # critical bands at or above the key's cutoff
 _CSII_KEYS = (_CSII_NAMES[0], _CSII_NAMES[2], _CSII_NAMES[4], _CSII_NAMES[5])
+# of the nmr family a key's result keeps the total noise-to-mask ratio, the share of disturbed frames and the ratio over the bands at
+# or above the key's cutoff
+_NMR_KEYS = (_NMR_NAMES[0], _NMR_NAMES[2], _NMR_NAMES[3])
 
 
 def _option_dict(value):
@@ -77,6 +80,7 @@ _SPLIT_REFUSED = {
     "auditory": lambda s: not B._is_number(s),
     "modulation": lambda s: not B._is_number(s),
     "csii": lambda s: not B._is_number(s),
+    "nmr": lambda s: not B._is_number(s),
 }
 
 
@@ -362,6 +366,32 @@ def every_key_order():
     return full_key_order() + tuple(k for f in _NEWER_FAMILIES for k in f.keys)
 
 
+def _nmr_args(h, v, keys):
+    """-> ((one split frequency per degradation key (_key_splits; None: NaN nmr_hf), n_fft, level_db), {"names": the family's keys})."""
+    q = v if isinstance(v, dict) else {}
+    return (_key_splits(q, keys), q.get("n_fft"), q.get("level_db", B.NMR_LEVEL_DB)), {"names": _NMR_KEYS}
+
+
+def _nmr_check(h, v):
+    _dict_option("nmr", v, ("n_fft", "level_db", "split"))
+    if v is not True and "n_fft" in v and v["n_fft"] is None:
+        raise ValueError("n_fft must be one of %s (leave it out for 32 ms frames)" % (B.PHASE_N_FFTS,))
+    (split, n_fft, level_db), _ = _nmr_args(h, v, ["k"])
+    h.audio_metrics._nmr_splits(h.audio_metrics._nmr_design(n_fft, level_db)["fc"], split, 1)
+
+
+# The families behind the 16 of _ALL_FAMILIES, whose count and 56 keys the tests pin: queued after them, their keys behind
+# every_key_order() and in front of ALIGN_KEYS.  A new family's row goes at the end.
+_OPEN_FAMILIES = (
+    _Family("nmr", "nmr_multi", "nmr_batch", _NMR_KEYS, _nmr_check, lambda h, keys: _nmr_args(h, h.nmr, keys), True),
+)
+
+
+def open_key_order():
+    """every_key_order(), the keys of the open families and ALIGN_KEYS behind it: the order a result lists its metrics in."""
+    return every_key_order() + tuple(k for f in _OPEN_FAMILIES for k in f.keys) + ALIGN_KEYS
+
+
 # The delay stage of SSR_Eval_Helper(align=...) is no registry family: it runs in front of the metrics and changes what they see.  What
 # it adds to a key's result sits behind the families' keys: the delay taken out, in samples at evaluation_sr, and the normalised
 # correlation at that delay.
@@ -452,7 +482,7 @@ class SSR_Eval_Helper:
                  setting_fft=None, setting_mp3_compression=None, save_processed_result=False, *,
                  precision="f64", device=None, download=False, lsd_split=None, stoi=None, waveform=None, mel=None,
                  quality=None, pitch=None, iir_exact=True, bootstrap=None, mel_dtw=None, phase=None, mrstft=None, bss_sdr=None,
-                 distribution=None, coherence=None, align=None, csii=None, auditory=None, modulation=None, loudness=None, bandwidth=None):
+                 distribution=None, coherence=None, align=None, nmr=None, csii=None, auditory=None, modulation=None, loudness=None, bandwidth=None):
         """lsd_split (not in the reference): None = off; True = every key also gets lsd_lf / lsd_hf, the LSD below / above its own
         cutoff (key_cutoff_hz; mp3 keys: NaN); a number = the same split frequency in Hz for every key, mp3 included.
         stoi (not in the reference): None = off; "stoi", "estoi" or "both" = every key also gets that intelligibility score
@@ -536,6 +566,14 @@ class SSR_Eval_Helper:
         cutoff: NaN) - all invariant to the output's gain (AudioMetrics.csii_multi / csii_batch at evaluation_sr, DESIGN.md section
         26); a dict = `n_fft` (256, 512, 1024 or 2048; default 16 ms), `hop` (default n_fft // 2), `band` ((lo_hz, hi_hz) of the band
         centres kept) and / or `split` (the same split frequency in Hz for every key, mp3 included).
+        nmr (not in the reference): None = off; True = every key also gets nmr, the total noise-to-mask ratio of the output against
+        the target in dB (the error spectrum per quarter-Bark band over the masking threshold the target itself produces - the FFT
+        ear model of ITU-R BS.1387, restated; negative = masked), rdf, the share of frames with a band at least 1.5 dB over the
+        threshold, and nmr_hf, nmr over the bands whose centre is at or above the key's own cutoff (key_cutoff_hz; mp3 keys and
+        keys with no band above the cutoff: NaN) (AudioMetrics.nmr_multi / nmr_batch at evaluation_sr); a
+        dict = `n_fft` (256, 512, 1024 or 2048; default 32 ms), `level_db` (the level of a full-scale sine in dB SPL; default 92)
+        and / or `split` (the same split frequency in Hz for every key, mp3 included).  Its keys sit behind those of every other
+        family.
         align (not in the reference): None = off, the result, its JSON and the launch sequence are what they are without the option;
         True = the delay of every output against its target is searched within 1024 samples either way and taken out before any
         metric sees the output (AudioMetrics.align_batch at evaluation_sr, after the resampling): the shift
@@ -564,8 +602,8 @@ class SSR_Eval_Helper:
         # every family option is checked here, before the caller's settings are touched (the mel checks need audio_metrics)
         options = dict(lsd_split=lsd_split, stoi=stoi, waveform=waveform, mel=mel, mel_dtw=mel_dtw, quality=quality, pitch=pitch,
                        phase=phase, mrstft=mrstft, bss_sdr=bss_sdr, coherence=coherence, loudness=loudness,
-                       bandwidth=bandwidth, auditory=auditory, modulation=modulation, csii=csii)
-        for f in _ALL_FAMILIES:
+                       bandwidth=bandwidth, auditory=auditory, modulation=modulation, csii=csii, nmr=nmr)
+        for f in _ALL_FAMILIES + _OPEN_FAMILIES:
             if options[f.option] is not None:
                 f.check(self, options[f.option])
             setattr(self, f.option, options[f.option])
@@ -879,7 +917,7 @@ class SSR_Eval_Helper:
         queued = []
         if all_proc:
             same_keys = multi and all(all_keys[i * K:(i + 1) * K] == all_keys[:K] for i in range(len(items)))
-            for f in _ALL_FAMILIES:
+            for f in _ALL_FAMILIES + _OPEN_FAMILIES:
                 if getattr(self, f.option) is None:
                     continue
                 if multi and (same_keys or not f.per_key):
@@ -1080,7 +1118,7 @@ class SSR_Eval_Helper:
             order = list(first) + sorted({k for b in box for k in b[0]} - set(first))
             mets = {m for b in box for m in b[1]}
         keys = order
-        order_keys = every_key_order() + ALIGN_KEYS
+        order_keys = open_key_order()
         mets = sorted(mets, key=lambda m: (order_keys.index(m) if m in order_keys else 99, m))
         rows = np.empty((len(local), len(keys) * len(mets)), dtype=np.float64)
         for i, r in enumerate(local):

@@ -43,6 +43,7 @@ _CSII_NAMES = ("csii", "csii_low", "csii_mid", "csii_high", "i3", "csii_hf", "cs
 _CSII_COLUMNS = (0, 1, 2, 3, 4, 5, 7)
 _ALIGN_NAMES = ("delay", "delay_frac", "align_corr", "align_edge")                        # the columns of ssr_align
 _CSII_COUNT_NAMES = ("n_segments", "n_low", "n_mid", "n_high")                            # columns 9 .. 12
+_NMR_NAMES = ("nmr", "nmr_seg", "rdf", "nmr_hf", "nmr_lf")                                # columns 0 .. 4 of ssr_nmr (column 5: frames)
 
 
 def which_mask(which, names):
@@ -1229,6 +1230,84 @@ class AudioMetrics:
         ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
         split_hz = _tile_key_splits(split_hz, K, n)
         return _regroup(self.csii_batch(ests, tgts, split_hz, n_fft, hop, band, names, return_bands, return_counts, resident, True), n, K, deferred)
+
+    # ---- nmr: is the difference audible?  The noise-to-mask ratio: the error spectrum per quarter-Bark band over the
+    # masking threshold the target itself produces (the FFT ear model of ITU-R BS.1387 after Kabal 2002, restated; no conformance
+    # is claimed, the ODG network is not built).  Negative: the error lies under the threshold
+    @staticmethod
+    def _nmr_names(names):
+        """The result keys asked for, in result order, or ValueError: None = all, or a non-empty tuple / list of them."""
+        return _names_asked(names, _NMR_NAMES)
+
+    @staticmethod
+    def _nmr_splits(fc, split, n):
+        """The first band whose centre frequency is at or above the split of n pairs, in [0, len(fc)]: split = None (no split: -1 for
+        every pair), one frequency in Hz for every pair, or a list of one per pair (None: -1 for that pair)."""
+        return _split_indices(split, n, lambda f: int(np.searchsorted(fc, f, side="left")))
+
+    def _nmr_design(self, n_fft, level_db):
+        """-> backend.nmr_design's dict: every option checked, nothing queued."""
+        return B.nmr_design(self.rate, n_fft, level_db)
+
+    def nmr(self, est, target, split_hz=None, n_fft=None, level_db=B.NMR_LEVEL_DB, names=None, return_bands=False):
+        """{'nmr', 'nmr_seg', 'rdf', 'nmr_hf', 'nmr_lf'} of one (estimate, target) pair at self.rate (8 to 192 kHz): nmr, the total
+        noise-to-mask ratio in dB - the mean over frames and quarter-Bark bands of the error power (the difference of the two
+        magnitude spectra) over the target's masking threshold, negative where the error is masked; nmr_seg, the mean over frames of
+        the frame's ratio in dB; rdf, the share of frames in which some band's ratio reaches 1.5 dB; nmr_hf / nmr_lf: nmr over the
+        bands whose centre is at or above / below split_hz (NaN without split_hz or where no such band exists).  n_fft: None = 32 ms
+        (backend.nmr_default_nfft), or 256, 512, 1024 or 2048, hop n_fft / 2; level_db: the level of a full-scale sine in dB SPL;
+        names: None, or the result keys wanted.  return_bands: also 'band_ratio' [Nc], the mean ratio per band over the frames
+        (linear), 'centre_hz' and 'frames'.  Shorter than one frame: NaN.  An estimate equal to the target: -200 and rdf 0."""
+        return self.nmr_batch([est], [target], split_hz, n_fft, level_db, names, return_bands)[0]
+
+    def nmr_batch(self, ests, targets, split_hz=None, n_fft=None, level_db=B.NMR_LEVEL_DB, names=None, return_bands=False, resident=False,
+                  deferred=False):
+        """nmr() for lists of pairs, with waveform_batch's input rules (metrics.py:89-90 truncation; float32 or float64 signals, read
+        in their own dtype: one ssr_nmr call per (target dtype, estimate dtype) group).  The masking threshold of a target object
+        passed for several pairs is made once.  split_hz: None, one frequency for every pair, or a list of one per pair (None: that
+        pair's nmr_hf and nmr_lf are NaN).  deferred: as evaluation_batch."""
+        d = self._nmr_design(n_fft, level_db)
+        fc = d["fc"]
+        if not isinstance(return_bands, bool):
+            raise ValueError("return_bands must be True or False")
+        keys = self._nmr_names(names)
+        n = min(len(ests), len(targets))
+        splits = self._nmr_splits(fc, split_hz, n)
+
+        def call(tgts, es, index, idx):
+            return B.nmr_metrics(tgts, es, index, self.rate, d["n_fft"], d["level_db"], [splits[i] for i in idx], return_bands, False, self._device,
+                                 deferred=True)
+
+        def dicts(vals):
+            rows, bands, _ = vals
+            out = []
+            for j, row in enumerate(rows):
+                q = {k: float(row[c]) for c, k in enumerate(_NMR_NAMES) if k in keys}
+                if return_bands:
+                    q["band_ratio"], q["centre_hz"], q["frames"] = np.array(bands[j]), np.array(fc), int(row[5])
+                out.append(q)
+            return out
+        _check_1d(list(ests[:n]) + list(targets[:n]))
+        return self._pairs((call, dicts), ests[:n], targets[:n], resident, deferred, by_dtype=True, per_pair=True)
+
+    def nmr_multi(self, ests_by_key, targets, split_hz=None, n_fft=None, level_db=B.NMR_LEVEL_DB, names=None, return_bands=False,
+                  resident=False, deferred=False):
+        """K estimates per target, as evaluation_multi: ests_by_key = K lists of n waveforms, targets = n waveforms -> n lists of K
+        dicts.  split_hz: None, one frequency for every key, or a list of one per key (None: NaN).  The K pairs of a target sit next
+        to each other in one call and the target's masking threshold is made once."""
+        ests, tgts, n, K = _flat_pairs(ests_by_key, targets)
+        split_hz = _tile_key_splits(split_hz, K, n)
+        return _regroup(self.nmr_batch(ests, tgts, split_hz, n_fft, level_db, names, return_bands, resident, True), n, K, deferred)
+
+    def masking_threshold(self, wav, n_fft=None, level_db=B.NMR_LEVEL_DB):
+        """(mask [T, Nc] float64, centre_hz [Nc]): the masking threshold of one signal at self.rate in dB (the level scale of
+        level_db), per frame of n_fft samples every n_fft / 2 (T = 1 + (len - n_fft) // (n_fft // 2), no padding) and quarter-Bark
+        band.  The call scores the signal against itself: ssr_nmr queues nothing without an estimate, so the noise and score kernels run
+        too - about 60 % on top of the excitation and mask kernels' time - and their result is dropped."""
+        d = self._nmr_design(n_fft, level_db)
+        wav = self._loudness_signal(wav)
+        _, _, mask = B.nmr_metrics([wav], [wav], [0], self.rate, d["n_fft"], d["level_db"], None, False, True, self._device)
+        return 10.0 * np.log10(mask), np.array(d["fc"])
 
     # ---- delay estimation and compensation (not in the reference; DESIGN §27): a stage in front of the metrics, no metric family.
     # The estimate's delay against the target within +- max_lag samples by a float64 cross-correlation, and the estimate with that
